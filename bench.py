@@ -1,9 +1,18 @@
 #!/usr/bin/env python
 """bench.py -- cost-volume Mvoxels/s of the fused RPC warp + variance build on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, pre-warm + --warmup steps, time --steps steps, write the outputs
+(--dump-outputs), print the JSON line (metric, value, unit, ms_per_step, config, devices).  Everything else -- the roofline
+(the build kernel timed on its own), the exchange's own timings at N > 1, the side workloads under "extra" and the CPU
+baselines -- runs only with --full (--no-extra / --no-cpu-baseline still leave out those two parts there).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step handed its caller, the float32 variance
+volume (of its plane shard at N > 1), as a fixed sample (dump_outputs()); the inputs are seeded, so two builds of the
+library run with the same arguments can be compared file for file.
 
 Metric (BASELINE.json): cost-volume Mvoxels/s = B*D*H*W / t for the fused warp + variance build,
 3-view, 768x384 planes, 64 height hypotheses, C=32 feature channels (configs[1], the shape the
@@ -18,10 +27,10 @@ partials (satmvs_amd/shard.py), inside the timed region; its stand-alone time is
 "exchange".  `value` is always the whole tile's voxels / step time.
 
 Before anything is timed the kernel is launched for --prewarm-seconds of wall clock (default 0.6 s)
-so that a short --warmup still measures steady clocks.  "extra" carries short runs of the other
+so that a short --warmup still measures steady clocks.  With --full, "extra" carries short runs of the other
 BASELINE shapes (cfg4 5-view shard, stage-3 C=8 planes, cfg5 homography volume, cfg3 cascade forward).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     HBM roofline of the dominant kernel: algorithmic bytes (138.25 B/voxel: 4*C write +
                4 height read + 4*C*V/D feature reads) / mean launch time from HIP events
                recorded on the launch stream, against the 8 TB/s HBM3E peak.
@@ -198,6 +207,27 @@ def time_steps(step, steps, barrier=lambda: None):
     barrier()
     elapsed = time.perf_counter() - t0
     return elapsed, float(np.mean([a.elapsed_time(b) for a, b in ev]))
+
+
+DUMP_SAMPLE = 1 << 23           # voxels of the volume in volume_sample.npy: 32 MB of float32
+DUMP_CORNER = (16, 64)          # rows x columns of the image corner in volume_corner.npy, every channel and plane
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the (1,C,D,H,W) float32 volume the last timed step wrote (2.4 GB at cfg2) as two files, 40 MB at cfg2:
+      volume_sample.npy  out.view(-1) at DUMP_SAMPLE flat indices drawn by torch.randint from a CPU generator seeded 0, sorted
+                         (the same indices for the same arguments), shape (DUMP_SAMPLE,)
+      volume_corner.npy  out[0, :, :, :16, :64], the image corner, where the source taps leave the views (shape (C, D, 16, 64))"""
+    os.makedirs(dirname, exist_ok=True)
+    flat = out.view(-1)
+    n = min(DUMP_SAMPLE, flat.numel())
+    g = torch.Generator(device="cpu").manual_seed(0)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g, dtype=torch.int64).sort().values
+    sample = flat[idx.to(out.device)].cpu().numpy()
+    r, c = DUMP_CORNER
+    corner = out[0, :, :, :r, :c].cpu().numpy()
+    np.save(os.path.join(dirname, "volume_sample.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(dirname, "volume_corner.npy"), np.ascontiguousarray(corner, dtype=np.float32))
 
 
 def rank_identities(dist, dev, world, rank, one_device):
@@ -587,10 +617,16 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="cfg2_rpc_3view_768x384x64_c32", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side workloads reported under \"extra\"")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, exchange timings, \"extra\", CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the volume the last timed step computed to DIR/*.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side workloads reported under \"extra\"")
     ap.add_argument("--prewarm-seconds", type=float, default=0.6)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -656,15 +692,20 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed, _ = time_steps(step, args.steps, barrier)
-    # the dominant kernel alone (no fold, no exchange) for the roofline: HIP events around each launch; and fold + build together
-    _, kern_ms = time_steps(kernel, min(args.steps, 100))
-    _, both_ms = time_steps(launch, min(args.steps, 100))
+    if args.dump_outputs and rank == 0 and D_local > 0:
+        dump_outputs(args.dump_outputs, out)
+    kern_ms = both_ms = None
+    if args.full:
+        # the dominant kernel alone (no fold, no exchange) for the roofline: HIP events around each launch; and fold + build together
+        _, kern_ms = time_steps(kernel, min(args.steps, 100))
+        _, both_ms = time_steps(launch, min(args.steps, 100))
 
     exchange = None
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dist is not None and args.full:
         _, ex_ms = time_steps(lambda: shard.allreduce_regression_state(state), 20, barrier)
 
         # the same steps with the exchange IN stream order (build -> exchange -> next build): single-tile latency, beside the
@@ -688,7 +729,7 @@ def main():
 
     ids = rank_identities(dist, dev, world, rank, one_device)   # collective: every rank takes part
     cfg4 = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         del out
         torch.cuda.empty_cache()
         cfg4 = cfg4_strong(dev, stream, rank, world, dist, barrier)     # collective: every rank takes part
@@ -696,8 +737,6 @@ def main():
     if rank == 0:
         vox_per_step = D * H * W                              # the whole tile, whatever the rank count
         ms_per_step = elapsed / args.steps * 1e3
-        bpv = algorithmic_bytes_per_voxel(V, C, D)
-        achieved = bpv * D_local * H * W / (kern_ms * 1e-3) / 1e9
         line = {
             "metric": "cost-volume Mvoxels/s (fused RPC warp + variance build)",
             "value": round(vox_per_step / (elapsed / args.steps) / 1e6, 1),
@@ -711,23 +750,26 @@ def main():
                        "planes_total": D, "H": H, "W": W, "depth_values": "per-voxel (B,D,H,W)",
                        "sharding": "height planes of one tile split over the ranks, regression partials exchanged each step (overlapping the next step's build when N > 1)",
                        "prewarm_seconds": args.prewarm_seconds},
-            "roofline": {"bound": "hbm", "kernel": kernel_name(V, C, D_local),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": measured_traffic(args.workload) if world == 1 else None,
-                         "bytes_per_voxel": bpv, "kernel_ms": round(kern_ms, 4), "fold_plus_kernel_ms": round(both_ms, 4),
-                         "note": ("one step = smvs_rpc_plane_coef (fold of the source cubics per plane, 3-5 us) + smvs_rpc_costvol_fwd_pc; `value` and "
-                                  "ms_per_step time both, kernel_ms / achieved / frac are the build kernel alone (HIP events on its stream)") if use_pc else
-                                 "one step = smvs_rpc_costvol_fwd (a shard below 8 Mi voxels is not worth the fold's launch: variance_cost_volume's rule)"},
         }
+        if args.full:
+            bpv = algorithmic_bytes_per_voxel(V, C, D)
+            achieved = bpv * D_local * H * W / (kern_ms * 1e-3) / 1e9
+            line["roofline"] = {"bound": "hbm", "kernel": kernel_name(V, C, D_local),
+                                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": measured_traffic(args.workload) if world == 1 else None,
+                                "bytes_per_voxel": bpv, "kernel_ms": round(kern_ms, 4), "fold_plus_kernel_ms": round(both_ms, 4),
+                                "note": ("one step = smvs_rpc_plane_coef (fold of the source cubics per plane, 3-5 us) + smvs_rpc_costvol_fwd_pc; `value` and "
+                                         "ms_per_step time both, kernel_ms / achieved / frac are the build kernel alone (HIP events on its stream)") if use_pc else
+                                        "one step = smvs_rpc_costvol_fwd (a shard below 8 Mi voxels is not worth the fold's launch: variance_cost_volume's rule)"}
         line["devices"] = ids
         if exchange is not None:
             line["exchange"] = exchange
             line["exchange_overlapped"] = True              # `value` is tile-stream throughput; exchange.ms_per_step_not_overlapped is the single-tile latency
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             line["extra"] = {"cfg4_strong_scaling": cfg4}
             if world == 1:
                 line["extra"].update(side_workloads(dev, stream))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(V, C, D, H, W)
             line["cpu_baseline_torch"] = cpu_baseline_torch(V, C, D, H, W)
         print(json.dumps(line))

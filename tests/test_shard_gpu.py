@@ -159,7 +159,7 @@ def test_bench_two_rank_rehearsal_on_one_device(tmp_path):
     env = dict(os.environ, SMVS_BENCH_ONE_DEVICE="1", SMVS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--prewarm-seconds", "0.05"]
+           "--prewarm-seconds", "0.05", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ TAG=${1:-r01_final}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-python $REPO/bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python $REPO/bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 bash $REPO/tools/profile.sh $TAG > "$OUT/profile_sh.log" 2>&1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d "$OUT/trace_cascade" -o trace -- python $REPO/tools/bench_pred.py > "$OUT/cascade.log" 2>&1

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/restamp
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-extra --steps 3 --warmup 1 --prewarm-seconds 0.05"
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-extra --steps 3 --warmup 1 --prewarm-seconds 0.05"
 for set in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $set -d "$OUT/pmc_$set" -o pmc -- $BENCH > "$OUT/pmc_$set.log" 2>&1 || echo "failed: $set" >> "$OUT/errors.log"
 done
