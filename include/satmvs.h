@@ -510,6 +510,31 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
                      void* workspace, size_t workspace_bytes, int N, int H, int W, int base_channels, int arch,
                      void* stream);
 
+/* ---- DSM production ------------------------------------------------------------------------
+ * Per-view height maps in image space -> one height grid in map coordinates (Transverse Mercator, e.g. UTM).
+ * tm7 (HOST array): ellipsoid a [m], inverse flattening, lat0 [deg], lon0 [deg], k0, false easting, false northing [m].
+ * smvs_tm_project: USGS series (Snyder), float64.  dir 0: (lat, lon) [deg] -> (E, N) [m]; dir 1: (E, N) -> (lat, lon).
+ *   a, b, o0, o1: n doubles each (device).
+ * smvs_rpc_dsm_bin: one height map (H,W) float32 with its 170-vector; pixel (x, y) = column x, row y.  A pixel is valid where
+ *   mask (uint8, nullable) is non-zero and the height is finite; (x, y, h) -> (lat, lon) by the inverse RPC (as
+ *   smvs_rpc_project dir 0) -> (E, N).  grid4 (HOST array): E0, N0 = centre of cell (0, 0), xres, yres [m];
+ *   col = floor((E - E0) / xres + 0.5), row = floor((N0 - N) / yres + 0.5) (IEEE quotients).  cell (H*W) int32 = row * gw + col,
+ *   or -1 (invalid or off the grid); count (gw*gh) uint32 ACCUMULATED over calls (zero-filled by the caller once per DSM);
+ *   east / north (H*W) float64, both or neither, NaN where the pixel is invalid.
+ * smvs_dsm_reduce: cell / height = the concatenated outputs of every bin call of one DSM (n points), count = their counts.
+ *   Every cell's heights are sorted on the order-preserving uint32 image of the float and reduced: mode 0 median (mean of the
+ *   two middle values in float64 for even counts), 1 mean (float64 sum in an order fixed by the count), 2 min, 3 max; empty
+ *   cells get nodata.  dsm (gh, gw) float32.  The result is bit-identical from run to run and under any permutation of the
+ *   points.  workspace: smvs_dsm_workspace_bytes(n, gw, gh) bytes (0 = unsupported sizes).
+ * Limits: n < 2^31 per reduce, gw * gh < 2^31 cells, positive sizes and resolutions. */
+int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
+int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
+                     const double* tm7, const double* grid4, int gw, int gh,
+                     int* cell, unsigned* count, double* east, double* north, void* stream);
+size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh);
+int smvs_dsm_reduce(const int* cell, const float* height, size_t n, const unsigned* count, int gw, int gh,
+                    int mode, float nodata, float* dsm, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

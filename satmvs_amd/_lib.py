@@ -75,12 +75,16 @@ _SIGNATURES = {
     "smvs_costreg_fwd": [_vp, _vp, _vp, _vp, _sz] + [_i] * 5 + [_vp],
     "smvs_featnet_pack_weights": [_vp, _i, _i, _vp, _vp],
     "smvs_featnet_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _sz] + [_i] * 5 + [_vp],
+    "smvs_tm_project": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp],
+    "smvs_rpc_dsm_bin": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "smvs_dsm_reduce": [_vp, _vp, _sz, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp],
 }
 _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": [_i], "smvs_red_workspace_bytes": [_i] * 4,
                "smvs_red_pred_workspace_bytes": [_i] * 4, "smvs_costreg_packed_floats": [_i],
                "smvs_costreg_workspace_bytes": [_i] * 5, "smvs_featnet_packed_floats": [_i] * 2,
                "smvs_featnet_workspace_bytes": [_i] * 5, "smvs_conv3x3_packed_floats": [_i] * 2,
-               "smvs_conv3d_packed_floats": [_i] * 2, "smvs_conv3d_wgrad_workspace_floats": [_i] * 6}
+               "smvs_conv3d_packed_floats": [_i] * 2, "smvs_conv3d_wgrad_workspace_floats": [_i] * 6,
+               "smvs_dsm_workspace_bytes": [_sz, _i, _i]}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",
                                                                     "smvs_set_arith", "smvs_get_arith"])
 ARITH_MODES = {"exact": 0, "fused": 1}      # SMVS_ARITH_EXACT / SMVS_ARITH_FUSED of include/satmvs.h

@@ -106,3 +106,14 @@ def save_rpc(filepath, rpc170):
     with open(filepath, "w") as f:
         for n, v in zip(_RPC_NAMES, rpc170):
             f.write("%s %.17g\n" % (n, v))
+
+
+def read_tfw(path):
+    """A world file (.tfw): six numbers, one per line -- x resolution, two rotation terms, -y resolution, and the easting and
+    northing of the CENTRE of the upper-left pixel.  -> float64 array of 6 (dataset/data_io.py:264-280 of the reference)."""
+    with open(path) as f:
+        lines = [ln for ln in f.read().splitlines() if ln.strip()]
+    tfw = np.array(lines, dtype=np.float64)
+    if tfw.shape[0] != 6:
+        raise ValueError("6 parameters expected in the tfw file, but got {}.".format(tfw.shape[0]))
+    return tfw

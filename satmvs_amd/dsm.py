@@ -1,0 +1,250 @@
+"""DSM production: per-view height maps (image space, RPC cameras) fused into one height grid in map coordinates.
+
+    grid = grid_for(heights, rpcs, proj, res=5.0)              # extent of every valid point, cell centres on multiples of res
+    dsm = heights_to_dsm(heights, rpcs, proj, grid)            # (gh, gw) float32, nodata where no point fell
+    write_dsm("out.tif", dsm, grid)                            # float32 TIFF + world file (.tfw)
+
+The hot path is native (include/satmvs.h, smvs_rpc_dsm_bin / smvs_dsm_reduce): one lane per pixel projects (x, y, h) through
+the inverse RPC and the Transverse Mercator forward into a cell; the reduce sorts every cell's heights and takes the median /
+mean / min / max.  The result is bit-identical from run to run and under any order of the maps.
+`proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MODES = {"median": 0, "mean": 1, "min": 2, "max": 3}
+
+
+@dataclass(frozen=True)
+class DSMGrid:
+    """A north-up grid: (e0, n0) is the CENTRE of cell (0, 0), the upper-left one; columns run east by xres, rows south by yres."""
+    e0: float
+    n0: float
+    xres: float
+    yres: float
+    width: int
+    height: int
+
+    def grid4(self):
+        return np.array([self.e0, self.n0, self.xres, self.yres], dtype=np.float64)
+
+    def cell_of(self, east, north):
+        """(col, row) of map points, float64 numpy: the kernel's rule with the same IEEE operations."""
+        col = np.floor((np.asarray(east, np.float64) - self.e0) / self.xres + 0.5)
+        row = np.floor((self.n0 - np.asarray(north, np.float64)) / self.yres + 0.5)
+        return col, row
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        raise _lib.SatMVSNativeError("DSM production runs on an MI355X only (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_list(x, n=None):
+    if x is None:
+        return [None] * n
+    if isinstance(x, (list, tuple)):
+        return list(x)
+    if (isinstance(x, np.ndarray) or isinstance(x, torch.Tensor)) and x.ndim == 3:
+        return [x[i] for i in range(x.shape[0])]
+    return [x]
+
+
+def _maps(heights, rpcs, masks, dev):
+    hs = _as_list(heights)
+    rs = _as_list(rpcs) if not (isinstance(rpcs, (np.ndarray, torch.Tensor)) and rpcs.ndim == 1) else [rpcs]
+    ms = _as_list(masks, len(hs))
+    if len(rs) != len(hs) or len(ms) != len(hs):
+        raise ValueError("one RPC (and one mask, if any) per height map: %d maps, %d rpcs, %d masks" % (len(hs), len(rs), len(ms)))
+    out = []
+    for h, r, m in zip(hs, rs, ms):
+        h = torch.as_tensor(h).to(device=dev, dtype=torch.float32).contiguous()
+        if h.ndim != 2:
+            raise ValueError("height maps are (H, W), got %s" % (tuple(h.shape),))
+        r = torch.as_tensor(r).to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if r.numel() != 170:
+            raise ValueError("rpc vectors must hold 170 values")
+        if m is not None:
+            m = torch.as_tensor(m).to(device=dev)
+            if tuple(m.shape) != tuple(h.shape):
+                raise ValueError("mask shape %s differs from the height map's %s" % (tuple(m.shape), tuple(h.shape)))
+            m = (m != 0).to(torch.uint8).contiguous()
+        out.append((h, r, m))
+    return out
+
+
+def _vp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _bin(h, r, m, tm7, grid4, gw, gh, cell, count, east=None, north=None):
+    dev = h.device
+    H, W = h.shape
+    with torch.cuda.device(dev):
+        _lib.call("smvs_rpc_dsm_bin", _lib.ptr(h), _lib.ptr(m) if m is not None else None, _lib.ptr(r), H, W,
+                  _vp(tm7), _vp(grid4), gw, gh, _lib.ptr(cell), _lib.ptr(count),
+                  _lib.ptr(east) if east is not None else None, _lib.ptr(north) if north is not None else None,
+                  _lib.current_stream(dev))
+
+
+def project_to_map(heights, rpcs, projection, masks=None):
+    """(east, north) float64 device tensors per map; NaN where a pixel is invalid (masked out or a non-finite height)."""
+    dev = _dev()
+    tm7 = projection.tm7()
+    dummy = DSMGrid(0.0, 0.0, 1.0, 1.0, 1, 1).grid4()
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = []
+    for h, r, m in _maps(heights, rpcs, masks, dev):
+        cell = torch.empty(h.shape, dtype=torch.int32, device=dev)
+        east = torch.empty(h.shape, dtype=torch.float64, device=dev)
+        north = torch.empty_like(east)
+        _bin(h, r, m, tm7, dummy, 1, 1, cell, count, east, north)
+        out.append((east, north))
+    return out
+
+
+def grid_from_extent(emin, emax, nmin, nmax, res):
+    """The grid of resolution `res` whose cells cover [emin, emax] x [nmin, nmax] with cell centres on integer multiples of res
+    (so that tiles and runs line up), every extreme point inside by the kernel's cell rule."""
+    res = float(res)
+    if not res > 0.0 or not all(math.isfinite(v) for v in (emin, emax, nmin, nmax, res)):
+        raise ValueError("grid_from_extent needs a finite extent and a positive resolution")
+    if emax < emin or nmax < nmin:
+        raise ValueError("empty extent")
+    e0 = math.floor(emin / res + 0.5) * res
+    n0 = math.ceil(nmax / res - 0.5) * res
+    g = DSMGrid(e0, n0, res, res, 1, 1)
+    c, r = g.cell_of(emin, nmax)
+    e0 -= res * max(0.0, -float(c))                          # rounding at a half cell: step one cell outward
+    n0 += res * max(0.0, -float(r))
+    g = DSMGrid(e0, n0, res, res, 1, 1)
+    c, r = g.cell_of(emax, nmin)
+    width, height = int(c) + 1, int(r) + 1
+    if width * height >= 2 ** 31:
+        raise ValueError("grid of %d x %d cells is too large (limit 2^31 cells)" % (width, height))
+    return DSMGrid(e0, n0, res, res, width, height)
+
+
+def grid_for(heights, rpcs, projection, res, masks=None):
+    """DSMGrid of resolution `res` [m] over the extent of every valid point of the maps."""
+    en = project_to_map(heights, rpcs, projection, masks)
+    lo, hi = [math.inf, math.inf], [-math.inf, -math.inf]
+    for east, north in en:
+        ok = torch.isfinite(east) & torch.isfinite(north)
+        if bool(ok.any()):
+            e, n = east[ok], north[ok]
+            lo = [min(lo[0], float(e.min())), min(lo[1], float(n.min()))]
+            hi = [max(hi[0], float(e.max())), max(hi[1], float(n.max()))]
+    if not math.isfinite(lo[0]):
+        raise ValueError("no valid point in the height maps")
+    return grid_from_extent(lo[0], hi[0], lo[1], hi[1], res)
+
+
+def reduce_cells(cell, height, count, grid, mode="median", nodata=-999.0):
+    """The reduce pass alone: cell int32 (n) and height float32 (n) device tensors, count (gw*gh) int32 from the bin pass ->
+    (gh, gw) float32 device tensor."""
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(MODES), mode))
+    dev = cell.device
+    n = cell.numel()
+    gw, gh = grid.width, grid.height
+    nbytes = _lib.load().smvs_dsm_workspace_bytes(n, gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported DSM size: %d points, %d x %d cells (limits: 2^31 points, 2^31 cells)" % (n, gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((gh, gw), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("smvs_dsm_reduce", _lib.ptr(cell), _lib.ptr(height), n, _lib.ptr(count), gw, gh, MODES[mode],
+                  float(nodata), _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.current_stream(dev))
+    return out
+
+
+def heights_to_dsm(heights, rpcs, projection, grid, masks=None, mode="median", nodata=-999.0, return_count=False):
+    """Fuse height maps (a list of (H, W) maps of any sizes, numpy or device tensors; one 170-vector RPC each; optional masks,
+    e.g. filter_depth's final mask) into the DSM of `grid`: every valid pixel goes to the cell its (E, N) falls in, every cell
+    takes the `mode` ("median", "mean", "min", "max") of its heights, empty cells get `nodata`.
+    -> (gh, gw) float32 (and int32 counts with return_count), numpy if the heights came as numpy, device tensors otherwise."""
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(MODES), mode))
+    as_numpy = not all(isinstance(h, torch.Tensor) for h in _as_list(heights))
+    dev = _dev()
+    maps = _maps(heights, rpcs, masks, dev)
+    n = sum(h.numel() for h, _, _ in maps)
+    if n >= 2 ** 31:
+        raise ValueError("too many points for one DSM: %d (limit 2^31)" % n)
+    gw, gh = int(grid.width), int(grid.height)
+    tm7, grid4 = projection.tm7(), grid.grid4()
+    cell = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.zeros(gw * gh, dtype=torch.int32, device=dev)
+    flat = torch.cat([h.reshape(-1) for h, _, _ in maps]) if len(maps) > 1 else maps[0][0].reshape(-1)
+    at = 0
+    for h, r, m in maps:                                     # every bin call writes its slice of one cell array
+        _bin(h, r, m, tm7, grid4, gw, gh, cell[at:at + h.numel()], count)
+        at += h.numel()
+    out = reduce_cells(cell, flat, count, grid, mode, nodata)
+    cnt = count.reshape(gh, gw)
+    if as_numpy:
+        out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
+    return (out, cnt) if return_count else out
+
+
+def write_dsm(path, dsm, grid):
+    """A float32 TIFF (Pillow) and, beside it, the world file (.tfw) in the six-line form of the reference's
+    gdal_create_dsm_file (dataset/data_io.py:289-296): xres, 0, 0, -yres, E and N of the centre of the upper-left cell."""
+    from PIL import Image
+    a = dsm.detach().cpu().numpy() if isinstance(dsm, torch.Tensor) else np.asarray(dsm)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != (grid.height, grid.width):
+        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (a.shape, grid.height, grid.width))
+    Image.fromarray(a, mode="F").save(path, format="TIFF")
+    text = str(grid.xres) + "\n0\n0\n" + str(-grid.yres) + "\n" + str(grid.e0) + "\n" + str(grid.n0)
+    with open(os.path.splitext(path)[0] + ".tfw", "w") as f:
+        f.write(text)
+    return path
+
+
+def read_dsm(path):
+    """(dsm float32, DSMGrid) of a TIFF written by write_dsm (or any float32 TIFF with a north-up .tfw beside it)."""
+    from PIL import Image
+    from .data_io import read_tfw
+    a = np.array(Image.open(path), dtype=np.float32)
+    t = read_tfw(os.path.splitext(path)[0] + ".tfw")
+    if t[1] != 0.0 or t[2] != 0.0:
+        raise ValueError("rotated world files are not supported")
+    return a, DSMGrid(float(t[4]), float(t[5]), float(t[0]), float(-t[3]), a.shape[1], a.shape[0])
+
+
+def dsm_metrics(est, gt, nodata, thresholds=(2.5, 7.5)):
+    """Accuracy of a DSM against a ground-truth DSM on the same grid (float64).  Cells equal to `nodata` or non-finite are
+    invalid.  -> dict: mae, rmse (over cells valid in both), "<t" = share of those cells with |est - gt| < t per threshold,
+    completeness = share of valid ground-truth cells that have an estimate, n = number of cells compared."""
+    e = torch.as_tensor(est).to(torch.float64)
+    g = torch.as_tensor(gt).to(device=e.device, dtype=torch.float64)
+    if e.shape != g.shape:
+        raise ValueError("shapes differ: %s vs %s" % (tuple(e.shape), tuple(g.shape)))
+    vg = torch.isfinite(g) & (g != nodata)
+    ve = torch.isfinite(e) & (e != nodata)
+    both = vg & ve
+    nb, ng = int(both.sum()), int(vg.sum())
+    out = {"n": nb, "completeness": nb / ng if ng else float("nan")}
+    if nb:
+        d = (e[both] - g[both]).abs()
+        out["mae"] = float(d.mean())
+        out["rmse"] = float(torch.sqrt((d * d).mean()))
+        for t in thresholds:
+            out["<%g" % t] = float((d < t).double().mean())
+    else:
+        out["mae"] = out["rmse"] = float("nan")
+        for t in thresholds:
+            out["<%g" % t] = float("nan")
+    return out
