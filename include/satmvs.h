@@ -20,8 +20,8 @@
  *     carry its own) and a mutex-guarded,
  *     per-device pool of helper streams/events that smvs_red_pred_planes / smvs_red_volume_planes
  *     borrow for the duration of a call (bounded by the peak number of concurrent calls on a device).
- *   - The shipped library never reads the environment: tuning / A/B switches exist only in builds
- *     made with -DSMVS_TUNING (tools/ab_build.sh).
+ *   - The library never reads the environment and has no tuning builds: every kernel variant and
+ *     threshold is fixed at compile time.
  *   - Deliberate differences from SURVEY.md section 8b's sketch: the Python binding is ctypes over
  *     this header (satmvs_amd/_lib.py), not a torch.utils.cpp_extension shim -- no torch types or
  *     headers are needed to build or call the library; and there is no smvs_shard_allreduce(ncclComm_t):

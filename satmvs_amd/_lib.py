@@ -13,7 +13,7 @@ import threading
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SMVS_LIB_PATH: load another build of the same library (A/B timing of kernel variants in one process-level run)
+# SMVS_LIB_PATH: load another build of the same library, e.g. another commit's, to time two builds against each other on one box
 LIB_PATH = os.environ.get("SMVS_LIB_PATH") or os.path.join(_HERE, "lib", "libsatmvs_hip.so")
 
 _vp, _i, _sz, _f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
@@ -116,21 +116,19 @@ def load():
         fn.restype = C.c_size_t
     lib.smvs_version.restype = C.c_char_p
     lib.smvs_last_error.restype = C.c_char_p
-    if hasattr(lib, "smvs_red_set_streams"):               # (older A/B builds loaded through SMVS_LIB_PATH predate these two)
-        lib.smvs_red_set_streams.argtypes = [_i]
-        lib.smvs_red_set_streams.restype = C.c_int
-        lib.smvs_shutdown.argtypes = []
-        lib.smvs_shutdown.restype = C.c_int
-    if hasattr(lib, "smvs_set_arith"):
-        lib.smvs_set_arith.argtypes = [_i]
-        lib.smvs_set_arith.restype = C.c_int
-        lib.smvs_get_arith.argtypes = []
-        lib.smvs_get_arith.restype = C.c_int
-        mode = os.environ.get("SMVS_ARITH")                 # the library itself never reads the environment
-        if mode:
-            if mode not in ARITH_MODES:
-                raise ValueError("SMVS_ARITH must be one of %s, got %r" % (sorted(ARITH_MODES), mode))
-            lib.smvs_set_arith(ARITH_MODES[mode])
+    lib.smvs_red_set_streams.argtypes = [_i]
+    lib.smvs_red_set_streams.restype = C.c_int
+    lib.smvs_shutdown.argtypes = []
+    lib.smvs_shutdown.restype = C.c_int
+    lib.smvs_set_arith.argtypes = [_i]
+    lib.smvs_set_arith.restype = C.c_int
+    lib.smvs_get_arith.argtypes = []
+    lib.smvs_get_arith.restype = C.c_int
+    mode = os.environ.get("SMVS_ARITH")                     # the library itself never reads the environment
+    if mode:
+        if mode not in ARITH_MODES:
+            raise ValueError("SMVS_ARITH must be one of %s, got %r" % (sorted(ARITH_MODES), mode))
+        lib.smvs_set_arith(ARITH_MODES[mode])
     _lib = lib
     return lib
 

@@ -65,28 +65,11 @@ __device__ __forceinline__ float reduce4_rows(float a, float b, float c, float d
     return a;
 }
 
-#ifndef SMVS_WGRAD2_XCD
-#define SMVS_WGRAD2_XCD 0               // sharers adjacent + one contiguous run of workgroups per XCD (the 3-D kernel's order).  Measured in round 5 on the casred graphed step, alternating: 58.6 / 58.1 against 59.0 / 58.2 ms -- inside the spread; off
-#endif
-
 template <int S>
 __global__ __launch_bounds__(256)
 void conv3x3_wgrad_kernel(const WgradParams p)
 {
     const int lane = threadIdx.x & 63;
-#if SMVS_WGRAD2_XCD
-    // (round 5, from the 3-D kernel below) the waves that read the same rows -- every channel pair wants a gradient row, every output
-    // group a window row -- run fastest in the unit order and every XCD gets one contiguous run of workgroups: sharers meet in one L2
-    int unit = (int)xcd_remap(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);   // one wave = one unit
-    unit = __builtin_amdgcn_readfirstlane(unit);
-    const int total = p.ncp * p.ncog * p.nxs * p.nrc * p.nbc;
-    if (unit >= total) return;
-    const int cp = unit % p.ncp; unit /= p.ncp;
-    const int cog = unit % p.ncog; unit /= p.ncog;
-    const int rc = unit % p.nrc; unit /= p.nrc;
-    const int xs = unit % p.nxs;
-    const int bc = unit / p.nxs;
-#else
     int unit = blockIdx.x * 4 + (threadIdx.x >> 6);                  // one wave = one unit
     unit = __builtin_amdgcn_readfirstlane(unit);
     const int total = p.ncp * p.ncog * p.nxs * p.nrc * p.nbc;
@@ -97,7 +80,6 @@ void conv3x3_wgrad_kernel(const WgradParams p)
     const int cp = unit % p.ncp; unit /= p.ncp;
     const int cog = unit % p.ncog;
     const int bc = unit / p.ncog;
-#endif
     const int b0 = bc * p.bchunk, b1 = min(p.B, b0 + p.bchunk);
     const int H = p.H, W = p.W, HW = H * W;
     const int HX = S * H, WX = S * W, HWX = HX * WX;                  // the window tensor's plane
@@ -251,48 +233,6 @@ void conv3x3_wgrad_kernel(const WgradParams p)
 // (a range of rows) x (a range of grid planes) x ONE depth tap kd -- 144 sums in registers; for every grid plane d of its range it
 // slides the 3x3 window down the rows of window plane S d + kd - 1 (planes outside the volume are skipped wave-uniformly).  Channel
 // strides are those of the (B,C,D,H,W) volumes, so nothing is copied or transposed.
-// Explicitly counted row pipeline (round 5, SMVS_WGRAD3_COUNTED; measured: no gain, off).  With plain loads the compiler closes every
-// iteration of the row loop with s_waitcnt vmcnt(0) -- the prefetched row is a loop-carried value -- so a row of memory latency is covered
-// by ONE row of arithmetic (72 v_pk_fma_f32).  Loads issued through inline assembly are invisible to
-// the compiler's wait insertion; the kernel waits itself, counted: two register sets, each requested two iterations before its use.
-__device__ __forceinline__ void wg_load(float& dst, const i32x4& r, uint32_t voff, int soff)
-{
-    asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=&v"(dst) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wg_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-// the counted wait that releases a register set: the registers are operands of the wait itself, so that no read of them can be scheduled
-// above it (an empty pinning statement next to an operand-less wait is not enough: the copies were hoisted over the wait)
-template <int N>
-__device__ __forceinline__ void wg_wait_set(float (&w)[2][3], float (&g)[8])
-{
-    asm volatile("s_waitcnt vmcnt(%14)"
-                 : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[0][2]), "+v"(w[1][0]), "+v"(w[1][1]), "+v"(w[1][2]),
-                   "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(g[4]), "+v"(g[5]), "+v"(g[6]), "+v"(g[7])
-                 : "n"(N) : "memory");
-}
-// The counted wait AND the hand-over of a set's 14 registers in ONE statement: the set is read nowhere else, so its registers live from the
-// load statements to this one and nothing can be scheduled (or copied) in between that reads them before the wait.
-template <int N>
-__device__ __forceinline__ void wg_wait_take(const float (&w)[2][3], const float (&g)[8], float (&fw)[1][2][3], float (&fg)[8])
-{
-    asm volatile("s_waitcnt vmcnt(%28)\n\t"
-                 "v_mov_b32 %0, %14\n\tv_mov_b32 %1, %15\n\tv_mov_b32 %2, %16\n\tv_mov_b32 %3, %17\n\tv_mov_b32 %4, %18\n\tv_mov_b32 %5, %19\n\t"
-                 "v_mov_b32 %6, %20\n\tv_mov_b32 %7, %21\n\tv_mov_b32 %8, %22\n\tv_mov_b32 %9, %23\n\tv_mov_b32 %10, %24\n\tv_mov_b32 %11, %25\n\t"
-                 "v_mov_b32 %12, %26\n\tv_mov_b32 %13, %27"
-                 : "=&v"(fw[0][0][0]), "=&v"(fw[0][0][1]), "=&v"(fw[0][0][2]), "=&v"(fw[0][1][0]), "=&v"(fw[0][1][1]), "=&v"(fw[0][1][2]),
-                   "=&v"(fg[0]), "=&v"(fg[1]), "=&v"(fg[2]), "=&v"(fg[3]), "=&v"(fg[4]), "=&v"(fg[5]), "=&v"(fg[6]), "=&v"(fg[7])
-                 : "v"(w[0][0]), "v"(w[0][1]), "v"(w[0][2]), "v"(w[1][0]), "v"(w[1][1]), "v"(w[1][2]),
-                   "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]), "n"(N)
-                 : "memory");
-}
-__device__ __forceinline__ void wg_wait_rows(float (&a)[2][3], float (&b)[2][3])
-{
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]),
-                   "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[0][2]), "+v"(b[1][0]), "+v"(b[1][1]), "+v"(b[1][2])
-                 :: "memory");
-}
 
 struct Wgrad3Params {
     const float* x; const float* dy; float* dw;
@@ -301,19 +241,6 @@ struct Wgrad3Params {
     int ndc, dchunk;                    // chunks of grid planes, planes per chunk
     float* part;                        // null: sums go to dw with float atomics; else (groups, waves per group, 144) partial sums for conv3d_wgrad_fold
 };
-
-#ifndef SMVS_WGRAD3_ROTATE
-#define SMVS_WGRAD3_ROTATE 1            // stride 1: four rotating row slots, loop unrolled by four (0: the sliding window, A/B)
-#endif
-#ifndef SMVS_WGRAD3_GC1
-#define SMVS_WGRAD3_GC1 1               // single-channel grid tensors (the `prob` layer) on the one-grid-channel instance (0: the 8-channel group, A/B)
-#endif
-#ifndef SMVS_WGRAD3_XCD
-#define SMVS_WGRAD3_XCD 1               // sharers of a row adjacent in the unit order + one contiguous run of workgroups per XCD (0: the first order, A/B)
-#endif
-#ifndef SMVS_WGRAD3_COUNTED
-#define SMVS_WGRAD3_COUNTED 0           // 1: stride 1 on the explicitly counted two-set row pipeline below.  Built and measured in round 5 (tests green): 10.4 against 9.9 ms per 5 casmvs steps -- row latency is not what bounds the kernel (two-ahead through the compiler: 9.9 as well); off
-#endif
 
 // GC: grid channels a wave carries -- 8, or 1 for the single-channel `prob` layer (round 5: with 8 it ran seven padding channels, a quarter
 // of the step's weight-gradient row iterations for one eighth of the useful work)
@@ -328,11 +255,10 @@ void conv3d_wgrad_kernel(const Wgrad3Params p)
     // each L2 fetched its own copy (2.2 GB of L2 misses per launch for 0.23 GB of tensors: the kernel ran at the fabric's rate).  Now depth
     // tap, channel pair and grid group run fastest and every XCD gets one contiguous run of the workgroup order (xcd_remap): the sharers
     // are neighbours on one XCD, in flight together.
-    const uint32_t wg = SMVS_WGRAD3_XCD ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const uint32_t wg = xcd_remap(blockIdx.x, gridDim.x);
     long long unit = (long long)wg * 4 + (threadIdx.x >> 6);           // one wave = one unit
     const long long total = (long long)p.ncp * p.ncog * p.nxs * p.nrc * 3 * p.ndc * p.B;
     if (unit >= total) return;
-#if SMVS_WGRAD3_XCD
     const int kd = __builtin_amdgcn_readfirstlane((int)(unit % 3)); unit /= 3;
     const int cp = __builtin_amdgcn_readfirstlane((int)(unit % p.ncp)); unit /= p.ncp;
     const int cog = __builtin_amdgcn_readfirstlane((int)(unit % p.ncog)); unit /= p.ncog;
@@ -340,16 +266,6 @@ void conv3d_wgrad_kernel(const Wgrad3Params p)
     const int xs = __builtin_amdgcn_readfirstlane((int)(unit % p.nxs)); unit /= p.nxs;
     const int dc = __builtin_amdgcn_readfirstlane((int)(unit % p.ndc));
     const int b = __builtin_amdgcn_readfirstlane((int)(unit / p.ndc));
-#else
-    // (first form) row chunk fastest, then column strip, depth tap, plane chunk, channel pair, output group, batch
-    const int rc = __builtin_amdgcn_readfirstlane((int)(unit % p.nrc)); unit /= p.nrc;
-    const int xs = __builtin_amdgcn_readfirstlane((int)(unit % p.nxs)); unit /= p.nxs;
-    const int kd = __builtin_amdgcn_readfirstlane((int)(unit % 3)); unit /= 3;
-    const int dc = __builtin_amdgcn_readfirstlane((int)(unit % p.ndc)); unit /= p.ndc;
-    const int cp = __builtin_amdgcn_readfirstlane((int)(unit % p.ncp)); unit /= p.ncp;
-    const int cog = __builtin_amdgcn_readfirstlane((int)(unit % p.ncog));
-    const int b = __builtin_amdgcn_readfirstlane((int)(unit / p.ncog));
-#endif
     const int D = p.D, H = p.H, W = p.W, HW = H * W;
     const int DX = S * D, HX = S * H, WX = S * W, HWX = HX * WX;
     const size_t csx = (size_t)DX * HWX, csy = (size_t)D * HW;        // channel strides (elements)
@@ -419,76 +335,23 @@ void conv3d_wgrad_kernel(const Wgrad3Params p)
 #pragma unroll
                     for (int k = 0; k < 3; ++k) acc[c][j][r * 3 + k] = fmaf(g[j], win[c][r][k], acc[c][j][r * 3 + k]);
     };
-    if constexpr (!(S == 1 && GC == 8 && SMVS_WGRAD3_COUNTED)) {
-        if (S == 1) {
-            float r0[2][3], r1[2][3];
-            load_row(y0 - 1, r0);
-            load_row(y0, r1);
+    if (S == 1) {
+        float r0[2][3], r1[2][3];
+        load_row(y0 - 1, r0);
+        load_row(y0, r1);
 #pragma unroll
-            for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { win[c][1][k] = r0[c][k]; win[c][2][k] = r1[c][k]; win[c][0][k] = 0.0f; }
-        } else {
-            float r0[2][3];
-            load_row(S * y0 - 1, r0);
+            for (int k = 0; k < 3; ++k) { win[c][1][k] = r0[c][k]; win[c][2][k] = r1[c][k]; win[c][0][k] = 0.0f; }
+    } else {
+        float r0[2][3];
+        load_row(S * y0 - 1, r0);
 #pragma unroll
-            for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { win[c][2][k] = r0[c][k]; win[c][0][k] = win[c][1][k] = 0.0f; }
-        }
+            for (int k = 0; k < 3; ++k) { win[c][2][k] = r0[c][k]; win[c][0][k] = win[c][1][k] = 0.0f; }
     }
-    if constexpr (S == 1 && GC == 8 && SMVS_WGRAD3_COUNTED) {
-        // (every load of this path goes through wg_load: one compiler-visible load whose value is first used inside the row loop would
-        //  put the compiler's own vmcnt(0) INTO the loop)
-        {
-            float r0[2][3], r1[2][3];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int yy = y0 - 1 + q;
-                i32x4 r = rx.v;
-                r.z = (yy >= 0 && yy < HX) ? r.z : 0;
-                const int so = (yy >= 0 && yy < HX) ? yy * WX * 4 : 0;
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) wg_load(q ? r1[c][k] : r0[c][k], r, cx[k], c * ch1 + so);
-            }
-            wg_wait_rows(r0, r1);
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { win[c][1][k] = r0[c][k]; win[c][2][k] = r1[c][k]; win[c][0][k] = 0.0f; }
-        }
-        // Two sets of 6 + 8 registers; set (y - y0) & 1 holds iteration y's rows.  A step hands its set over to the arithmetic's registers
-        // inside the counted wait (wg_wait_take) and requests the set again, for iteration y + 2, BEFORE its arithmetic: a request has two
-        // rows of arithmetic to land in.  In flight at a wait: the other set's 14 loads.
-        float sw[2][2][3], sg[2][8];
-        auto issue = [&](int yi, float (&w)[2][3], float (&g)[8]) __attribute__((always_inline)) {
-            i32x4 rw = rx.v, rg = ry.v;
-            const bool vw = yi < y1 && yi + 1 < HX, vg = yi < y1;     // (yi + 1 >= 0 always: yi >= y0 >= 0)
-            rw.z = vw ? rw.z : 0; rg.z = vg ? rg.z : 0;               // rows outside the plane / past the chunk: zero records = zeros
-            const int sow = vw ? (yi + 1) * WX * 4 : 0, sog = vg ? yi * W * 4 : 0;
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) wg_load(w[c][k], rw, cx[k], c * ch1 + sow);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) wg_load(g[j], rg, cy, gch[j] + sog);
-        };
-        auto step = [&](int y, float (&w)[2][3], float (&g)[8]) __attribute__((always_inline)) {
-            float fw[1][2][3], fg[8];
-            wg_wait_take<14>(w, g, fw, fg);
-            issue(y + 2, w, g);
-            if (y < y1) fma_row(fw, fg);                              // (wave-uniform: an odd chunk's last half-step multiplies nothing)
-        };
-        issue(y0, sw[0], sg[0]);
-        issue(y0 + 1, sw[1], sg[1]);
-        for (int y = y0; y < y1; y += 2) {
-            step(y, sw[0], sg[0]);
-            step(y + 1, sw[1], sg[1]);
-        }
-        wg_wait<0>();                                                 // nothing of ours in flight when the next plane starts
-    } else if constexpr (S == 1 && SMVS_WGRAD3_ROTATE) {
+    if constexpr (S == 1) {
         // Rotating window (round 5): FOUR row slots per window channel -- a step reads slots t, t+1, t+2 (mod 4) as window rows 0..2 and
         // the row of the NEXT step lands in slot t+3 while it runs -- and two sets of grid values; the loop is unrolled by four so every
         // slot index is a constant: no window slide, no hand-over copies (the first form spent ~50 of its ~125 vector instructions per row
@@ -695,7 +558,7 @@ static void wgrad3_split(smvs::Wgrad3Params& p, bool two_stage)
     const long long base = (long long)p.ncp * p.ncog * p.nxs * 3 * p.B;
     int dchunk = D, rows = H;
     if (two_stage) {
-        const long long slots = tune_int("SMVS_WGRAD3_SLOTS", 2048);
+        constexpr long long slots = 2048;                     // the waves the chip holds at a time (above)
         long long best = -1;
         for (int dcs = 1; dcs <= D; ++dcs) {
             const int nd = (D + dcs - 1) / dcs;
@@ -750,7 +613,7 @@ extern "C" SMVS_EXPORT int smvs_conv3d_wgrad(const float* window, const float* g
     const long long units = base * ndc * p.nrc;
     if ((units + 3) / 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
     const dim3 grd((unsigned)((units + 3) / 4));
-    if (Cgrid == 1 && SMVS_WGRAD3_GC1) {
+    if (Cgrid == 1) {
         if (stride == 1) hipLaunchKernelGGL((conv3d_wgrad_kernel<1, 1>), grd, dim3(256), 0, (hipStream_t)stream, p);
         else             hipLaunchKernelGGL((conv3d_wgrad_kernel<2, 1>), grd, dim3(256), 0, (hipStream_t)stream, p);
     } else {

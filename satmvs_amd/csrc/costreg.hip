@@ -441,7 +441,7 @@ void convT3d_split_kernel(const Conv3Args a)
 
 // One layer on the kernels above: wm = MFMA-order weights (null: direct kernels)
 static void cr_launch_layer(const CrLayer& l, const float* in, const float* w, const float* scale, const float* shift, const float* wm,
-                            const float* skip, float* out, int B, const int (&di)[3], const int (&dout)[3], bool direct_only, hipStream_t st)
+                            const float* skip, float* out, int B, const int (&di)[3], const int (&dout)[3], hipStream_t st)
 {
     Conv3Args a{};
     a.in = in; a.w = w; a.scale = scale; a.shift = shift;
@@ -458,19 +458,17 @@ static void cr_launch_layer(const CrLayer& l, const float* in, const float* w, c
         mfma_conv_launch<27>(m, B, st);
     } else if (l.transposed) {
         dim3 grd((a.Wi + 63) / 64, (a.Hi * a.Di + 3) / 4, B * ncog);
-        static const int split_below = tune_int("SMVS_CONV_SPLIT_BELOW", 1024);
-        if ((long long)((a.Di * a.Hi * a.Wi + 63) / 64) * B * ncog < split_below / 2 && !direct_only)
+        constexpr int SPLIT_BELOW = 512;         // workgroups (of the 64-position split form) below which the channel-split kernel runs
+        if ((long long)((a.Di * a.Hi * a.Wi + 63) / 64) * B * ncog < SPLIT_BELOW)
             hipLaunchKernelGGL(convT3d_split_kernel, dim3((a.Di * a.Hi * a.Wi + 63) / 64, 1, B * ncog), dim3(256), 0, st, a);
         else
             hipLaunchKernelGGL(convT3d_kernel, grd, dim3(256), 0, st, a);
     } else {
         dim3 grd((a.Wo + 63) / 64, (a.Ho * a.Do + 3) / 4, B * ncog);
         const dim3 grd1((a.Wo + CR_S1_TILE - 1) / CR_S1_TILE, (a.Ho * a.Do + 3) / 4, B * ncog);
-        static const bool gather = tune_int("SMVS_CONV3D_GATHER", 0) == 1;
-        if (l.stride == 1 && !gather && l.cout <= 2) hipLaunchKernelGGL(conv3d_s1_kernel<2>, grd1, dim3(256), 0, st, a);
-        else if (l.stride == 1 && !gather) hipLaunchKernelGGL(conv3d_s1_kernel<CR_COT>, grd1, dim3(256), 0, st, a);
-        else if (l.stride == 1)       hipLaunchKernelGGL(conv3d_kernel<1>, grd, dim3(256), 0, st, a);
-        else               hipLaunchKernelGGL(conv3d_kernel<2>, grd, dim3(256), 0, st, a);
+        if (l.stride == 1 && l.cout <= 2) hipLaunchKernelGGL(conv3d_s1_kernel<2>, grd1, dim3(256), 0, st, a);
+        else if (l.stride == 1)           hipLaunchKernelGGL(conv3d_s1_kernel<CR_COT>, grd1, dim3(256), 0, st, a);
+        else                              hipLaunchKernelGGL(conv3d_kernel<2>, grd, dim3(256), 0, st, a);
     }
 }
 
@@ -549,7 +547,6 @@ SMVS_EXPORT int smvs_costreg_fwd(const float* packed, const float* vol, float* o
     cr_layers(C, L);
     const CrLayout lay = cr_layout(C);
     const CrWorkspace ws = cr_workspace(B, D, H, W);
-    const bool direct_only = tune_int("SMVS_CONV_DIRECT", 0) == 1;      // A/B switch (tuning builds): direct kernels only
     float* f = (float*)workspace;
     hipStream_t st = (hipStream_t)stream;
     const int dims[4][3] = {{D, H, W}, {D / 2, H / 2, W / 2}, {D / 4, H / 4, W / 4}, {D / 8, H / 8, W / 8}};
@@ -567,8 +564,7 @@ SMVS_EXPORT int smvs_costreg_fwd(const float* packed, const float* vol, float* o
         if ((long long)l.cin * dims[s.lin][0] * dims[s.lin][1] * dims[s.lin][2] * 4 >= (1ll << 32))
             return fail(SMVS_ERR_ARG, "layer %d input larger than 4 GiB per batch item", i);
         cr_launch_layer(l, s.in, packed + lay.w[s.layer], packed + lay.scale[s.layer], packed + lay.shift[s.layer],
-                        cr_use_mfma(l) && !direct_only ? packed + lay.wm[s.layer] : nullptr, s.skip, s.out, B, dims[s.lin], dims[s.lout],
-                        direct_only, st);
+                        cr_use_mfma(l) ? packed + lay.wm[s.layer] : nullptr, s.skip, s.out, B, dims[s.lin], dims[s.lout], st);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "costreg_fwd launch: %s", hipGetErrorString(e));
@@ -623,7 +619,7 @@ SMVS_EXPORT int smvs_conv3d_fwd(int kind, const float* in, const float* packed, 
     const size_t n = cr_packed_conv(Cin, Cout);
     const int cp = ncog * CR_COT;
     const bool mf = kind != 2 && mfma_conv_ok(Cin, 0, Cout);
-    cr_launch_layer(l, in, packed, packed + n, packed + n + cp, mf ? packed + n + 2 * cp : nullptr, skip, out, B, di, dout, false, (hipStream_t)stream);
+    cr_launch_layer(l, in, packed, packed + n, packed + n + cp, mf ? packed + n + 2 * cp : nullptr, skip, out, B, di, dout, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3d_fwd launch: %s", hipGetErrorString(e));
     return SMVS_OK;

@@ -127,15 +127,6 @@ static int costvol_fwd(int geo_kind, const float* ref_fea, const float* const* s
 
 extern "C" {
 
-#ifdef SMVS_TIMING
-SMVS_EXPORT int smvs_debug_timing(unsigned long long* out12, int reset)
-{
-    hipDeviceSynchronize();
-    if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(smvs::smvs_timing), 96) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[12] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(smvs::smvs_timing), z, 96) != hipSuccess) return 1; }
-    return 0;
-}
-#endif
 
 SMVS_EXPORT int smvs_set_arith(int mode)
 {

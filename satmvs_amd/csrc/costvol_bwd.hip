@@ -54,40 +54,10 @@ struct CostVolBwdParams {
     int xt, yt, dct, dch;
 };
 
-#ifndef SMVS_BWD_OCC
-#define SMVS_BWD_OCC 2                 // waves per SIMD the kernel is compiled for
-#endif
-#ifndef SMVS_BWD_ABLATE
-#define SMVS_BWD_ABLATE 0              // timing experiments only (wrong results): 1 no flush atomics, 2 no box adds, 4 no reference atomic, 16 geometry only, 32 box adds as ds_add_u32
-#endif
-#ifndef SMVS_BWD_DCH8_SRC
-#define SMVS_BWD_DCH8_SRC 4           // up to this many source views a lane keeps 8 planes of taps (2 beyond: the register scheme only); measured 3 / 4 views: 4.01 -> 3.66, 6.78 -> 5.88 ms against 4-plane chunks
-#endif
-#ifndef SMVS_BWD_BOX_AHEAD
-#define SMVS_BWD_BOX_AHEAD 0           // 1: feature boxes two channels ahead on three LDS buffers (1-2 source views).  Measured in round 5: 3.91-3.96 against 3.89-3.92 ms (profiles/r05_bwd_prefetch2.txt) -- the boxes' latency is not what the waves wait for; off
-#endif
-#ifndef SMVS_BWD_FLUSH_TOGETHER
-#define SMVS_BWD_FLUSH_TOGETHER 0      // 1: (1-2 source views) the flush exchanges of every view in flight together, one wait.  Measured in round 5: 3.92 against 3.93 ms -- the two LDS round trips per channel are not what the waves wait for; off
-#endif
-#ifndef SMVS_BWD_KEEP_WEIGHTS
-#define SMVS_BWD_KEEP_WEIGHTS 1        // boxed path, 1-2 source views: tap weights kept in registers over the channel loop (A/B switch)
-#endif
-#ifndef SMVS_BWD_MEAN_MUL
-#define SMVS_BWD_MEAN_MUL 1            // interior waves: mean over the views as sum * RN(1/V) instead of the exact division (A/B switch)
-#endif
-#ifndef SMVS_BWD_LDS
-#define SMVS_BWD_LDS 1                 // 0: never take the boxed path (A/B)
-#endif
-#ifdef SMVS_BWD_TIMING
-// profiling builds only (tools/ab_build.sh x -DSMVS_BWD_TIMING, AB_SRC=costvol_bwd.hip): per-wave phase stamps of the boxed path in shader
-// clocks, read back through smvs_debug_timing_bwd().  [0] geometry + set-up, [1] top-of-channel wait for the loads, [2] flush of the
-// previous channel's boxes, [3] issue of the next loads / boxes, [4] plane loop, [7] waves
-__device__ unsigned long long smvs_bwd_timing[8];
-__device__ __forceinline__ unsigned long long bnow() { unsigned long long t = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return t; }
-#define SMVS_BT(...) __VA_ARGS__
-#else
-#define SMVS_BT(...)
-#endif
+constexpr int BWD_OCC = 2;                         // waves per SIMD the kernel is compiled for
+// up to this many source views a lane keeps 8 planes of taps (2 beyond: the register scheme only); measured 3 / 4 views: 4.01 -> 3.66,
+// 6.78 -> 5.88 ms against 4-plane chunks
+constexpr int DCH8_SRC = 4;
 // one word per tap: 00 | y0 << 15 | x0 while the geometry runs, then the byte offset the tap's path wants
 constexpr uint32_t TAP_DROPPED = 0x80000000u;      // = SMVS_OOB: a load through it returns 0
 constexpr uint32_t TAP_PARTIAL = 0xC0000000u;      // | (y0+1) << 15 | (x0+1): some corner lies outside the image
@@ -127,47 +97,12 @@ __device__ __forceinline__ void fbox_wait_n(f32x2& north, f32x2& south)
 // the four corners of a full tap into the gradient box (LDS byte address of the north-west cell); no return value, in order per wave
 __device__ __forceinline__ void gbox_add4(uint32_t addr, float c0, float c1, float c2, float c3)
 {
-#if SMVS_BWD_ABLATE & 32            // timing experiment (wrong results): 32-bit integer adds into the same cells
-    const int i0 = (int)c0, i1 = (int)c1, i2 = (int)c2, i3 = (int)c3;
-    asm volatile("ds_add_u32 %0, %1\n\t"
-                 "ds_add_u32 %0, %2 offset:8\n\t"
-                 "ds_add_u32 %0, %3 offset:%5\n\t"
-                 "ds_add_u32 %0, %4 offset:%6"
-                 :: "v"(addr), "v"(i0), "v"(i1), "v"(i2), "v"(i3), "n"(BOX_W * 8), "n"(BOX_W * 8 + 8) : "memory");
-    return;
-#endif
     const double d0 = (double)c0, d1 = (double)c1, d2 = (double)c2, d3 = (double)c3;
     asm volatile("ds_add_f64 %0, %1\n\t"
                  "ds_add_f64 %0, %2 offset:8\n\t"
                  "ds_add_f64 %0, %3 offset:%5\n\t"
                  "ds_add_f64 %0, %4 offset:%6"
                  :: "v"(addr), "v"(d0), "v"(d1), "v"(d2), "v"(d3), "n"(BOX_W * 8), "n"(BOX_W * 8 + 8) : "memory");
-}
-// the same exchange without the wait and without the rounding: the caller issues every view's eight first and waits once (gbox_wait_all)
-__device__ __forceinline__ void gbox_take8_nowait(uint32_t addr, double (&d)[BOX_H])
-{
-    const double zero = 0.0;
-    asm volatile("ds_wrxchg_rtn_b64 %0, %8, %9\n\t"
-                 "ds_wrxchg_rtn_b64 %1, %8, %9 offset:%10\n\t"
-                 "ds_wrxchg_rtn_b64 %2, %8, %9 offset:%11\n\t"
-                 "ds_wrxchg_rtn_b64 %3, %8, %9 offset:%12\n\t"
-                 "ds_wrxchg_rtn_b64 %4, %8, %9 offset:%13\n\t"
-                 "ds_wrxchg_rtn_b64 %5, %8, %9 offset:%14\n\t"
-                 "ds_wrxchg_rtn_b64 %6, %8, %9 offset:%15\n\t"
-                 "ds_wrxchg_rtn_b64 %7, %8, %9 offset:%16"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7])
-                 : "v"(addr), "v"(zero), "n"(BOX_W * 8), "n"(BOX_W * 16), "n"(BOX_W * 24), "n"(BOX_W * 32),
-                   "n"(BOX_W * 40), "n"(BOX_W * 48), "n"(BOX_W * 56)
-                 : "memory");
-}
-template <int NV>
-__device__ __forceinline__ void gbox_wait_all(double (&d)[NV][BOX_H])
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int s = 0; s < NV; ++s)
-#pragma unroll
-        for (int i = 0; i < BOX_H; ++i) asm volatile("" : "+v"(d[s][i]));
 }
 // read and clear the lane's cell of box row I (no wait)
 template <int I>
@@ -215,15 +150,13 @@ __device__ __forceinline__ void gbox_take8(uint32_t addr, float (&v)[BOX_H])
 }
 
 template <int GEO, int NSRC, int DCH>
-__global__ __launch_bounds__(64 * BWD_WAVES, SMVS_BWD_OCC)
+__global__ __launch_bounds__(64 * BWD_WAVES, BWD_OCC)
 void costvol_bwd_kernel(const CostVolBwdParams p)
 {
     static_assert(DCH * NSRC <= 32, "tap flag masks");
-    constexpr bool BOX = SMVS_BWD_LDS && NSRC <= BOX_MAX_SRC;
-    // feature boxes: two buffers (the next channel's boxes land while this one's are read) -- three with 1-2 source views, where the
-    // boxes are requested TWO channels ahead like the gradient planes (round 5: the first of the eight plane chunks of a tile that asks
-    // for a channel's rows takes an HBM miss, ~2-4 us, more than a channel of arithmetic)
-    constexpr int NFB = (SMVS_BWD_BOX_AHEAD && NSRC <= 2) ? 3 : 2;
+    constexpr bool BOX = NSRC <= BOX_MAX_SRC;
+    // feature boxes: two buffers (the next channel's boxes land while this one's are read)
+    constexpr int NFB = 2;
     constexpr int WAVE_LDS = NSRC * (NFB * FBOX_BYTES + GBOX_BYTES);        // [NFB buffers][view] feature boxes, then [view] gradient boxes
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[BOX ? BWD_WAVES * WAVE_LDS : 16];
     uint32_t L = xcd_remap(blockIdx.x, gridDim.x);
@@ -231,7 +164,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
     const int dchunk = L % p.dct; L /= p.dct;
     const int ytile = L % p.yt;
     const int b = L / p.yt;
-    SMVS_BT(const unsigned long long bt_start = bnow(); unsigned long long bt_wait = 0, bt_flush = 0, bt_issue = 0, bt_planes = 0;)
     const int lane = threadIdx.x;                           // blockDim = (64, BWD_WAVES): threadIdx.y = wave
     const int wv_ = threadIdx.y;
     // The wave's pixels: a 32 x 2 patch (the two waves side by side) where the boxed path exists; kernels without it (more
@@ -270,7 +202,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
     float tf[DCH][NSRC][2];                                 // x and y fraction of the tap: the four weights are rebuilt per channel (2 registers instead of 4)
     uint32_t take = 0, give = 0;                            // bit d*NSRC+s: fold the west lane's east pair in / hand mine to the east lane
     uint32_t any_partial = 0, any_take = 0, any_hole = 0;   // wave-uniform: some lane of the wave has such a tap (hole: not a full tap)
-    uint32_t all_take = 0;                                  // wave-uniform: a 32-lane row of the patch is one run of cells, west to east, in both rows
     bool boxed = BOX;                                       // wave-uniform: every view's box fits
     int box_g0[NSRC];                                       // wave-uniform: element offset of the box's first cell inside an H x W plane
     int box_rows[NSRC];                                     // wave-uniform: rows of the box any full tap of the wave touches (the flush visits no other)
@@ -355,7 +286,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
                     if (__builtin_amdgcn_ballot_w64((e & TAP_PARTIAL) == TAP_PARTIAL) != 0) any_partial |= bit;
                     if (__builtin_amdgcn_ballot_w64(!full) != 0) any_hole |= bit;
                     if (__builtin_amdgcn_ballot_w64(tk) != 0) any_take |= bit;
-                    if (BOX && __builtin_amdgcn_ballot_w64(tk) == 0xfffffffefffffffeull) all_take |= bit;      // every lane but the two row starts
                 }
                 __builtin_amdgcn_sched_barrier(0);          // one view at a time: its 80 coefficients leave the SGPRs before the next view's arrive
             }
@@ -388,7 +318,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
     any_partial = __builtin_amdgcn_readfirstlane(any_partial);
     any_take = __builtin_amdgcn_readfirstlane(any_take);
     any_hole = __builtin_amdgcn_readfirstlane(any_hole);
-    all_take = __builtin_amdgcn_readfirstlane(all_take);
 
     // ---- B: channels ---------------------------------------------------------------------------------------------
     const float* refp = p.ref + (size_t)b * C * HW + pix;
@@ -425,7 +354,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
 #pragma unroll
     for (int k = 0; k < DCH; ++k) g_next[k] = gp[(size_t)min(k, d1 - d0 - 1) * HW];
 
-    if (SMVS_BWD_ABLATE & 16) { if (tt[0][0] == 0x12345u) p.grad_ref[lane] = tf[0][0][0] + (float)take + (float)give + (float)box_g0[0]; return; }
     if (BOX && boxed) {
         // ================================ boxed waves ==========================================================
         // DMA slot map of a feature box: lane l of instruction j lays down cells (row 4j + l/16, columns 4(l%16) .. +3); cells
@@ -433,7 +361,7 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
         // 1-2 source views: the four weights of every tap stay in registers over the channel loop ({nw, ne}, {sw, se}: 4 per tap instead of
         // the 2 fractions) -- rebuilding them per channel was 10 of a plane's 44 VALU instructions, and the plane loop is bound by VALU
         // issue + the LDS pipe at 2 waves per SIMD (round 6, profiles/r06_bwd_phases.txt); with more views the registers are not there.
-        constexpr bool KEEPW = SMVS_BWD_KEEP_WEIGHTS && NSRC <= 2;
+        constexpr bool KEEPW = NSRC <= 2;
         f32x2 kwn[KEEPW ? DCH : 1][NSRC], kws[KEEPW ? DCH : 1][NSRC];
         if constexpr (KEEPW) {
 #pragma unroll
@@ -492,23 +420,6 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
             }
         };
         auto flush_boxes = [&](int c) {                     // one atomic per touched cell: row i of the box, column = lane
-            if constexpr (SMVS_BWD_FLUSH_TOGETHER && NSRC <= 2) {
-                // every view's exchanges first, ONE wait (round 5: per view the wave sat through a full LDS round trip, twice per channel)
-                double d[NSRC][BOX_H];
-#pragma unroll
-                for (int s = 0; s < NSRC; ++s) gbox_take8_nowait(gbox_lds + (uint32_t)(s * GBOX_BYTES) + (uint32_t)lane * 8u, d[s]);
-                gbox_wait_all<NSRC>(d);
-#pragma unroll
-                for (int s = 0; s < NSRC; ++s) {
-                    float* q = p.grad_src[s] + ((size_t)b * C + c) * HW + box_g0[s] + lane;
-#pragma unroll
-                    for (int i = 0; i < BOX_H; ++i) {
-                        const float v = (float)d[s][i];
-                        if (v != 0.0f && !((SMVS_BWD_ABLATE & 1) && v != 1234.5f)) unsafeAtomicAdd(q + i * W, v);
-                    }
-                }
-                return;
-            }
 #pragma unroll
             for (int s = 0; s < NSRC; ++s) {
                 // only the rows some tap of the wave reaches (wave-uniform, known since the geometry: typically 3-4 of the 8) are
@@ -525,7 +436,7 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
                     for (int i = 0; i < NR; ++i) {
                         // untouched cells (still 0) send nothing: their lanes carry an out-of-range offset, which the range check drops
                         const float v = (float)d[i];
-                        const bool send = v != 0.0f && !((SMVS_BWD_ABLATE & 1) && v != 1234.5f);
+                        const bool send = v != 0.0f;
                         (void)llvm_raw_buffer_atomic_fadd_f32(v, rg.v, (int)(send ? gvo[s] : SMVS_OOB), so + i * W4, 0);
                     }
                 };
@@ -551,9 +462,7 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
             for (int k = 0; k < DCH; ++k) g_far[k] = gp[((size_t)min(1, C - 1) * D + min(k, d1 - d0 - 1)) * HW];
         }
         float gref_prev = 0.0f;
-        SMVS_BT(const unsigned long long bt_geo = bnow();)
         stage(0, 0);
-        if constexpr (NFB == 3) stage(min(1, C - 1), 1);
         auto channel = [&](const int c, float (&gcur)[DCH]) __attribute__((always_inline)) {
 #pragma unroll
             for (int k = 0; k < DCH; ++k)
@@ -561,34 +470,24 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
                 for (int s = 0; s < NSRC; ++s) asm volatile("" : "+v"(tt[k][s]));       // see the other loop
             // this channel's boxes, r (requested one iteration ago) and g (two iterations ago) have arrived once only the newest DCH
             // operations -- the gradient planes of channel c + 1 -- are still in flight
-            // (three box buffers: the boxes of channel c + 1 -- 2 NSRC instructions, issued in front of those planes -- may be in flight too)
-            SMVS_BT(const unsigned long long bt0 = bnow();)
-            if constexpr (NFB == 3) {
-                if (c == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NSRC) : "memory");     // (the prologue issued the boxes of channel 1 last)
-                else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NSRC + DCH) : "memory");
-            } else if (c == 0 || AHEAD == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the prologue issued the boxes last)
+            if (c == 0 || AHEAD == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the prologue issued the boxes last)
             else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(DCH) : "memory");
-            SMVS_BT(const unsigned long long bt1 = bnow(); bt_wait += bt1 - bt0;)
             const float r = r_next;
             float gq[DCH];
 #pragma unroll
             for (int k = 0; k < DCH; ++k) gq[k] = gcur[k];
             if (c > 0) {                                    // the previous channel's sums leave while this one is worked on
                 flush_boxes(c - 1);
-                if (!((SMVS_BWD_ABLATE & 4) && gref_prev != 1234.5f))
-                    (void)llvm_raw_buffer_atomic_fadd_f32(gref_prev, rgref.v, (int)(active ? pix4 : SMVS_OOB), (c - 1) * HW * 4, 0);
+                (void)llvm_raw_buffer_atomic_fadd_f32(gref_prev, rgref.v, (int)(active ? pix4 : SMVS_OOB), (c - 1) * HW * 4, 0);
             }
-            SMVS_BT(const unsigned long long bt2 = bnow(); bt_flush += bt2 - bt1;)
             {
                 const int cn = min(c + 1, C - 1), cf = min(c + AHEAD, C - 1);
                 r_next = llvm_raw_buffer_load_f32(rref.v, (int)pix4, cn * HW * 4, 0);     // (ahead of the boxes: it must have arrived by the next channel)
-                if constexpr (NFB == 3) stage(cf, (c + 2) % 3);
-                else stage(cn, (c + 1) & 1);
+                stage(cn, (c + 1) & 1);
                 load_planes(cf, gcur);
             }
-            SMVS_BT(const unsigned long long bt3 = bnow(); bt_issue += bt3 - bt2;)
             const int choff = c * HW * 4;
-            const uint32_t fpar = wave_lds + (uint32_t)((NFB == 3 ? c % 3 : (c & 1)) * NSRC * FBOX_BYTES);
+            const uint32_t fpar = wave_lds + (uint32_t)((c & 1) * NSRC * FBOX_BYTES);
             float gref = 0.0f;
             if (any_hole == 0) {
                 // Interior of the image (every tap of the chunk is a full tap, every lane and plane is live): straight-line code,
@@ -621,13 +520,13 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
                         wv[s] = t;
                         sum = sum + t;
                     }
-                    const float m = SMVS_BWD_MEAN_MUL ? sum * rV : div_by_views(sum, fV, rV);      // (the gradient's tolerance, not the forward's bits: one multiply)
+                    const float m = sum * rV;      // (the gradient's tolerance, not the forward's bits: one multiply)
                     gref = fmaf(g, r - m, gref);
 #pragma unroll
                     for (int s = 0; s < NSRC; ++s) {
                         const float gw = g * (wv[s] - m);
                         const f32x2 cn = wn[s] * gw, cs = ws[s] * gw;
-                        if (!(SMVS_BWD_ABLATE & 2)) gbox_add4(KEEPW ? tga[k][s] : gbox_lds + (uint32_t)(s * GBOX_BYTES) + 2u * tt[k][s], cn.x, cn.y, cs.x, cs.y);
+                        gbox_add4(KEEPW ? tga[k][s] : gbox_lds + (uint32_t)(s * GBOX_BYTES) + 2u * tt[k][s], cn.x, cn.y, cs.x, cs.y);
                     }
                 }
             } else
@@ -680,15 +579,14 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
                     const float c0 = cn.x, c1 = cn.y, c2 = cs.x, c3 = cs.y;
                     const uint32_t ga = gbox_lds + (uint32_t)(s * GBOX_BYTES) + 2u * e;
                     if (any_hole & bit) {
-                        if ((e & TAP_DROPPED) == 0) { if (!(SMVS_BWD_ABLATE & 2)) gbox_add4(ga, c0, c1, c2, c3); }
+                        if ((e & TAP_DROPPED) == 0) gbox_add4(ga, c0, c1, c2, c3);
                         else if ((e & TAP_PARTIAL) == TAP_PARTIAL) scatter_partial(e, s, c, c0, c1, c2, c3);
-                    } else if (!(SMVS_BWD_ABLATE & 2)) {
+                    } else {
                         gbox_add4(ga, c0, c1, c2, c3);
                     }
                 }
             }
             gref_prev = gref;
-            SMVS_BT(bt_planes += bnow() - bt3;)
         };
         if constexpr (AHEAD == 2) {
             for (int c = 0; c < C; c += 2) {
@@ -699,20 +597,7 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
             for (int c = 0; c < C; ++c) channel(c, g_next);
         }
         flush_boxes(C - 1);
-        if (!((SMVS_BWD_ABLATE & 4) && gref_prev != 1234.5f))
-            (void)llvm_raw_buffer_atomic_fadd_f32(gref_prev, rgref.v, (int)(active ? pix4 : SMVS_OOB), (C - 1) * HW * 4, 0);
-#ifdef SMVS_BWD_TIMING
-        if (lane == 0) {
-            atomicAdd(&smvs_bwd_timing[0], bt_geo - bt_start); atomicAdd(&smvs_bwd_timing[1], bt_wait); atomicAdd(&smvs_bwd_timing[2], bt_flush);
-            atomicAdd(&smvs_bwd_timing[3], bt_issue); atomicAdd(&smvs_bwd_timing[4], bt_planes); atomicAdd(&smvs_bwd_timing[5], bnow() - bt_start);
-            atomicAdd(&smvs_bwd_timing[7], 1ull);
-            if (any_hole == 0) {
-                // [6]: low 32 bits = plane-view pairs whose rows are single runs; bits 32.. = waves where ALL are; (reported by tools/wave_timing_bwd.py)
-                const bool every = all_take == (DCH * NSRC >= 32 ? 0xffffffffu : (1u << (DCH * NSRC)) - 1u);
-                atomicAdd(&smvs_bwd_timing[6], (unsigned long long)__builtin_popcount(all_take) + (every ? (1ull << 32) : 0ull));
-            }
-        }
-#endif
+        (void)llvm_raw_buffer_atomic_fadd_f32(gref_prev, rgref.v, (int)(active ? pix4 : SMVS_OOB), (C - 1) * HW * 4, 0);
         return;
     }
 
@@ -807,7 +692,7 @@ void costvol_bwd_kernel(const CostVolBwdParams p)
         }
 #pragma unroll
         for (int s = 0; s < NSRC; ++s) flush(s);
-        if (active && !((SMVS_BWD_ABLATE & 4) && gref != 1234.5f)) unsafeAtomicAdd(grefp + (size_t)c * HW, gref);
+        if (active) unsafeAtomicAdd(grefp + (size_t)c * HW, gref);
     }
 }
 
@@ -815,7 +700,7 @@ template <int GEO, int NSRC>
 static hipError_t launch_bwd_n(CostVolBwdParams p, hipStream_t st)
 {
     // planes per lane: the taps of a chunk live in registers (5 per tap)
-    constexpr int DCH = NSRC <= SMVS_BWD_DCH8_SRC ? 8 : NSRC <= 4 ? 4 : 2;
+    constexpr int DCH = NSRC <= DCH8_SRC ? 8 : NSRC <= 4 ? 4 : 2;
     p.dch = DCH < p.D ? DCH : p.D;
     p.dct = (p.D + DCH - 1) / DCH;
     const long long nb = (long long)p.xt * p.yt * p.dct * p.B;
@@ -841,15 +726,6 @@ static hipError_t launch_bwd(const CostVolBwdParams& p, hipStream_t st)
 
 }  // namespace smvs
 
-#ifdef SMVS_BWD_TIMING
-extern "C" SMVS_EXPORT int smvs_debug_timing_bwd(unsigned long long* out8, int reset)
-{
-    hipDeviceSynchronize();
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(smvs::smvs_bwd_timing), 64) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(smvs::smvs_bwd_timing), z, 64) != hipSuccess) return 1; }
-    return 0;
-}
-#endif
 
 extern "C" SMVS_EXPORT int smvs_costvol_bwd(int geo_kind, const float* grad_var, const float* ref_fea,
                                             const float* const* src_fea, int n_src, const double* geo,

@@ -185,10 +185,7 @@ void costvol_fwd_kernel(const CostVolParams p)
 
 // ---- geometry shared by the staged (LDS) kernel ----------------------------------------------------
 constexpr int WV_TX = 32, WV_TY = 2;          // ref pixels per wave
-#ifndef SMVS_WG_WAVES
-#define SMVS_WG_WAVES 2
-#endif
-constexpr int WV_WAVES = SMVS_WG_WAVES;       // waves per workgroup, stacked in y: 32 x 8 pixels
+constexpr int WV_WAVES = 2;                   // waves per workgroup, stacked in y: 32 x 8 pixels
 
 __device__ __forceinline__ int wave_min(int v)
 {
@@ -236,72 +233,17 @@ __device__ __forceinline__ int wave_max(int v)
 // group, so results never depend on which path ran.  Bits are identical to the direct kernel and to
 // the oracle.
 // =====================================================================================================
-#ifndef SMVS_BOX_W
-#define SMVS_BOX_W 44                 // staged box width: 11 chunks of 4 columns (a 40-column box from any 4-aligned origin)
-#endif
-#ifndef SMVS_ONE_BASE
-#define SMVS_ONE_BASE (-1)            // A/B switch of profiling builds
-#endif
-#ifndef SMVS_BOX_W8
-#define SMVS_BOX_W8 52                // ... of a box shared by 8 planes (3+ sources)
-#endif
-#ifndef SMVS_WAVES_PER_SIMD
-#define SMVS_WAVES_PER_SIMD 3
-#endif
-constexpr int DM_BW = SMVS_BOX_W;      // staged box width (columns)
-#ifndef SMVS_BOX_R
-#define SMVS_BOX_R 5
-#endif
-constexpr int DM_R = SMVS_BOX_R;        // staged box rows: 2 pixel rows + south tap + parallax/rotation slack
+constexpr int DM_BW = 44;               // staged box width: 11 chunks of 4 columns (a 40-column box from any 4-aligned origin)
+constexpr int DM_BW8 = 52;              // ... of a box shared by 8 planes (3+ sources)
+constexpr int DM_R = 5;                 // staged box rows: 2 pixel rows + south tap + parallax/rotation slack
 constexpr int DM_NBUF = 2;
-#ifndef SMVS_ABLATE
-#define SMVS_ABLATE 0                 // profiling builds only (tools/ab_build.sh x -DSMVS_ABLATE=n): 1 stores dropped, 2 no staging DMA, 4 no float64 chain, 8 no LDS tap reads, 32 no packed arithmetic, 64 staging DMA issued with every lane out of range (no memory traffic), 128 staging DMA from the first 64 KB of a channel (cache hits), 256 a step does not wait for its DMA to land, 512 no workgroup barrier per step (shared boxes) -- results are WRONG
-#endif
-#ifndef SMVS_O2P_PLANES
-#define SMVS_O2P_PLANES 4          // planes per evaluation pass of a source view's cubics
-#endif
-#ifndef SMVS_PC_PLANES
-#define SMVS_PC_PLANES 4           // ... and of the bivariate (plane-constant) chain: 6 folded coefficients per plane and cubic in SGPRs
-#endif
-#ifndef SMVS_WPS_DP8
-#define SMVS_WPS_DP8 2                // waves per SIMD the 8-plane instance is compiled for
-#endif
-#ifndef SMVS_WPS_DP8_FUSED
-#define SMVS_WPS_DP8_FUSED 2          // the same for the fused-arithmetic instance
-#endif
-#ifndef SMVS_WPS_NSRC34_DP2
-#define SMVS_WPS_NSRC34_DP2 2         // 3-4 sources, 1-2 planes per wave (166 VGPRs at 4 sources): waves per SIMD compiled for
-#endif
-#ifndef SMVS_WPS_NSRC34_DP4
-#define SMVS_WPS_NSRC34_DP4 2         // 3-4 sources, 4 planes per wave: waves per SIMD compiled for
-#endif
-#ifndef SMVS_NSRC34_DP
-#define SMVS_NSRC34_DP 4              // planes per wave of a 3-4 source sweep (A/B switch of profiling builds)
-#endif
-#ifndef SMVS_DP8_MINC
-#define SMVS_DP8_MINC 32              // fewest channels for which a sweep that divides into eights takes 8 planes per wave
-#endif
-#ifndef SMVS_DP8_HOMO
-#define SMVS_DP8_HOMO 1               // 8 planes per wave for the homography variant too (round 3: 0.557 vs 0.583 ms at 768x384x64, C=32)
-#endif
-#ifndef SMVS_DP8
-#define SMVS_DP8 1                    // 8 planes per wave for rpc C=32 sweeps (A/B switch of profiling builds)
-#endif
-#ifndef SMVS_STORE_AUX
-#define SMVS_STORE_AUX 2              // nt: the variance volume streams out once, keep it from evicting feature rows in L2
-#endif
-constexpr int STORE_AUX = SMVS_STORE_AUX;
-
-#ifdef SMVS_TIMING
-// profiling builds only (tools/ab_build.sh x -DSMVS_TIMING): per-wave phase stamps in shader clocks, read back through
-// smvs_debug_timing().  [0] geometry phase, [1] box + setup, [2] channel-pair loop, [3] of which spent in the vmcnt waits,
-// [4] of which in the lgkmcnt waits of the last plane, [5] DMA issue
-__device__ unsigned long long smvs_timing[12];      // [8] heights + plane check (prefetch), [9] reciprocal scales + ref view, [10] source views + taps
-__device__ __forceinline__ unsigned long long now() { unsigned long long t = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return t; }
-#define SMVS_T(...) __VA_ARGS__
-#else
-#define SMVS_T(...)
-#endif
+constexpr int O2P_PLANES = 4;           // planes per evaluation pass of a source view's cubics
+constexpr int PC_PLANES = 4;            // ... and of the bivariate (plane-constant) chain: 6 folded coefficients per plane and cubic in SGPRs
+// waves per SIMD the per-wave instances are compiled for: 3 at 1-2 sources and 1-4 planes per wave, 2 for the 8-plane instances
+// (exact and fused arithmetic) and at 3+ sources (166 VGPRs at 4 sources and 1-2 planes)
+constexpr int WPS_SMALL = 3, WPS_LARGE = 2;
+constexpr int DP8_MINC = 32;            // fewest channels for which a sweep that divides into eights takes 8 planes per wave
+constexpr int STORE_AUX = 2;            // nt: the variance volume streams out once, keep it from evicting feature rows in L2
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
@@ -327,7 +269,7 @@ struct TapD { uint32_t base[DM_NBUF]; f32x2 wn, ws; };       // base[parity] = L
 // over NWP x DP.  NWY = 0: every wave stages its own box and never meets a barrier (WV_WAVES waves stacked in y).
 template <int GEO, int NSRC, int CT, int DP, int AR, int NWY = 0, int NWP = 1, int WPS = 0>
 __global__ __launch_bounds__(NWY > 0 ? 64 * NWY * NWP : 64 * WV_WAVES,
-                             NWY > 0 ? WPS : (NSRC <= 2 && DP <= 4 ? SMVS_WAVES_PER_SIMD : NSRC <= 2 ? (AR == AR_FUSED ? SMVS_WPS_DP8_FUSED : SMVS_WPS_DP8) : (NSRC <= 4 && DP <= 2 ? SMVS_WPS_NSRC34_DP2 : NSRC <= 4 ? SMVS_WPS_NSRC34_DP4 : 2)))
+                             NWY > 0 ? WPS : NSRC <= 2 && DP <= 4 ? WPS_SMALL : WPS_LARGE)
 void costvol_dma_kernel(const CostVolParams p)
 {
     // Staging layout of one source box and channel pair: [row][channel of the pair][column] dwords, row pitch 2*BW; filled
@@ -337,26 +279,17 @@ void costvol_dma_kernel(const CostVolParams p)
     constexpr int NY = SHARED ? NWY : WV_WAVES;              // of which stacked in y
     // box width: 44 columns hold 4-5 planes of a 5-view 1536-wide tile (1.7 columns of parallax per plane at the steepest view);
     // a box shared by 8 planes takes 52
-    constexpr int BW = SHARED && DP * NWP >= 8 && NSRC > 2 ? SMVS_BOX_W8 : DM_BW, R = SHARED ? 2 * NWY + 3 : DM_R, C4 = BW / 4;
+    constexpr int BW = SHARED && DP * NWP >= 8 && NSRC > 2 ? DM_BW8 : DM_BW, R = SHARED ? 2 * NWY + 3 : DM_R, C4 = BW / 4;
     constexpr int SLOTS = R * 2 * C4;                        // 16-byte chunks per source box and channel pair
     constexpr int NI = (SLOTS + 63) / 64;                    // DMA instructions per source box and channel pair
     constexpr int SRC_DW = NI * 256;                         // dwords per source box, padded to whole DMA instructions
     constexpr int BUF_DW = NSRC * SRC_DW;
     constexpr int ZPAD_DW = 3 * BW + 4;                      // always-zero dwords a dropped tap reads (offsets 0 .. 3*BW+1)
-    // ONE_BASE: a tap keeps one LDS address (buffer 0) and the odd steps add the buffer pitch -- one VALU add per tap and odd
-    // step for NSRC * DP fewer registers; every buffer is then followed by its own zero cells, so that a dropped tap's address
-    // moves with the others.  Taken where registers decide the occupancy (the shared form, 3+ sources).
-    constexpr bool ONE_BASE = SMVS_ONE_BASE >= 0 ? (SHARED && SMVS_ONE_BASE) : (SHARED && WPS >= 3 && NSRC > 2);
-    constexpr int BUFP_DW = ONE_BASE ? BUF_DW + ZPAD_DW : BUF_DW;       // buffer pitch
-    constexpr int TILE_DW = ONE_BASE ? DM_NBUF * BUFP_DW : DM_NBUF * BUF_DW + ZPAD_DW;
+    constexpr int TILE_DW = DM_NBUF * BUF_DW + ZPAD_DW;
     constexpr int NSTEP = CT / 2;
     static_assert(BW % 4 == 0 && CT % 2 == 0 && 2 * DP + 2 <= 63 && DP * NSRC <= 32, "chunks / steps / vmcnt bookkeeping / tap mask");
     __shared__ __attribute__((aligned(16))) uint32_t tile_all[SHARED ? 1 : WV_WAVES][(TILE_DW + 3) & ~3];
     __shared__ __attribute__((aligned(16))) int xch[SHARED ? NW : 1][NSRC][4];   // shared form: every wave's tap extents
-#ifdef SMVS_LDS_PAD
-    __shared__ float lds_pad[SMVS_LDS_PAD / 4];            // profiling builds only: caps the workgroups per CU
-    if (p.B < 0) lds_pad[threadIdx.x] = 0.0f;
-#endif
     // one wave = one 32 x 2 pixel patch x ONE group of DP planes (p.dch == DP): no loop over groups, so
     // nothing of the geometry phase stays live across the channel-pair loop
     uint32_t L = xcd_remap(blockIdx.x, gridDim.x);
@@ -401,11 +334,7 @@ void costvol_dma_kernel(const CostVolParams p)
 
     // zero cells behind each buffer: a tap whose footprint misses the image reads these, so it
     // contributes 0 * weight exactly like four masked gathers (0, or NaN for a NaN coordinate)
-    if constexpr (ONE_BASE) {
-        for (int i = lane; i < ZPAD_DW; i += 64) tile[BUF_DW + i] = tile[BUFP_DW + BUF_DW + i] = 0u;     // (every wave writes the same zeros)
-    } else {
-        for (int i = lane; i < ZPAD_DW; i += 64) tile[DM_NBUF * BUF_DW + i] = 0u;
-    }
+    for (int i = lane; i < ZPAD_DW; i += 64) tile[DM_NBUF * BUF_DW + i] = 0u;
 
     const float fV = (float)p.V;
     const float rV = p.rV;
@@ -418,9 +347,8 @@ void costvol_dma_kernel(const CostVolParams p)
     const double fx = (double)min(x, W - 1), fy = (double)min(y, H - 1);
     const uint32_t pix4 = (uint32_t)pix * 4u;
 
-    SMVS_T(const unsigned long long t_start = now(); unsigned long long t_vm = 0, t_dma = 0, t_st = 0;)
     constexpr int PC_LPR = (DP * PC_PER_CUBIC * 8 + 63) / 64 + (DP * PC_PER_CUBIC * 8 % 64 ? 1 : 0);      // 64-byte lines per coefficient run of DP planes
-    const bool pc_maybe = GEO == 0 && p.pc != nullptr && p.depth_is_4d != HEIGHT_GENERATED && !(SMVS_ABLATE & 4) && np > 0;     // (np <= 0: shared form, a wave past the last plane only stages)
+    const bool pc_maybe = GEO == 0 && p.pc != nullptr && p.depth_is_4d != HEIGHT_GENERATED && np > 0;     // (np <= 0: shared form, a wave past the last plane only stages)
     const int dg0 = min(dg, p.d_end - 1);
     // heights of the group's planes (tail planes shadow the last one; they are never stored)
     float hf[DP];
@@ -454,7 +382,6 @@ void costvol_dma_kernel(const CostVolParams p)
     }
 
     bool use_pc = false;
-    SMVS_T(const unsigned long long t_chk = now();)
     // ---- A: taps of the group's planes -----------------------------------------------------------
     TapD tap[DP][NSRC];
     uint32_t txy[DP][NSRC];
@@ -470,7 +397,7 @@ void costvol_dma_kernel(const CostVolParams p)
     ref_n.a = ref_n.b = ref_n.h = 0.0;
 #pragma unroll
     for (int s = 0; s < NSRC; ++s) src_n[s].a = src_n[s].b = src_n[s].h = 0.0;
-    if (GEO == 0 && !(SMVS_ABLATE & 4)) {
+    if (GEO == 0) {
         // The 3 reciprocal scales of every view, in VGPRs (18 SGPRs would not survive the coefficient loads).
         if (pc_maybe) {
             // the fold kernel divided already (smvs_device.h, PC_SCALES): scalar loads out of the workspace, copied to VGPRs
@@ -491,9 +418,8 @@ void costvol_dma_kernel(const CostVolParams p)
             }
         }
     }
-    SMVS_T(const unsigned long long t_ref = now();)
     // PQ planes per pass: every source coefficient is fetched into SGPRs once for all of them
-    constexpr int PQ = DP < SMVS_O2P_PLANES ? DP : SMVS_O2P_PLANES;
+    constexpr int PQ = DP < O2P_PLANES ? DP : O2P_PLANES;
     static_assert(DP % PQ == 0, "planes per pass");
     // Planes and source views for the heights hh.  PC: every plane's height is the one its coefficients were folded for (the bivariate
     // source cubics, smvs_device.h); else the trivariate chain.
@@ -502,7 +428,7 @@ void costvol_dma_kernel(const CostVolParams p)
         okmask = 0;
 #pragma unroll
         for (int s = 0; s < NSRC; ++s) { lo_x[s] = lo_y[s] = INT_MAX; hi_x[s] = hi_y[s] = INT_MIN; }
-        if (GEO == 0 && !(SMVS_ABLATE & 4)) {
+        if (GEO == 0) {
             // ref view, image -> ground: plane-invariant part once per pixel, Horner in the height per plane.  (Formed inside, so that the
             // 24 registers of the pixel part die before the source passes: a wave that has to redo its planes forms them again.)
             P2OPix px;
@@ -515,18 +441,12 @@ void costvol_dma_kernel(const CostVolParams p)
 #pragma unroll
             for (int s = 0; s < NSRC; ++s) {
                 float gxs[PQ], gys[PQ];
-                if (SMVS_ABLATE & 4) {
-#pragma unroll
-                    for (int u = 0; u < PQ; ++u) {
-                        gxs[u] = ((float)fx + 0.37f + 0.011f * hh[pq + u] * (float)(s + 1)) / half_wm1 - 1.0f;
-                        gys[u] = ((float)fy + 0.21f) / half_hm1 - 1.0f;
-                    }
-                } else if (GEO == 0) {
+                if (GEO == 0) {
                     double samp[PQ], line[PQ];
                     if constexpr (PC) {
                         // planes per pass of the bivariate chain: 4 where the instance has 256 registers (8 planes per wave, 2 waves per SIMD), 2 in the
                         // 168-register instances (9 monomial registers pairs per plane in flight: 4 planes spilled 20 registers to scratch)
-                        constexpr int PQW = DP >= 8 ? SMVS_PC_PLANES : 2, PQC = PQ < PQW ? PQ : PQW;
+                        constexpr int PQW = DP >= 8 ? PC_PLANES : 2, PQC = PQ < PQW ? PQ : PQW;
 #pragma unroll
                         for (int v = 0; v < PQ; v += PQC)
                             o2p_pc_xn<PQC>(geo_d + (size_t)(s + 1) * RPC_LEN, src_n[s], lat + pq + v, lon + pq + v,
@@ -632,7 +552,6 @@ void costvol_dma_kernel(const CostVolParams p)
         }
     }
 
-    SMVS_T(const unsigned long long t_geo = now();)
     // ---- B: the wave's bounding box per source -------------------------------------------------------
     // The box origin is moved left onto a chunk grid that the image edge it may touch falls on (column 0, or column W
     // when the last column a tap reads lies within a chunk of the right edge and W is not a multiple of 4): a 16-byte
@@ -712,8 +631,6 @@ void costvol_dma_kernel(const CostVolParams p)
                 const int gx = bxs + col, gy = bys + row;
                 const bool valid = (row < bhs) && (col < bws) && ((uint32_t)gy < (uint32_t)H) && (gx >= 0) && (gx + 4 <= W);
                 vk[k] = valid ? (uint32_t)(rel + (bys * W + bxs) * 4) : SMVS_OOB;
-                if (SMVS_ABLATE & 64) vk[k] = SMVS_OOB;
-                if (SMVS_ABLATE & 128) vk[k] = valid ? (vk[k] & 0xfff0u) : SMVS_OOB;
                 usek[k] = (i < NDMA) && (64 * j < bhs * 2 * C4);
                 dstk[k] = (uint32_t)(sk * SRC_DW * 4 + j * 1024);
                 rsk[k] = make_rsrc(sp + (size_t)b * CT * HW, (uint32_t)CT * (uint32_t)HW * 4u);
@@ -730,8 +647,6 @@ void costvol_dma_kernel(const CostVolParams p)
                 const int gx = bx0[s] + col, gy = by0[s] + row;
                 const bool valid = (row < bh[s]) && (col < bw[s]) && ((uint32_t)gy < (uint32_t)H) && (gx >= 0) && (gx + 4 <= W);
                 vo[s][j] = valid ? (uint32_t)(rel + (by0[s] * W + bx0[s]) * 4) : SMVS_OOB;
-                if (SMVS_ABLATE & 64) vo[s][j] = SMVS_OOB;
-                if (SMVS_ABLATE & 128) vo[s][j] = valid ? (vo[s][j] & 0xfff0u) : SMVS_OOB;
             }
         }
         }
@@ -742,14 +657,14 @@ void costvol_dma_kernel(const CostVolParams p)
                 const bool ok = (okmask >> (pl * NSRC + s)) & 1u;
                 const int box0 = s * SRC_DW - ((by0[s] + 1) * (2 * BW) + bx0[s] + 1);      // wave-uniform
                 const uint32_t a = tile_lds + 4u * (uint32_t)((int)txy[pl][s] + box0);
-                const uint32_t z = tile_lds + 4u * (uint32_t)(ONE_BASE ? BUF_DW : DM_NBUF * BUF_DW);
+                const uint32_t z = tile_lds + 4u * (uint32_t)(DM_NBUF * BUF_DW);
                 tap[pl][s].base[0] = ok ? a : z;
-                tap[pl][s].base[1] = ONE_BASE ? 0u : ok ? a + 4u * (uint32_t)BUF_DW : z;
+                tap[pl][s].base[1] = ok ? a + 4u * (uint32_t)BUF_DW : z;
             }
         uint32_t ovo[DP];                                 // per-plane byte offset of this pixel inside one channel volume
 #pragma unroll
         for (int pl = 0; pl < DP; ++pl)
-            ovo[pl] = (active && pl < np && !(SMVS_ABLATE & 1)) ? (uint32_t)((SMVS_ABLATE & 16) ? ((dg + pl) & 3) : (dg + pl - p.d_begin + p.d_out_off)) * (uint32_t)HW * 4u + pix4
+            ovo[pl] = (active && pl < np) ? (uint32_t)(dg + pl - p.d_begin + p.d_out_off) * (uint32_t)HW * 4u + pix4
                                           : SMVS_OOB;       // inactive lanes / tail planes: store dropped by the range check
 
         // (s, j) are unrolled loop indices but not constant expressions: dispatch to the immediate-offset variant
@@ -773,8 +688,7 @@ void costvol_dma_kernel(const CostVolParams p)
 #pragma unroll
         for (int s = 0; s < NSRC; ++s) ni[s] = (bh[s] * 2 * C4 + 63) >> 6;
         auto issue_dma = [&](int st) {
-            if (SMVS_ABLATE & 2) return;
-            const uint32_t buf = tile_lds + (uint32_t)((st & 1) * BUFP_DW * 4);
+            const uint32_t buf = tile_lds + (uint32_t)((st & 1) * BUF_DW * 4);
             const int choff = 2 * st * HW * 4;
             if constexpr (SHARED) {
 #pragma unroll
@@ -792,7 +706,6 @@ void costvol_dma_kernel(const CostVolParams p)
             }
         };
 
-        SMVS_T(const unsigned long long t_setup = now();)
         // prologue: pair 0
         // ref feature pairs run two steps ahead of their use, in registers
         f32x2 ref0, ref1;
@@ -811,20 +724,16 @@ void costvol_dma_kernel(const CostVolParams p)
             // offset).  vmcnt retires in order, so DMA(st) has landed once at most that many
             // operations are outstanding.
             const f32x2 refc = ref0;
-            SMVS_T(const unsigned long long tw0 = now();)
-            if (SMVS_ABLATE & 256) { if (st == 0) wait_vmcnt<0>(); }      // profiling: the landing of DMA(st) is not waited for
-            else if (st == 0) wait_vmcnt<0>();
+            if (st == 0) wait_vmcnt<0>();
             else if (st + 1 < NSTEP) wait_vmcnt<2 * DP + 2>();
             else wait_vmcnt<2 * DP>();
             // shared form: my part of DMA(st) has landed -> so has everybody's, and everybody has finished step st-1, whose
             // buffer DMA(st+1) is about to overwrite.  (A wave's LDS reads of step st-1 have all returned: its last unit
             // waited for lgkmcnt(0).)
-            if constexpr (SHARED) { if (!(SMVS_ABLATE & 512)) asm volatile("s_barrier" ::: "memory"); }
-            SMVS_T(const unsigned long long tw1 = now(); t_vm += tw1 - tw0;)
+            if constexpr (SHARED) asm volatile("s_barrier" ::: "memory");
             ref0 = ref1;
             if (st + 1 < NSTEP) {
                 issue_dma(st + 1);
-                SMVS_T(t_dma += now() - tw1;)
                 const int nx = (st + 2 < NSTEP) ? 2 * st + 4 : 0;   // dummy reload keeps the count constant
                 ref1.x = llvm_raw_buffer_load_f32(rref.v, (int)pix4, nx * HW * 4, 0);
                 ref1.y = llvm_raw_buffer_load_f32(rref.v, (int)pix4, (nx + 1) * HW * 4, 0);
@@ -847,23 +756,16 @@ void costvol_dma_kernel(const CostVolParams p)
             const f32x2 rvv = {rV, fV};
             auto read_unit = [&](int u) {
                 const int pl = u / UPP, s0 = (u % UPP) * US;
-                if (SMVS_ABLATE & 8) {
-#pragma unroll
-                    for (int k = 0; k < US; ++k) cv[u & 1][k][0] = cv[u & 1][k][1] = cv[u & 1][k][2] = cv[u & 1][k][3] = tap[pl][s0 + k].wn;
-                    return;
-                }
 #pragma unroll
                 for (int k = 0; k < US; ++k)
-                    lds_read_tap_planar<BW>(ONE_BASE ? tap[pl][s0 + k].base[0] + (uint32_t)(PAR * BUFP_DW * 4) : tap[pl][s0 + k].base[PAR],
+                    lds_read_tap_planar<BW>(tap[pl][s0 + k].base[PAR],
                                             cv[u & 1][k][0], cv[u & 1][k][1], cv[u & 1][k][2], cv[u & 1][k][3]);
             };
             auto store_plane = [&](int pl, f32x2 var) {
-                SMVS_T(const unsigned long long ts0 = now();)
                 llvm_raw_buffer_store_f32(var.x, ro.v, (int)ovo[pl], 0, STORE_AUX);
                 llvm_raw_buffer_store_f32(var.y, ro.v, (int)ovo[pl], och1, STORE_AUX);
-                SMVS_T(t_st += now() - ts0;)
             };
-            if constexpr (AR == AR_FUSED && !(SMVS_ABLATE & (8 | 32))) {
+            if constexpr (AR == AR_FUSED) {
                 // Fused arithmetic: differences to the ref feature straight out of the bilinear chains (weights and ref
                 // pre-scaled), variance in 3 (2 sources) / 1 (1 source) / 2 S + 1 (S sources) packed operations; the tail
                 // of a unit rides in the gaps of the next unit's bilinear block (smvs_device.h).
@@ -929,8 +831,7 @@ void costvol_dma_kernel(const CostVolParams p)
                 if (u + 1 < NU) read_unit(u + 1);
                 // reads per unit = 4*US; everything older than the next unit's reads has returned
                 f32x2 (&c)[US][4] = cv[u & 1];
-                if (SMVS_ABLATE & 8) {
-                } else if constexpr (US == 1) {
+                if constexpr (US == 1) {
                     f32x2 d0, d1, d2, d3;
                     d0 = d1 = d2 = d3 = (f32x2)(0.0f);
                     if (u + 1 < NU) lds_wait<4>(c[0][0], c[0][1], c[0][2], c[0][3], d0, d1, d2, d3);
@@ -941,10 +842,6 @@ void costvol_dma_kernel(const CostVolParams p)
                 }
                 const int pl = u / UPP, k = u % UPP, s0 = k * US;
                 f32x2 a, b;
-                if (SMVS_ABLATE & 32) {
-                    if (u > 0 && k == 0) store_plane(pl - 1, c[0][0]);
-                    continue;
-                }
                 if constexpr (US == 2) pk_bilinear2(a, b, c[0][0], c[0][1], c[0][2], c[0][3], tap[pl][s0].wn, tap[pl][s0].ws,
                                                     c[1][0], c[1][1], c[1][2], c[1][3], tap[pl][s0 + 1].wn, tap[pl][s0 + 1].ws);
                 else                   pk_bilinear1(a, c[0][0], c[0][1], c[0][2], c[0][3], tap[pl][s0].wn, tap[pl][s0].ws);
@@ -959,30 +856,17 @@ void costvol_dma_kernel(const CostVolParams p)
                     else                   pk_accumulate1(accS[k & 1], accT[k & 1], sin, tin, a);
                 }
             }
-            if (SMVS_ABLATE & 32) store_plane(DP - 1, cv[0][0][1]);
-            else store_plane(DP - 1, pk_variance<1>(T, S));
+            store_plane(DP - 1, pk_variance<1>(T, S));
         };
         static_assert(NSTEP % 2 == 0, "two steps per loop iteration");
         for (int st = 0; st < NSTEP; st += 2) {
             step(st, std::integral_constant<int, 0>());
             step(st + 1, std::integral_constant<int, 1>());
         }
-#ifdef SMVS_TIMING
-        {
-            const unsigned long long t_end = now();
-            if (lane == 0) {
-                atomicAdd(&smvs_timing[0], t_geo - t_start); atomicAdd(&smvs_timing[1], t_setup - t_geo);
-                atomicAdd(&smvs_timing[2], t_end - t_setup); atomicAdd(&smvs_timing[3], t_vm);
-                atomicAdd(&smvs_timing[5], t_dma); atomicAdd(&smvs_timing[4], t_st); atomicAdd(&smvs_timing[7], 1ull);
-                atomicAdd(&smvs_timing[8], t_chk - t_start); atomicAdd(&smvs_timing[9], t_ref - t_chk); atomicAdd(&smvs_timing[10], t_geo - t_ref);
-            }
-        }
-#endif
     } else {
         // ---- fallback: direct gathers for this plane group (box larger than the staged tile).
         //      Rare and wave-uniform; the source taps are rebuilt plane by plane from the ground point
         //      of phase A in a rolled loop (same float64 values as the staged path would have used).
-        SMVS_T(if (lane == 0) atomicAdd(&smvs_timing[6], 1ull);)      // waves that took the fallback
         const float* refp = p.ref + (size_t)b * CT * HW + pix;
         float* outp = p.out + (size_t)b * CT * p.D_out * HW + pix;
 #pragma unroll 1
@@ -1044,32 +928,19 @@ void costvol_dma_kernel(const CostVolParams p)
 }
 
 // Kernel choice.  The staged kernel serves 2-8 views at C = 8/16/32 (one channel volume of the output < 2 GiB);
-// everything else (and SMVS_COSTVOL_DIRECT=1 in tuning builds) takes the direct-gather kernel.  Both produce
+// everything else takes the direct-gather kernel.  Both produce
 // identical bits.  Planes per wave (DP): a whole sweep is cut into groups of 8 (2-3 views) or 4 planes (the taps of a
 // group live in registers; with 3-4 sources the LDS tiles allow two workgroups per CU, i.e. 256 VGPRs per lane), the
 // plane-at-a-time launches of the pred loop get DP = 1 so that no float64 work is spent on planes that are not stored.
-enum { K_DIRECT = 0, K_DMA = 2 };
-
-static int kernel_choice()
-{
-    return tune_int("SMVS_COSTVOL_DIRECT", 0) == 1 ? K_DIRECT : K_DMA;      // A/B switch (tuning builds only)
-}
-
 // Order of the workgroups of one band of rows (an XCD sweeps a run of consecutive workgroups, xcd_remap): x tile fastest, then
 // plane chunk -- every plane chunk walks the band's source rows once more and finds them in that XCD's L2 (4 MiB) as long as the
 // band's staged rows fit: rows x sources x channels x W x 4 B = 1 MB at the metric shape (traffic 1.007 x algorithmic).  At
 // 5 views x 1536 columns the band is 3.9 MB: every chunk missed and the features came from HBM once per plane chunk (FETCH_SIZE
 // 1.58 GB against 0.755 GB for the 8-plane shard, 12 GB for the 64-plane sweep; profiles/r04_cfg4_summary.txt).  Above 1.5 MB
 // the plane chunk runs fastest instead: all plane chunks of an x tile are in flight together and share ~0.1 MB.
-#ifndef SMVS_CHUNK_MAJOR
-#define SMVS_CHUNK_MAJOR (-1)         // A/B switch of profiling builds: 0 / 1 force an order
-#endif
-#ifndef SMVS_GROUP_ROWS
-#define SMVS_GROUP_ROWS 8            // tile rows per group of the chunk-major order (shared-box form; A/B switch of profiling builds)
-#endif
+constexpr int GROUP_ROWS = 8;          // tile rows per group of the chunk-major order (shared-box form)
 static int launch_order(const CostVolParams& p, int rows, int nsrc)
 {
-    if (SMVS_CHUNK_MAJOR >= 0) return SMVS_CHUNK_MAJOR;
     return (long long)rows * nsrc * p.C * p.W * 4 > 1536 * 1024 ? 1 : 0;
 }
 
@@ -1085,18 +956,12 @@ static hipError_t launch_staged(CostVolParams p, hipStream_t st)
     const long long nb = (long long)p.xt * p.yt * p.dct * p.B;
     if (nb >= (1ll << 31)) return hipErrorInvalidValue;
     dim3 blk(64 * WV_WAVES), grd((unsigned)nb);
-#ifdef SMVS_ONLY_BENCH
-    // profiling builds: only the instances the headline bench launches (seconds instead of a minute to compile)
-    if constexpr (GEO == 0 && (NSRC == 2 || NSRC == 4) && DP >= 2) { if (p.C == 32) hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 32, DP, AR>), grd, blk, 0, st, p); }
-    return hipGetLastError();
-#else
     switch (p.C) {
     case 8:  hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 8, DP, AR>), grd, blk, 0, st, p); break;
     case 16: hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 16, DP, AR>), grd, blk, 0, st, p); break;
     default: hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 32, DP, AR>), grd, blk, 0, st, p); break;
     }
     return hipGetLastError();
-#endif
 }
 
 // Shared-box form: a workgroup = NWY x NWP waves = 32 x 2 NWY pixels x DP NWP planes
@@ -1109,55 +974,20 @@ static hipError_t launch_shared(CostVolParams p, hipStream_t st)
     p.dch = DP;
     p.dct = (nd + DP * NWP - 1) / (DP * NWP);
     p.chunk_major = launch_order(p, WV_TY * NWY + 3, NSRC);
-    p.group_rows = SMVS_GROUP_ROWS;
+    p.group_rows = GROUP_ROWS;
     const long long nb = (long long)p.xt * p.yt * p.dct * p.B;
     if (nb >= (1ll << 31)) return hipErrorInvalidValue;
     dim3 blk(64 * NWY * NWP), grd((unsigned)nb);
-#ifdef SMVS_ONLY_BENCH
-    if (p.C == 32) hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 32, DP, AR, NWY, NWP, WPS>), grd, blk, 0, st, p);
-    return hipGetLastError();
-#else
     switch (p.C) {
     case 8:  hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 8, DP, AR, NWY, NWP, WPS>), grd, blk, 0, st, p); break;
     case 16: hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 16, DP, AR, NWY, NWP, WPS>), grd, blk, 0, st, p); break;
     default: hipLaunchKernelGGL((costvol_dma_kernel<GEO, NSRC, 32, DP, AR, NWY, NWP, WPS>), grd, blk, 0, st, p); break;
     }
     return hipGetLastError();
-#endif
 }
 
 // shared-box configuration of the 3-4 source sweeps (4+ planes): planes per wave, waves in y, waves along planes, waves per SIMD
-#ifndef SMVS_N34_SHARED
-#define SMVS_N34_SHARED 1
-#endif
-#ifndef SMVS_N34_DP
-#define SMVS_N34_DP 4
-#endif
-#ifndef SMVS_N34_NWY
-#define SMVS_N34_NWY 2
-#endif
-#ifndef SMVS_N34_NWP
-#define SMVS_N34_NWP 2
-#endif
-#ifndef SMVS_N34_WPS
-#define SMVS_N34_WPS 2
-#endif
-// ... and of the 1-2 source sweeps that divide into eights at C = 32 (A/B switch; 0 = every wave its own box)
-#ifndef SMVS_N2_SHARED
-#define SMVS_N2_SHARED 0
-#endif
-#ifndef SMVS_N2_DP
-#define SMVS_N2_DP 8
-#endif
-#ifndef SMVS_N2_NWY
-#define SMVS_N2_NWY 2
-#endif
-#ifndef SMVS_N2_NWP
-#define SMVS_N2_NWP 1
-#endif
-#ifndef SMVS_N2_WPS
-#define SMVS_N2_WPS 2
-#endif
+constexpr int N34_DP = 4, N34_NWY = 2, N34_NWP = 2, N34_WPS = 2;
 
 template <int GEO, int NSRC, int AR>
 static hipError_t launch_ct(CostVolParams p, hipStream_t st)
@@ -1169,7 +999,7 @@ static hipError_t launch_ct(CostVolParams p, hipStream_t st)
         // exact-division argument of div_half_int
         const bool staged_ok = (p.C == 8 || p.C == 16 || p.C == 32) && p.W >= 2 && p.H >= 2 && p.W < 65535 && p.H < 65535 &&
                                (long long)p.D_out * p.H * p.W * 4 < (1ll << 31);
-        if (kernel_choice() != K_DIRECT && staged_ok) {
+        if (staged_ok) {
             if (nd == 1) return launch_staged<GEO, NSRC, 1, AR>(p, st);
             // 6-8 views: 4 planes x 5-7 sources of tap state need more than 256 registers (one wave per SIMD) -> 2 planes per wave
             if (nd == 2 || NSRC > 4) return launch_staged<GEO, NSRC, 2, AR>(p, st);
@@ -1177,16 +1007,9 @@ static hipError_t launch_ct(CostVolParams p, hipStream_t st)
             // voxel and the ref view's plane-invariant part amortised over twice the planes outweigh the drop to two
             // waves per SIMD (219 VGPRs) -- measured 0.699 vs 0.717 ms at the metric shape; at C = 8 (float64-bound) 4 planes per
             // wave stay faster (0.053 vs 0.061 ms)
-#if SMVS_N2_SHARED
-            if constexpr (NSRC <= 2 && GEO == 0) { if (nd % 8 == 0 && p.C == 32) return launch_shared<GEO, NSRC, SMVS_N2_DP, AR, SMVS_N2_NWY, SMVS_N2_NWP, SMVS_N2_WPS>(p, st); }
-#endif
-#if SMVS_N34_SHARED
-            if constexpr (NSRC > 2 && NSRC <= 4) { if (nd % (SMVS_N34_DP * SMVS_N34_NWP) == 0) return launch_shared<GEO, NSRC, SMVS_N34_DP, AR, SMVS_N34_NWY, SMVS_N34_NWP, SMVS_N34_WPS>(p, st); }
-#endif
-#if SMVS_DP8
-            if constexpr (NSRC <= 2 && (GEO == 0 || SMVS_DP8_HOMO)) { if (nd % 8 == 0 && p.C >= SMVS_DP8_MINC) return launch_staged<GEO, NSRC, 8, AR>(p, st); }
-#endif
-            if constexpr (NSRC > 2 && NSRC <= 4 && SMVS_NSRC34_DP == 2) return launch_staged<GEO, NSRC, 2, AR>(p, st);
+            if constexpr (NSRC > 2 && NSRC <= 4) { if (nd % (N34_DP * N34_NWP) == 0) return launch_shared<GEO, NSRC, N34_DP, AR, N34_NWY, N34_NWP, N34_WPS>(p, st); }
+            // (the homography variant too: 0.557 vs 0.583 ms at 768x384x64, C = 32, round 3)
+            if constexpr (NSRC <= 2) { if (nd % 8 == 0 && p.C >= DP8_MINC) return launch_staged<GEO, NSRC, 8, AR>(p, st); }
             if constexpr (NSRC <= 4) return launch_staged<GEO, NSRC, 4, AR>(p, st);
         }
     }
@@ -1197,14 +1020,12 @@ static hipError_t launch_ct(CostVolParams p, hipStream_t st)
     const long long nblocks = (long long)p.xt * p.yt * p.dct * p.B;
     if (nblocks >= (1ll << 31)) return hipErrorInvalidValue;
     dim3 blk(TILE_X, TILE_Y);
-#ifndef SMVS_ONLY_BENCH
     switch (p.C) {
     case 8:  hipLaunchKernelGGL((costvol_fwd_kernel<GEO, NSRC, 8, AR>), dim3(nblocks), blk, 0, st, p); break;
     case 16: hipLaunchKernelGGL((costvol_fwd_kernel<GEO, NSRC, 16, AR>), dim3(nblocks), blk, 0, st, p); break;
     case 32: hipLaunchKernelGGL((costvol_fwd_kernel<GEO, NSRC, 32, AR>), dim3(nblocks), blk, 0, st, p); break;
     default: hipLaunchKernelGGL((costvol_fwd_kernel<GEO, NSRC, 0, AR>), dim3(nblocks), blk, 0, st, p); break;
     }
-#endif
     return hipGetLastError();
 }
 

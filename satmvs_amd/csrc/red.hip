@@ -38,15 +38,8 @@ constexpr int COT = 8;                       // output channels per lane
 // stage): depth 2/3 + scalar weights 3.70 / 3.44 / 2.45; depth 4/6 3.58 / 3.63 / 2.57; depth 4/6 + weights through
 // LDS 3.50 / 4.15 / 2.83 -- the deeper variants shave the 192x96 stage and cost more on the larger ones (registers,
 // code size, an LDS copy per workgroup), so the shallow ones ship.
-#ifndef SMVS_CONV_PREFETCH
-#define SMVS_CONV_PREFETCH 2                 // channels of taps in flight per wave in the direct convolutions
-#endif
-#ifndef SMVS_WLDS
-#define SMVS_WLDS 0                          // 1: channel-split direct kernels read their weights from LDS instead of scalar loads
-#endif
-#ifndef SMVS_CONVT_PREFETCH
-#define SMVS_CONVT_PREFETCH 3
-#endif
+constexpr int CONV_PREFETCH = 2;             // channels of taps in flight per wave in the direct convolutions
+constexpr int CONVT_PREFETCH = 3;            // ... in the transposed convolution
 constexpr int NSLOT = 64;                    // GroupNorm statistics are accumulated in 64 partial slots per
                                              // (sample, norm group): ~36 same-address float64 atomics per slot
                                              // instead of ~18000 on one address (measured: 237 us -> 25 us for the full-resolution gate convolution)
@@ -141,10 +134,7 @@ struct ConvArgs {
     // s / inA_bmod) when inA_bmod > 0, else (batch s, plane 0); its first channel starts at
     // inA + batch*inA_bs + plane*inA_ps and channels are inA_cs floats apart.
     size_t inA_cs, inA_bs, inA_ps; int inA_bmod;
-    // Partial convolution over a slice of the layer's input channels (the ConvGRU convolutions split into their state-independent
-    // and state-dependent halves, see issue_front): the packed weights hold CinW input channels (0 = CA + CB), this launch uses
-    // channels wc0 .. wc0 + CA + CB - 1 of them; `init` (same shape as out, or null) is added to the sums before the statistics.
-    const float* init; int wc0, CinW;
+    const float* init;                       // same shape as out, or null: added to the sums before the statistics (smvs_conv3x3_fwd)
 };
 
 typedef const float __attribute__((address_space(4))) * cw_t;
@@ -163,21 +153,12 @@ __device__ __forceinline__ float wave_sum_f(float v)
 //   LDS.  The coarse planes give a few dozen workgroups on a 256-CU part: there the time is one wave's
 //   serial channel loop (a load round trip per channel), so 4x shorter chains = ~3x shorter kernels.
 // Both: the taps of the next channels are in flight while channel c is multiplied.
-// SPLIT with SMVS_WLDS stages the workgroup's weights ([Cin][9][COT], Cin <= WLDS_MAX_CIN) in LDS first (off: see above).
 // (bx,by,bz) = the workgroup's grid coordinates (blockIdx of the plain launch; decoded from a flat index by the
 // level-batched launch); smem: CONV_SMEM_FLOATS floats (SPLIT) / 8 floats.
-constexpr int WLDS_MAX_CIN = 64;
-constexpr int CONV_PART_FLOATS = 3 * COT * 64;
-constexpr int WLDS_FLOATS = SMVS_WLDS ? WLDS_MAX_CIN * 9 * COT : 0;
-constexpr int CONV_SMEM_FLOATS = CONV_PART_FLOATS + WLDS_FLOATS;
-// FUSE (stride 1): the B operand is the element-wise ConvGRU stage `fz` (mfma_conv.h: FuseB), computed by the workgroup
-// into `tile` (LDS, CB x CONV_FUSE_TH(SPLIT) x CONV_FUSE_TW floats) before the channel loop.
-constexpr int CONV_FUSE_TW = 66;
-constexpr int conv_fuse_th(bool split) { return split ? 3 : 6; }
-template <int STRIDE, bool SPLIT, bool FUSE = false>
-__device__ __forceinline__ void conv3x3_body(const ConvArgs& a, int bx, int by, int bz, float* smem, const FuseB* fz = nullptr, float* tile = nullptr)
+constexpr int CONV_SMEM_FLOATS = 3 * COT * 64;
+template <int STRIDE, bool SPLIT>
+__device__ __forceinline__ void conv3x3_body(const ConvArgs& a, int bx, int by, int bz, float* smem)
 {
-    static_assert(!FUSE || STRIDE == 1, "fused element-wise stages feed the stride-1 ConvGRU convolutions");
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ox = bx * 64 + lane;
     const int oy = SPLIT ? by : by * 4 + wave;
@@ -223,111 +204,67 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, int bx, int by, 
         ini[j] = (a.init && active && co < a.Cout && (!SPLIT || wave == 0))
                      ? a.init[(a.out_bstride ? (size_t)b * a.out_bstride + (size_t)co * a.Ho * a.Wo : ((size_t)b * a.Cout + co) * a.Ho * a.Wo) + (size_t)oy * a.Wo + ox] : 0.0f;
     }
-    const int CinW = a.CinW ? a.CinW : Cin;
-    const cw_t wbase = (cw_t)(uintptr_t)(a.w + ((size_t)cog * CinW + a.wc0) * 9 * COT);
-    const float* wl = smem + CONV_PART_FLOATS;
-    constexpr bool WL = SPLIT && SMVS_WLDS;
-    if (WL) {
-        const float* wg = a.w + ((size_t)cog * CinW + a.wc0) * 9 * COT;
-        float* wd = smem + CONV_PART_FLOATS;
-        for (int i = threadIdx.x * 4; i < Cin * 9 * COT; i += 256 * 4) *(float4*)(wd + i) = *(const float4*)(wg + i);
-        __syncthreads();
-    }
+    const cw_t wbase = (cw_t)(uintptr_t)(a.w + (size_t)cog * Cin * 9 * COT);
 
     const int per = SPLIT ? (Cin + 3) / 4 : Cin;
     const int c0 = SPLIT ? wave * per : 0, c1 = SPLIT ? min(Cin, c0 + per) : Cin;
-    constexpr int FTH = conv_fuse_th(SPLIT);
-    if constexpr (FUSE) {
-        fuse_fill_tile<4, 8, FTH, CONV_FUSE_TW>(*fz, b, a.Hi, a.Wi, (SPLIT ? by : by * 4) - 1, bx * 64 - 1, tile, wave, cog == 0);
-        if (fz->zero && bx == 0 && by == 0 && bz == 0)
-            for (int i = threadIdx.x; i < fz->zero_n; i += 256) fz->zero[i] = 0.0;
-        __syncthreads();
-    }
     // NPF-1 channels of taps are in flight while one is multiplied.
-    constexpr int NPF = SMVS_CONV_PREFETCH;
+    constexpr int NPF = CONV_PREFETCH;
     struct Taps { mf32x3 r[ROWS ? 3 : 1]; float t[ROWS ? 1 : 9]; };   // one of the two is used (compile-time)
     Taps v[NPF];
-    // taps of input channel cc: from memory (A half; B half when not fused) or from the LDS tile (fused B half)
-    auto load = [&](Taps& V, int cc, auto lds_tag) {
-        constexpr bool LDS = decltype(lds_tag)::value;
-        if constexpr (LDS) {
-            const float* tc = tile + (size_t)(cc - a.CA) * (FTH * CONV_FUSE_TW) + (SPLIT ? 0 : wave) * CONV_FUSE_TW + lane;
-            if (ROWS) {
+    // taps of input channel cc (A half or B half)
+    auto load = [&](Taps& V, int cc) {
+        const bool fa = cc < a.CA;                                     // wave-uniform: scalar selects
+        i32x4 rx;
+        rx.x = fa ? rA.v.x : rB.v.x; rx.y = fa ? rA.v.y : rB.v.y;
+        rx.z = fa ? rA.v.z : rB.v.z; rx.w = rA.v.w;
+        const int co = fa ? cc * csA * 4 : (cc - a.CA) * HWi * 4;
+        if (ROWS) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { V.r[k].x = tc[k * CONV_FUSE_TW]; V.r[k].y = tc[k * CONV_FUSE_TW + 1]; V.r[k].z = tc[k * CONV_FUSE_TW + 2]; }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) V.t[k] = tc[(k / 3) * CONV_FUSE_TW + k % 3];
-            }
+            for (int k = 0; k < 3; ++k) V.r[k] = llvm_raw_buffer_load_v3f32(rx, (int)roff[k], co, 0);
         } else {
-            const bool fa = cc < a.CA;                                 // wave-uniform: scalar selects
-            i32x4 rx;
-            rx.x = fa ? rA.v.x : rB.v.x; rx.y = fa ? rA.v.y : rB.v.y;
-            rx.z = fa ? rA.v.z : rB.v.z; rx.w = rA.v.w;
-            const int co = fa ? cc * csA * 4 : (cc - a.CA) * HWi * 4;
-            if (ROWS) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) V.r[k] = llvm_raw_buffer_load_v3f32(rx, (int)roff[k], co, 0);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) V.t[k] = llvm_raw_buffer_load_f32(rx, (int)off[k], co, 0);
-            }
+            for (int k = 0; k < 9; ++k) V.t[k] = llvm_raw_buffer_load_f32(rx, (int)off[k], co, 0);
         }
     };
-    auto fma = [&](const Taps& V, int cc, auto lds_tag) {
-        constexpr bool LDS = decltype(lds_tag)::value;
+    auto fma = [&](const Taps& V, int cc) {
         float t[9];
         const float sc = cc < a.CA ? a.scaleA : 1.0f;
         if (ROWS) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 float l0 = V.r[k].x, l1 = V.r[k].y, l2 = V.r[k].z;
-                if (!LDS && anypad) { l2 = padR ? 0.0f : (padL ? l1 : l2); l1 = padL ? l0 : l1; l0 = padL ? 0.0f : l0; }   // (the LDS tile carries its zero padding)
+                if (anypad) { l2 = padR ? 0.0f : (padL ? l1 : l2); l1 = padL ? l0 : l1; l0 = padL ? 0.0f : l0; }
                 t[3 * k] = l0 * sc; t[3 * k + 1] = l1 * sc; t[3 * k + 2] = l2 * sc;
             }
         } else {
 #pragma unroll
             for (int k = 0; k < 9; ++k) t[k] = V.t[k] * sc;
         }
-        if (WL) {
-            const float* wc = wl + cc * 9 * COT;
+        const cw_t wc = wbase + (size_t)cc * 9 * COT;
 #pragma unroll
-            for (int k = 0; k < 9; ++k)
+        for (int k = 0; k < 9; ++k)
 #pragma unroll
-                for (int j = 0; j < COT; ++j) acc[j] = fmaf(t[k], wc[k * COT + j], acc[j]);
-        } else {
-            const cw_t wc = wbase + (size_t)cc * 9 * COT;
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int j = 0; j < COT; ++j) acc[j] = fmaf(t[k], wc[k * COT + j], acc[j]);
-        }
+            for (int j = 0; j < COT; ++j) acc[j] = fmaf(t[k], wc[k * COT + j], acc[j]);
     };
     // The loads are UNCONDITIONAL (past the end: the last channel again, unused) -- a load under a branch makes the
     // compiler wait with vmcnt(0) before every multiply block, and the prefetch hides nothing (mfma_conv.h).
-    // Channels [lo, hi) of this wave in order (the accumulation order is the unfused kernel's).
-    auto run = [&](int lo, int hi, auto lds_tag) {
-        const int cl = max(hi - 1, lo);
+    // Channels [c0, c1) of this wave in order.
+    {
+        const int cl = max(c1 - 1, c0);
 #pragma unroll
-        for (int i = 0; i < NPF - 1; ++i) load(v[i], min(lo + i, cl), lds_tag);
-        for (int cc = lo; cc < hi; cc += NPF) {
+        for (int i = 0; i < NPF - 1; ++i) load(v[i], min(c0 + i, cl));
+        for (int cc = c0; cc < c1; cc += NPF) {
 #pragma unroll
             for (int i = 0; i < NPF; ++i) {
-                load(v[(i + NPF - 1) % NPF], min(cc + i + NPF - 1, cl), lds_tag);
+                load(v[(i + NPF - 1) % NPF], min(cc + i + NPF - 1, cl));
                 __builtin_amdgcn_sched_barrier(0);
-                if (cc + i < hi) fma(v[i], cc + i, lds_tag);
+                if (cc + i < c1) fma(v[i], cc + i);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-    };
-    if constexpr (FUSE) {
-        if (c0 < min(c1, a.CA)) run(c0, min(c1, a.CA), std::false_type());
-        if (max(c0, a.CA) < c1) run(max(c0, a.CA), c1, std::true_type());
-    } else {
-        run(c0, c1, std::false_type());
     }
 
-    if (FUSE) __syncthreads();                // the B tile shares its LDS with the scratch below: every wave is out of its channel loop
     if (SPLIT) {
         float (*part)[COT][64] = (float (*)[COT][64])smem;
         if (wave > 0) {
@@ -417,8 +354,7 @@ __device__ __forceinline__ void conv3x3_rows_body(const ConvArgs& a, int bx, int
             ini[r][j] = (a.init && colok && oy0 + r < a.Ho && co < a.Cout)
                             ? a.init[(a.out_bstride ? (size_t)b * a.out_bstride + (size_t)co * HWo : ((size_t)b * a.Cout + co) * HWo) + (size_t)(oy0 + r) * a.Wo + ox] : 0.0f;
         }
-    const int CinW = a.CinW ? a.CinW : Cin;
-    const cw_t wbase = (cw_t)(uintptr_t)(a.w + ((size_t)cog * CinW + a.wc0) * 9 * COT);
+    const cw_t wbase = (cw_t)(uintptr_t)(a.w + (size_t)cog * Cin * 9 * COT);
     constexpr int NPF = 2;
     struct Taps { float t[NT]; };
     Taps v[NPF];
@@ -536,26 +472,14 @@ void convT3x3s2_kernel(const ConvArgs a)
 #pragma unroll
         for (int j = 0; j < COT; ++j) acc[q][j] = 0.0f;
     const cw_t wbase = (cw_t)(uintptr_t)(a.w + (size_t)cog * a.CA * 9 * COT);
-    __shared__ __attribute__((aligned(16))) float ct_smem[SPLIT ? 3 * 4 * COT * 64 + WLDS_FLOATS : 4];
-    const float* wl = ct_smem + 3 * 4 * COT * 64;
-    constexpr bool WL = SPLIT && SMVS_WLDS;
-    if (WL) {                                    // weights of this cout group through LDS (see conv3x3_body)
-        const float* wg = a.w + (size_t)cog * a.CA * 9 * COT;
-        float* wd = ct_smem + 3 * 4 * COT * 64;
-        for (int i = threadIdx.x * 4; i < a.CA * 9 * COT; i += 256 * 4) *(float4*)(wd + i) = *(const float4*)(wg + i);
-        __syncthreads();
-    }
+    __shared__ __attribute__((aligned(16))) float ct_smem[SPLIT ? 3 * 4 * COT * 64 : 4];
     const int per = SPLIT ? (a.CA + 3) / 4 : a.CA;
     const int c0 = SPLIT ? wave * per : 0, c1 = SPLIT ? min(a.CA, c0 + per) : a.CA;
 #define SMVS_CT_LOAD(V, CC) \
     { _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) V[k_] = llvm_raw_buffer_load_f32(rA.v, (int)off[k_], (CC) * HWi * 4, 0); }
 #define SMVS_CT_FMA(V, CC)                                                                             \
     {                                                                                                  \
-        if (WL) { const float* wc = wl + (CC) * 9 * COT; SMVS_CT_FMA_BODY(V, wc) }                     \
-        else { const cw_t wc = wbase + (size_t)(CC) * 9 * COT; SMVS_CT_FMA_BODY(V, wc) }               \
-    }
-#define SMVS_CT_FMA_BODY(V, wc)                                                                        \
-    {                                                                                                  \
+        const cw_t wc = wbase + (size_t)(CC) * 9 * COT;                                                \
         _Pragma("unroll") for (int j = 0; j < COT; ++j) {                                              \
             acc[0][j] = fmaf(V[0], wc[4 * COT + j], acc[0][j]);                                        \
             acc[1][j] = fmaf(V[0], wc[5 * COT + j], fmaf(V[1], wc[3 * COT + j], acc[1][j]));           \
@@ -565,7 +489,7 @@ void convT3x3s2_kernel(const ConvArgs a)
         }                                                                                              \
     }
     // NPF-1 channels of taps in flight ahead of the multiply (4 loads per channel only)
-    constexpr int NPF = SMVS_CONVT_PREFETCH;
+    constexpr int NPF = CONVT_PREFETCH;
     float v[NPF][4];
     const int cl = max(c1 - 1, 0);               // unconditional loads (see conv3x3_body)
 #pragma unroll
@@ -581,7 +505,6 @@ void convT3x3s2_kernel(const ConvArgs a)
     }
 #undef SMVS_CT_LOAD
 #undef SMVS_CT_FMA
-#undef SMVS_CT_FMA_BODY
     if (SPLIT) {
         float (*part)[4 * COT][64] = (float (*)[4 * COT][64])ct_smem;
         if (wave > 0) {
@@ -736,14 +659,10 @@ __device__ __forceinline__ void gn_coeffs2(const double* st0, const double* st1,
     m0 = lds2[0][0]; r0 = lds2[0][1]; m1 = lds2[1][0]; r1 = lds2[1][1];
 }
 
-// Gate activations of the shipped element-wise kernels: expf / tanhf and a true division (the fast forms of the fused
-// tuning-build launches, mfma_conv.h -- rcp + __expf, tanh as 1 - 2 / (1 + e^2x) -- lose bits in every one of up to 384 recurrent steps
-// and bought nothing on these memory-bound kernels).  SMVS_RED_FAST_ACT=1 (profiling builds) keeps the fast forms.
-#ifndef SMVS_RED_FAST_ACT
-#define SMVS_RED_FAST_ACT 0
-#endif
-__device__ __forceinline__ float sigmoidf_(float x) { return SMVS_RED_FAST_ACT ? fuse_sigmoid(x) : 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return SMVS_RED_FAST_ACT ? fuse_tanh(x) : tanhf(x); }
+// Gate activations of the element-wise kernels: expf / tanhf and a true division (the fast forms -- rcp + __expf, tanh
+// as 1 - 2 / (1 + e^2x) -- lose bits in every one of up to 384 recurrent steps and bought nothing on these memory-bound kernels).
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float tanhf_(float x) { return tanhf(x); }
 
 // ---- level-batched launches ------------------------------------------------------------------------------------------
 // The four ConvGRU levels of a plane do not depend on each other (only the decoder crosses levels), and each of
@@ -752,9 +671,8 @@ __device__ __forceinline__ float tanhf_(float x) { return SMVS_RED_FAST_ACT ? fu
 // Per plane: gate convolutions, gate apply, candidate convolutions, combine = 4 launches instead of 16, and the
 // levels run side by side without streams or events.
 struct ConvJob {
-    ConvArgs a; MfmaConvArgs m;              // kind 0/1: a (direct, unsplit / channel-split); kind 2: m (MFMA, one cout tile per workgroup)
+    ConvArgs a; MfmaConvArgs m;              // kind 0/1/6: a (direct, unsplit / channel-split / 4 rows per lane); kind 2-4: m (MFMA)
     int kind, gx, gy, blk0;                  // grid (gx, gy, rest) flattened; workgroups [blk0, next job's blk0)
-    FuseB fuse;                              // fused launches: the element-wise stage this convolution computes for its B operand (direct kinds; MFMA kinds: m.fuse)
 };
 struct ConvJobs { ConvJob j[4]; int n; };
 
@@ -776,37 +694,7 @@ void conv_jobs_kernel(const ConvJobs J)
     else if (jb.kind == 2) mfma_conv_body<9, 1, 4>(jb.m, bx, t, smem);
     else if (jb.kind == 1) conv3x3_body<1, true>(jb.a, bx, t % jb.gy, t / jb.gy, smem);
     else if (jb.kind == 6) conv3x3_rows_body<4>(jb.a, bx, t % jb.gy, t / jb.gy, smem);
-    else if (jb.kind == 5) conv3x3_rows_body<2>(jb.a, bx, t % jb.gy, t / jb.gy, smem);
     else conv3x3_body<1, false>(jb.a, bx, t % jb.gy, t / jb.gy, smem);
-}
-
-// Fused launches (conv_jobs_fused_kernel): the convolution computes the element-wise ConvGRU stage that feeds its B operand
-// into LDS first (mfma_conv.h: FuseB) -- 2 dependent launches per plane instead of 4.  LDS: the job bodies' own scratch +
-// the largest B tile (MFMA, 64 channels x 3 x 34; direct 16 x 3 x 66 / 8 x 6 x 66).
-constexpr int FUSE_TILE_FLOATS = 64 * MFMA_FUSE_TH * MFMA_FUSE_TW;
-__host__ __device__ inline int fuse_tile_floats(int kind, int CB)
-{
-    return kind == 0 ? CB * conv_fuse_th(false) * CONV_FUSE_TW : kind == 1 ? CB * conv_fuse_th(true) * CONV_FUSE_TW
-         : (kind == 3 ? 2 : 1) * CB * MFMA_FUSE_TH * MFMA_FUSE_TW;
-}
-
-__global__ __launch_bounds__(256)
-void conv_jobs_fused_kernel(const ConvJobs J)
-{
-    // one allocation: the B tile is dead when the bodies' scratch (split-K partials, statistics) comes into use
-    __shared__ __attribute__((aligned(16))) float smem[JOBS_SMEM_FLOATS > FUSE_TILE_FLOATS ? JOBS_SMEM_FLOATS : FUSE_TILE_FLOATS];
-    float* tile = smem;
-    int bid = blockIdx.x, l = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (i < J.n && bid >= J.j[i].blk0) l = i;
-    const ConvJob& jb = J.j[l];
-    bid -= jb.blk0;
-    const int bx = bid % jb.gx, t = bid / jb.gx;
-    if (jb.kind == 3) mfma_conv_body<9, 1, 4, 2, true>(jb.m, bid, 0, smem, tile);
-    else if (jb.kind == 2) mfma_conv_body<9, 1, 4, 4, true>(jb.m, bx, t, smem, tile);
-    else if (jb.kind == 1) conv3x3_body<1, true, true>(jb.a, bx, t % jb.gy, t / jb.gy, smem, &jb.fuse, tile);
-    else conv3x3_body<1, false, true>(jb.a, bx, t % jb.gy, t / jb.gy, smem, &jb.fuse, tile);
 }
 
 struct GruJob {                              // the element-wise stages of one level
@@ -927,9 +815,8 @@ void gru_combine_kernel(const GruJobs J)
 constexpr int CH_MAX = 8, NSL_MAX = 2 * CH_MAX;
 static int red_chunk(int B, int C, int H, int W)
 {
-    int ch = (size_t)B * H * W <= (size_t)tune_int("SMVS_RED_CHUNK8_BELOW", 131072) ? 8 : 4;   // small planes: the host's enqueue rate binds
-    const int force = tune_int("SMVS_RED_CHUNK", 0);
-    if (force == 1 || force == 2 || force == 4 || force == 8) ch = force;
+    constexpr size_t CHUNK8_BELOW = 131072;
+    int ch = (size_t)B * H * W <= CHUNK8_BELOW ? 8 : 4;                                        // small planes: the host's enqueue rate binds
     while (ch > 1 && (long long)C * ch * H * W * 4 >= (1ll << 30)) ch >>= 1;                // chunk addressed with 32-bit byte offsets
     return ch;
 }
@@ -942,10 +829,6 @@ struct RedWorkspace {                        // offsets in floats into the calle
     size_t e[3], e_stride[3], gates[4], rh[4], cand[4], hsnap[4], hsnap_stride[4], sum[3], stats[2];   // stats: doubles, offset in floats (8-byte aligned)
     // hsnap[g] + slot * hsnap_stride[g]: like e, the slots of a chunk are adjacent = one dense batch of CH*B samples for the
     // decoder, which runs once per CHUNK of planes (planes = batch dimension); sum[] holds a chunk.
-    size_t gates2[4], halt[4];               // fused plane loop: the gate convolution's second buffer, the state's second buffer
-    // xg / xc [g] + slot * stride: the state-INDEPENDENT half of the gate / candidate convolutions of a plane (input channels of
-    // the encoder level, bias included), computed by the front for a chunk of planes; the recurrent chain continues them.
-    size_t xg[4], xg_stride[4], xc[4], xc_stride[4];
     size_t total;
 };
 
@@ -973,47 +856,16 @@ static RedWorkspace red_workspace(int B, int C, int H, int W)
         w.sum[i] = take((size_t)w.CH * B * HID[i] * hs[i] * ws[i]);
     for (int p = 0; p < 2; ++p)
         w.stats[p] = take((size_t)B * 4 * 3 * NSLOT * 2 * 2);   // 4 GRUs x (reset, update, output) x NSLOT x (sum, sumsq) doubles
-    for (int i = 0; i < 4; ++i) {
-        w.gates2[i] = take((size_t)B * 2 * HID[i] * hs[i] * ws[i]);
-        w.halt[i] = take((size_t)B * HID[i] * hs[i] * ws[i]);
-    }
-    for (int i = 0; i < 4; ++i) {
-        w.xg_stride[i] = (size_t)B * 2 * HID[i] * hs[i] * ws[i];
-        w.xg[i] = take(w.xg_stride[i] * w.NSL);
-        w.xc_stride[i] = (size_t)B * HID[i] * hs[i] * ws[i];
-        w.xc[i] = take(w.xc_stride[i] * w.NSL);
-    }
     w.total = o;
     return w;
 }
 
-static bool g_red_direct_only()
-{
-    return tune_int("SMVS_CONV_DIRECT", 0) == 1;            // A/B switch (tuning builds): direct kernels only
-}
-
-#ifndef SMVS_MFMA_UNIT_WAVES
-#define SMVS_MFMA_UNIT_WAVES 1               // level-batched RED launches: unit-per-wave MFMA jobs in the throughput regime (0: round 2, A/B)
-#endif
-static int g_mfma_units(int which)
-{
-    static const int v1 = tune_int("SMVS_MFMA_UNITS_KS1", 1024), v2 = tune_int("SMVS_MFMA_UNITS_KS2", 512);
-    return which == 0 ? v1 : v2;                            // (tile, cout tile) units of a layer from which its MFMA job runs one / two waves per unit
-}
-
-static int g_split_below()
-{
-    static const int v = tune_int("SMVS_CONV_SPLIT_BELOW", 512);
-    return v;                                               // workgroups (unsplit) below which the channel-split kernels run
-                                                            // (1024 -> 512: the 384x192 level-1 gate convolution, 576 workgroups, is
-                                                            //  24 -> ~16 us unsplit; stage 2 of the cascade 3.13 -> 3.01 ms)
-}
-
-static int g_rows_from()
-{
-    static const int v = tune_int("SMVS_CONV_ROWS4_FROM", 1024);
-    return v;                                               // workgroups (nine-tap kernel, one sample) from which a lane computes 4 output rows
-}
+// (tile, cout tile) units of a layer from which its MFMA job of a level-batched launch runs one / two waves per unit
+constexpr int MFMA_UNITS_KS1 = 1024, MFMA_UNITS_KS2 = 512;
+// workgroups (unsplit) below which the channel-split kernels run (1024 -> 512: the 384x192 level-1 gate convolution, 576 workgroups,
+// is 24 -> ~16 us unsplit; stage 2 of the cascade 3.13 -> 3.01 ms)
+constexpr int SPLIT_BELOW = 512;
+constexpr int ROWS4_FROM = 1024;             // workgroups (nine-tap kernel, one sample) from which a lane computes 4 output rows
 
 static MfmaConvArgs mfma_args(int stride, const ConvArgs& a, const float* wm)
 {
@@ -1022,7 +874,7 @@ static MfmaConvArgs mfma_args(int stride, const ConvArgs& a, const float* wm)
     m.out = a.out; m.stats = a.stats; m.ngroups = a.ngroups; m.nslot = NSLOT;
     m.Cout = a.Cout; m.relu = a.relu; m.stride = stride;
     m.Di = m.Do = 1; m.Hi = a.Hi; m.Wi = a.Wi; m.Ho = a.Ho; m.Wo = a.Wo;
-    m.init = a.init; m.wcip0 = a.wc0 / 2; m.wcipN = a.CinW / 2;
+    m.init = a.init;
     return m;
 }
 
@@ -1032,20 +884,20 @@ static MfmaConvArgs mfma_args(int stride, const ConvArgs& a, const float* wm)
 static void launch_conv(int stride, const ConvArgs& a, int B, hipStream_t st, const float* wm = nullptr, int Bh = 0)
 {
     if (Bh <= 0) Bh = B;
-    if (wm && !a.inA_cs && mfma_conv_ok(a.CA, a.CB, a.Cout) && !g_red_direct_only()) {
+    if (wm && !a.inA_cs && mfma_conv_ok(a.CA, a.CB, a.Cout)) {
         mfma_conv_launch<9>(mfma_args(stride, a, wm), B, st, Bh);
         return;
     }
     const int ncog = (a.Cout + COT - 1) / COT;
     const int wx = (a.Wo + 63) / 64;
-    if (wx * ((a.Ho + 3) / 4) * Bh * ncog < g_split_below() && (!SMVS_WLDS || a.CA + a.CB <= WLDS_MAX_CIN)) {   // coarse plane: latency regime
+    if (wx * ((a.Ho + 3) / 4) * Bh * ncog < SPLIT_BELOW) {         // coarse plane: latency regime
         dim3 grd(wx, a.Ho, B * ncog), blk(256);
         if (stride == 1) hipLaunchKernelGGL((conv3x3_kernel<1, true>), grd, blk, 0, st, a);
         else             hipLaunchKernelGGL((conv3x3_kernel<2, true>), grd, blk, 0, st, a);
         return;
     }
     dim3 grd(wx, (a.Ho + 3) / 4, B * ncog), blk(256);
-    if (stride == 1 && wx * ((a.Ho + 3) / 4) * ncog >= g_rows_from())          // throughput regime (one sample's geometry): 4 output rows per lane
+    if (stride == 1 && wx * ((a.Ho + 3) / 4) * ncog >= ROWS4_FROM)          // throughput regime (one sample's geometry): 4 output rows per lane
         hipLaunchKernelGGL((conv3x3_rows_kernel<4>), dim3(wx, (a.Ho + 15) / 16, B * ncog), blk, 0, st, a);
     else if (stride == 1) hipLaunchKernelGGL((conv3x3_kernel<1, false>), grd, blk, 0, st, a);
     else             hipLaunchKernelGGL((conv3x3_kernel<2, false>), grd, blk, 0, st, a);
@@ -1056,7 +908,7 @@ static int conv_job(ConvJob& j, const ConvArgs& a, int B, const float* wm, int b
 {
     if (Bh <= 0) Bh = B;                      // the batch the kernel VARIANT is chosen for (see launch_conv)
     j.blk0 = blk0;
-    if (wm && !a.inA_cs && mfma_conv_ok(a.CA, a.CB, a.Cout) && !g_red_direct_only()) {
+    if (wm && !a.inA_cs && mfma_conv_ok(a.CA, a.CB, a.Cout)) {
         j.kind = 2; j.m = mfma_args(1, a, wm);
         j.gx = ((a.Wo + 31) / 32) * a.Ho * B; j.gy = a.Cout / 32;
         j.m.ntiles = j.gx;
@@ -1064,21 +916,19 @@ static int conv_job(ConvJob& j, const ConvArgs& a, int B, const float* wm, int b
         // per workgroup, so that a wave's K loop is long enough to stream (mfma_conv.h).  Chosen from the geometry of ONE
         // sample: a plane's bits do not depend on batch, chunking or sharding.
         const int units1 = ((a.Wo + 31) / 32) * a.Ho * j.gy;
-        if (SMVS_MFMA_UNIT_WAVES && units1 >= g_mfma_units(0)) { j.kind = 4; j.gx = (j.gx * j.gy + 3) / 4; return j.gx; }
-        if (SMVS_MFMA_UNIT_WAVES && units1 >= g_mfma_units(1)) { j.kind = 3; j.gx = (j.gx * j.gy + 1) / 2; return j.gx; }
+        if (units1 >= MFMA_UNITS_KS1) { j.kind = 4; j.gx = (j.gx * j.gy + 3) / 4; return j.gx; }
+        if (units1 >= MFMA_UNITS_KS2) { j.kind = 3; j.gx = (j.gx * j.gy + 1) / 2; return j.gx; }
         return j.gx * j.gy;
     }
     j.a = a;
     const int ncog = (a.Cout + COT - 1) / COT;
     j.gx = (a.Wo + 63) / 64;
-    const bool split = j.gx * ((a.Ho + 3) / 4) * Bh * ncog < g_split_below() && (!SMVS_WLDS || a.CA + a.CB <= WLDS_MAX_CIN);
+    const bool split = j.gx * ((a.Ho + 3) / 4) * Bh * ncog < SPLIT_BELOW;
     j.kind = split ? 1 : 0;
     j.gy = split ? a.Ho : (a.Ho + 3) / 4;
-    // throughput regime (chosen from ONE sample's geometry): 4 / 2 output rows per lane
-    static const int rows2 = tune_int("SMVS_CONV_ROWS2_FROM", 1 << 30);      // (2 rows per lane: no gain measured at cascade stage 2; tuning builds)
+    // throughput regime (chosen from ONE sample's geometry): 4 output rows per lane
     const int wg1 = j.gx * ((a.Ho + 3) / 4) * ncog;
-    if (!split && wg1 >= g_rows_from()) { j.kind = 6; j.gy = (a.Ho + 15) / 16; }
-    else if (!split && wg1 >= rows2) { j.kind = 5; j.gy = (a.Ho + 7) / 8; }
+    if (!split && wg1 >= ROWS4_FROM) { j.kind = 6; j.gy = (a.Ho + 15) / 16; }
     return j.gx * j.gy * B * ncog;
 }
 
@@ -1088,7 +938,7 @@ static void launch_convT(const ConvArgs& a, int B, hipStream_t st, int Bh = 0)
     if (Bh <= 0) Bh = B;
     const int ncog = (a.Cout + COT - 1) / COT;
     const int wx = (a.Wi + 63) / 64;
-    if (wx * ((a.Hi + 3) / 4) * Bh * ncog < g_split_below()) {
+    if (wx * ((a.Hi + 3) / 4) * Bh * ncog < SPLIT_BELOW) {
         hipLaunchKernelGGL(convT3x3s2_kernel<true>, dim3(wx, a.Hi, B * ncog), dim3(256), 0, st, a);
         return;
     }
@@ -1121,9 +971,8 @@ static RedPipe* red_pipe_create()
     // ahead of the front's and the decoder's wherever they compete for CUs
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    const int pr = tune_int("SMVS_RED_PRIO", 1);
-    bool ok = (pr ? hipStreamCreateWithPriority(&p->rec, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&p->rec, hipStreamNonBlocking)) == hipSuccess
-           && (pr == 2 ? hipStreamCreateWithPriority(&p->dec, hipStreamNonBlocking, lo) : hipStreamCreateWithFlags(&p->dec, hipStreamNonBlocking)) == hipSuccess;
+    bool ok = hipStreamCreateWithPriority(&p->rec, hipStreamNonBlocking, hi) == hipSuccess
+           && hipStreamCreateWithFlags(&p->dec, hipStreamNonBlocking) == hipSuccess;
     for (int r = 0; r < RING && ok; ++r)
         ok = hipEventCreateWithFlags(&p->enc[r], hipEventDisableTiming) == hipSuccess
           && hipEventCreateWithFlags(&p->state[r], hipEventDisableTiming) == hipSuccess
@@ -1203,31 +1052,10 @@ struct RedIssuer {
         sD = multi ? P.dec : r.main;
         for (int g = 0; g < 4; ++g) { hs[g] = r.H >> g; wd[g] = r.W >> g; }
     }
-    // Fused plane loop (2 dependent launches per plane, the element-wise stages computed by the consuming convolutions into
-    // LDS: mfma_conv.h, FuseB).  Built and measured in round 4 -- correct (every RED test passes with it on) and SLOWER:
-    // 80 / 152 us per plane at cascade stages 1 / 2 against 62 / 95 for the four-launch chain (profiles/r04_red_fusion.txt).
-    // The premise was wrong: the two element-wise launches cost 5-8 us of kernel + ~3 us of gap each, not 13 us; computing
-    // their stage per tile (3-12x redundantly: halos, one tile per output-channel group) inside the latency chain of the
-    // convolutions costs 10-33 us per launch, and what bounded the plane was the decoder chain on the other stream.  Kept
-    // for tuning builds (SMVS_RED_FUSED=1); the shipped library never takes this path.
-    bool fused() const { return tune_int("SMVS_RED_FUSED", 0) == 1; }
-    float* state_buf(int g, int k) const { return (k & 1) ? r.wsf + ws.halt[g] : r.state[g]; }     // state entering plane k of this call
-    float* gates_buf(int g, int k) const { return r.wsf + ((k & 1) ? ws.gates2[g] : ws.gates[g]); }
     int CH() const { return ws.CH; }
     double* stats_of(int k) const { return (double*)(r.wsf + ws.stats[k & 1]); }
     float* e_of(int k, int i) const { return r.wsf + ws.e[i] + (size_t)(k % ws.NSL) * ws.e_stride[i]; }
     float* hsnap_of(int k, int g) const { return r.wsf + ws.hsnap[g] + (size_t)(k % ws.NSL) * ws.hsnap_stride[g]; }
-    float* xg_of(int k, int g) const { return r.wsf + ws.xg[g] + (size_t)(k % ws.NSL) * ws.xg_stride[g]; }
-    float* xc_of(int k, int g) const { return r.wsf + ws.xc[g] + (size_t)(k % ws.NSL) * ws.xc_stride[g]; }
-    // The ConvGRU convolutions act on cat(x, h) / cat(x, r*h): their x half does not depend on the recurrent state.  With the
-    // split on, the front computes it (+ bias) for a whole chunk of planes (planes = batch, caller's stream, under the previous
-    // chunk's chain) and the chain's two convolutions per plane walk the hidden channels only (8 of 40 input channels at level 1
-    // of cascade stage 1, half of them at the coarser levels), starting from those sums.  Built and measured in round 4 (every
-    // RED test passes with it on; profiles/r04_red_xsplit.txt): the chain's convolutions get 18.3 -> 13.0 / 15.4 -> 11.8 us
-    // shorter at stage 1, but a convolution over half the channels costs well over half the time (tile set-up, epilogue, the extra
-    // store + load of the partial sums) and the x halves compete with the chain for the CUs: 57 -> 54 us per plane at stage 1,
-    // 98 -> 100 at stage 2, 262 -> 288 at stage 3.  Off; tuning builds: SMVS_RED_XSPLIT=1.
-    bool xsplit() const { return !fused() && tune_int("SMVS_RED_XSPLIT", 0) == 1; }
     // Per-level chains (one stream per ConvGRU level, every level walking its own 4 launches per plane, no event between levels):
     // built and measured in round 6, REJECTED -- 175 / 198 / 377 us per plane at cascade stages 1 / 2 / 3 against 55 / 92 / 226 for
     // the level-batched chain, 19.2-20.2 ms per cascade forward against 7.6-7.7 (profiles/r06_red_per_level.txt).  Six concurrent
@@ -1270,29 +1098,6 @@ struct RedIssuer {
             a.Hi = hs[i]; a.Wi = wd[i]; a.Ho = hs[i + 1]; a.Wo = wd[i + 1]; a.relu = 1;
             launch_conv(2, a, n * B, r.main, r.packed + L.conv_wm[i], r.pred ? ch * B : B);
         }
-        if (xsplit()) {
-            ConvJobs jg{}, jc{};
-            jg.n = jc.n = 4;
-            int nbg = 0, nbc = 0;
-            const int Bh = r.pred ? ch * B : B;
-            for (int q = 0; q < 4; ++q) {
-                const int g = 3 - q, hc = HID[g];
-                const int cx = g == 0 ? C : enc_out[g - 1];
-                for (int pass = 0; pass < 2; ++pass) {
-                    ConvArgs a{};
-                    if (g == 0) { cost_view(k0, a); if (r.pred) { a.inA_ps = (size_t)r.H * r.W; a.inA_bmod = B; } }
-                    else a.inA = e_of(k0, g - 1);
-                    a.CA = cx; a.scaleA = g == 0 ? -1.0f : 1.0f; a.CinW = cx + hc;
-                    a.w = r.packed + (pass ? L.out_w[g] : L.gate_w[g]); a.bias = r.packed + (pass ? L.out_b[g] : L.gate_b[g]);
-                    a.out = pass ? xc_of(k0, g) : xg_of(k0, g);
-                    a.Cout = pass ? hc : 2 * hc; a.Hi = a.Ho = hs[g]; a.Wi = a.Wo = wd[g];
-                    if (pass) nbc += conv_job(jc.j[q], a, n * B, r.packed + L.out_wm[g], nbc, Bh);
-                    else      nbg += conv_job(jg.j[q], a, n * B, r.packed + L.gate_wm[g], nbg, Bh);
-                }
-            }
-            hipLaunchKernelGGL(conv_jobs_kernel, dim3(nbg), dim3(256), 0, r.main, jg);
-            hipLaunchKernelGGL(conv_jobs_kernel, dim3(nbc), dim3(256), 0, r.main, jc);
-        }
         if (multi) (void)hipEventRecord(P.enc[k0 % RING], r.main);
         return SMVS_OK;
     }
@@ -1319,22 +1124,15 @@ struct RedIssuer {
             const float sx = g == 0 ? -1.0f : 1.0f;
             double* sg = stats + (size_t)g * B * 3 * NSLOT * 2;           // [b][reset,update][slot][2], then [b][slot][2] for the output norm
             double* so = sg + (size_t)B * 2 * NSLOT * 2;
-            const bool xs = xsplit();
             ConvArgs a{};
-            if (xs) { a.inA = r.state[g]; a.CA = hc; a.scaleA = 1.0f; a.wc0 = cx; a.CinW = cx + hc; a.init = xg_of(k, g); }
-            else {
-                if (g == 0) cost_view(k, a); else a.inA = e_of(k, g - 1);
-                a.CA = cx; a.scaleA = sx; a.inB = r.state[g]; a.CB = hc; a.bias = packed + L.gate_b[g];
-            }
+            if (g == 0) cost_view(k, a); else a.inA = e_of(k, g - 1);
+            a.CA = cx; a.scaleA = sx; a.inB = r.state[g]; a.CB = hc; a.bias = packed + L.gate_b[g];
             a.w = packed + L.gate_w[g]; a.out = wsf + ws.gates[g]; a.stats = sg; a.ngroups = 2;
             a.Cout = 2 * hc; a.Hi = a.Ho = hs[g]; a.Wi = a.Wo = wd[g];
             nb_gate += conv_job(gate.j[q], a, B, packed + L.gate_wm[g], nb_gate);
             ConvArgs o{};
-            if (xs) { o.inA = wsf + ws.rh[g]; o.CA = hc; o.scaleA = 1.0f; o.wc0 = cx; o.CinW = cx + hc; o.init = xc_of(k, g); }
-            else {
-                if (g == 0) cost_view(k, o); else o.inA = e_of(k, g - 1);
-                o.CA = cx; o.scaleA = sx; o.inB = wsf + ws.rh[g]; o.CB = hc; o.bias = packed + L.out_b[g];
-            }
+            if (g == 0) cost_view(k, o); else o.inA = e_of(k, g - 1);
+            o.CA = cx; o.scaleA = sx; o.inB = wsf + ws.rh[g]; o.CB = hc; o.bias = packed + L.out_b[g];
             o.w = packed + L.out_w[g]; o.out = wsf + ws.cand[g]; o.stats = so; o.ngroups = 1;
             o.Cout = hc; o.Hi = o.Ho = hs[g]; o.Wi = o.Wo = wd[g];
             nb_cand += conv_job(cand.j[q], o, B, packed + L.out_wm[g], nb_cand);
@@ -1344,138 +1142,17 @@ struct RedIssuer {
             u.on_w = packed + L.on_w[g]; u.on_b = packed + L.on_b[g];
             u.h = r.state[g]; u.h_out = r.state[g]; u.rh = wsf + ws.rh[g]; u.cand = wsf + ws.cand[g]; u.hsnap = hsnap_of(k, g);
             u.zero_next = stats_next ? stats_next + (size_t)g * B * 3 * NSLOT * 2 : nullptr;
-            u.vec = tune_int("SMVS_GRU_VEC", 1) == 1 && hw % 4 == 0 && ((uintptr_t)u.h | (uintptr_t)u.h_out | (uintptr_t)u.hsnap | (uintptr_t)u.gates | (uintptr_t)u.rh | (uintptr_t)u.cand) % 16 == 0;
+            u.vec = hw % 4 == 0 && ((uintptr_t)u.h | (uintptr_t)u.h_out | (uintptr_t)u.hsnap | (uintptr_t)u.gates | (uintptr_t)u.rh | (uintptr_t)u.cand) % 16 == 0;
             u.HC = hc; u.HW = hw; u.gx = (int)(((size_t)hc * hw / (u.vec ? 4 : 1) + 255) / 256); u.blk0 = nb_gru;
             nb_gru += u.gx * B;
         }
-        if (tune_int("SMVS_RED_SPLIT_JOBS", 0)) {                       // tuning builds: one launch per level, to time the jobs
-            for (int pass = 0; pass < 2; ++pass) {
-                const ConvJobs& all = pass ? cand : gate;
-                for (int q = 0; q < 4; ++q) {
-                    ConvJobs one{};
-                    one.n = 1; one.j[0] = all.j[q]; one.j[0].blk0 = 0;
-                    const int nb = (q < 3 ? all.j[q + 1].blk0 : (pass ? nb_cand : nb_gate)) - all.j[q].blk0;
-                    hipLaunchKernelGGL(conv_jobs_kernel, dim3(nb), dim3(256), 0, sR, one);
-                }
-                if (!pass) hipLaunchKernelGGL(gru_gate_apply_kernel, dim3(nb_gru), dim3(256), 0, sR, gru);
-            }
-        } else {
         hipLaunchKernelGGL(conv_jobs_kernel, dim3(nb_gate), dim3(256), 0, sR, gate);
         hipLaunchKernelGGL(gru_gate_apply_kernel, dim3(nb_gru), dim3(256), 0, sR, gru);
         hipLaunchKernelGGL(conv_jobs_kernel, dim3(nb_cand), dim3(256), 0, sR, cand);
-        }
         hipLaunchKernelGGL(gru_combine_kernel, dim3(nb_gru), dim3(256), 0, sR, gru);
         // the decoder runs per chunk: only the chunk's last plane signals it (an event per plane costs the chain ~1 us each)
         if (multi && ((k + 1) % ws.CH == 0 || d + 1 == d_end)) (void)hipEventRecord(P.state[k % RING], sR);
         return SMVS_OK;
-    }
-
-    // Fused chain of plane k: L_A = [combine of plane k-1 on load] + gate convolutions, L_B = [gate apply on load] + candidate
-    // convolutions.  The state entering plane k lives in state_buf(., k) (the caller's tensors for even k, the workspace for odd
-    // k): L_A(k) computes it from plane k-1's raw gates / candidates and stores it there (and into the decoder's snapshot of plane
-    // k-1); gate buffers alternate likewise (L_A(k) reads plane k-1's update gate while it writes plane k's gates).
-    // After the last plane issue_final_combine() produces the final state in the caller's tensors.
-    int issue_recurrent_fused(int k)
-    {
-        const int d = d_begin + k;
-        const int B = r.B, C = r.C;
-        float* wsf = r.wsf;
-        const float* packed = r.packed;
-        const int enc_out[3] = {16, 32, 64};
-        double* stats = stats_of(k);
-        double* stats_prev = stats_of(k + 1);                                 // ring of two: plane k-1's = plane k+1's
-        const bool has_next = d + 1 < d_end;
-        if (multi && k % ws.CH == 0) (void)hipStreamWaitEvent(sR, P.enc[k % RING], 0);
-        ConvJobs gate{}, cand{};
-        gate.n = cand.n = 4;
-        int nb_gate = 0, nb_cand = 0;
-        for (int q = 0; q < 4; ++q) {
-            const int g = 3 - q;
-            const int hc = HID[g];
-            const int cx = g == 0 ? C : enc_out[g - 1];
-            const float sx = g == 0 ? -1.0f : 1.0f;
-            const size_t lvl = (size_t)g * B * 3 * NSLOT * 2;
-            double* sg = stats + lvl;
-            double* so = sg + (size_t)B * 2 * NSLOT * 2;
-            FuseB fa{};                                                        // gate convolution: B = h(k) = combine of plane k-1
-            fa.HC = hc; fa.nslot = NSLOT;
-            if (k > 0) {
-                fa.mode = FUSE_COMBINE;
-                fa.gates = gates_buf(g, k - 1); fa.cand = wsf + ws.cand[g]; fa.h = state_buf(g, k - 1);
-                fa.h_out = state_buf(g, k); fa.hsnap = hsnap_of(k - 1, g);
-                fa.stats_g = stats_prev + lvl; fa.stats_o = stats_prev + lvl + (size_t)B * 2 * NSLOT * 2;
-                fa.gw = packed + L.un_w[g]; fa.gb = packed + L.un_b[g]; fa.ow = packed + L.on_w[g]; fa.ob = packed + L.on_b[g];
-            }
-            ConvArgs a{};
-            if (g == 0) cost_view(k, a); else a.inA = e_of(k, g - 1);
-            a.CA = cx; a.scaleA = sx; a.inB = state_buf(g, k); a.CB = hc;
-            a.w = packed + L.gate_w[g]; a.bias = packed + L.gate_b[g]; a.out = gates_buf(g, k); a.stats = sg; a.ngroups = 2;
-            a.Cout = 2 * hc; a.Hi = a.Ho = hs[g]; a.Wi = a.Wo = wd[g];
-            nb_gate += conv_job(gate.j[q], a, B, packed + L.gate_wm[g], nb_gate);
-            gate.j[q].fuse = fa; gate.j[q].m.fuse = fa;
-            FuseB fb{};                                                        // candidate convolution: B = r * h(k)
-            fb.mode = FUSE_APPLY; fb.HC = hc; fb.nslot = NSLOT;
-            fb.gates = gates_buf(g, k); fb.h = state_buf(g, k); fb.stats_g = sg;
-            fb.gw = packed + L.rn_w[g]; fb.gb = packed + L.rn_b[g];
-            // plane k+1's statistics (= plane k-1's buffer: its last reader, L_A(k), is behind us) are cleared by this launch
-            if (has_next && q == 0) { fb.zero = stats_prev; fb.zero_n = B * 4 * 3 * NSLOT * 2; }
-            ConvArgs o{};
-            if (g == 0) cost_view(k, o); else o.inA = e_of(k, g - 1);
-            o.CA = cx; o.scaleA = sx; o.inB = state_buf(g, k); o.CB = hc;
-            o.w = packed + L.out_w[g]; o.bias = packed + L.out_b[g]; o.out = wsf + ws.cand[g]; o.stats = so; o.ngroups = 1;
-            o.Cout = hc; o.Hi = o.Ho = hs[g]; o.Wi = o.Wo = wd[g];
-            nb_cand += conv_job(cand.j[q], o, B, packed + L.out_wm[g], nb_cand);
-            cand.j[q].fuse = fb; cand.j[q].m.fuse = fb;
-        }
-        if (k > 0) hipLaunchKernelGGL(conv_jobs_fused_kernel, dim3(nb_gate), dim3(256), 0, sR, gate);
-        else       hipLaunchKernelGGL(conv_jobs_kernel, dim3(nb_gate), dim3(256), 0, sR, gate);       // plane 0 of the call: the state is the caller's
-        if (multi && k > 0) (void)hipEventRecord(P.state[(k - 1) % RING], sR);                         // plane k-1's snapshots are complete
-        hipLaunchKernelGGL(conv_jobs_fused_kernel, dim3(nb_cand), dim3(256), 0, sR, cand);
-        return SMVS_OK;
-    }
-
-    // the combine stage of the call's last plane: final state into the caller's tensors, snapshots for its decoder
-    int issue_final_combine(int k)
-    {
-        const int B = r.B;
-        float* wsf = r.wsf;
-        const float* packed = r.packed;
-        double* stats = stats_of(k);
-        GruJobs gru{};
-        gru.n = 4; gru.B = B;
-        int nb = 0;
-        for (int q = 0; q < 4; ++q) {
-            const int g = 3 - q;
-            const int hc = HID[g], hw = hs[g] * wd[g];
-            GruJob& u = gru.j[q];
-            double* sg = stats + (size_t)g * B * 3 * NSLOT * 2;
-            u.gates = gates_buf(g, k); u.stats_g = sg; u.stats_o = sg + (size_t)B * 2 * NSLOT * 2;
-            u.un_w = packed + L.un_w[g]; u.un_b = packed + L.un_b[g]; u.on_w = packed + L.on_w[g]; u.on_b = packed + L.on_b[g];
-            u.h = state_buf(g, k); u.h_out = r.state[g]; u.cand = wsf + ws.cand[g]; u.hsnap = hsnap_of(k, g);
-            u.HC = hc; u.HW = hw; u.gx = (int)(((size_t)hc * hw + 255) / 256); u.blk0 = nb;
-            nb += u.gx * B;
-        }
-        hipLaunchKernelGGL(gru_combine_kernel, dim3(nb), dim3(256), 0, sR, gru);
-        if (multi) (void)hipEventRecord(P.state[k % RING], sR);
-        return SMVS_OK;
-    }
-
-    // can every job of the fused launches hold its B tile in the kernel's LDS?  (geometry only)
-    bool fused_fits() const
-    {
-        const int enc_out[3] = {16, 32, 64};
-        for (int g = 0; g < 4; ++g) {
-            const int hc = HID[g], cx = g == 0 ? r.C : enc_out[g - 1];
-            for (int pass = 0; pass < 2; ++pass) {
-                ConvArgs a{};
-                ConvJob j{};
-                a.CA = cx; a.CB = hc; a.Cout = pass ? hc : 2 * hc; a.Hi = a.Ho = hs[g]; a.Wi = a.Wo = wd[g];
-                static const float dummy = 0.0f;
-                (void)conv_job(j, a, r.B, &dummy, 0);
-                if (j.kind >= 4 || fuse_tile_floats(j.kind, hc) > FUSE_TILE_FLOATS) return false;
-            }
-        }
-        return true;
     }
 
     // Decoder of planes [k0, k0+n) (one chunk; k0 a multiple of CH) from their state snapshots, output convolution, regression
@@ -1524,10 +1201,9 @@ static int red_run_planes(const RedRun& r, int d_begin, int d_end)
     const int nplanes = d_end - d_begin;
     if (nplanes <= 0) return SMVS_OK;
     // one plane alone: the cross-stream hops cost more than they buy (measured) -> caller's stream only
-    const bool multi = nplanes > 1 && tune_int("SMVS_RED_STREAMS", 2) != 0 && g_red_streams.load(std::memory_order_relaxed) != 0;
+    const bool multi = nplanes > 1 && g_red_streams.load(std::memory_order_relaxed) != 0;
     RedIssuer is(r, *pp, multi, d_begin, d_end);
     const RedPipe& P = *pp;
-    const bool fused = is.fused() && is.fused_fits();
     if (r.pred && !r.reg_volume)
         if (int rc0 = resolve_heights(r.depth, r.depth_is_4d, r.gen, r.D, r.H, r.W, is.hmode, is.hg)) return rc0;
     // the first plane's statistics are cleared here; afterwards each level clears the next plane's buffer itself
@@ -1542,19 +1218,9 @@ static int red_run_planes(const RedRun& r, int d_begin, int d_end)
         // this half of the ring was last used by chunk j-2; its last plane leaving the decoder implies all of it
         if (multi && k0 >= 2 * ch) (void)hipStreamWaitEvent(r.main, P.done[(k0 - ch - 1) % RING], 0);
         rc = is.issue_front(k0, n);
-        for (int k = k0; k < k0 + n && !rc; ++k)
-            rc = fused ? is.issue_recurrent_fused(k) : is.issue_recurrent(k);
+        for (int k = k0; k < k0 + n && !rc; ++k) rc = is.issue_recurrent(k);
         if (rc) break;
-        if (fused) {
-            // (tuning builds) plane k's snapshots come out of plane k+1's first launch: the decoder runs one chunk behind
-            if (k0 > 0) rc = is.issue_decoder(k0 - ch, ch);
-            if (!rc && k0 + n == nplanes) {
-                rc = is.issue_final_combine(nplanes - 1);
-                if (!rc) rc = is.issue_decoder(k0, n);
-            }
-        } else {
-            rc = is.issue_decoder(k0, n);
-        }
+        rc = is.issue_decoder(k0, n);
     }
     if (rc) {
         // a launch failed mid-loop: drain the helper streams before the lease goes back to the pool and the caller
@@ -1573,16 +1239,6 @@ static int red_run_planes(const RedRun& r, int d_begin, int d_end)
 
 extern "C" {
 
-#ifdef SMVS_TIMING
-// profiling builds only: copies (and clears) the MFMA body's phase counters, 8 x 8 unsigned long long
-SMVS_EXPORT void smvs_debug_mfma_timing(unsigned long long* out)
-{
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(smvs::smvs_mfma_timing), sizeof(unsigned long long) * 64);
-    unsigned long long z[64] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(smvs::smvs_mfma_timing), z, sizeof(z));
-}
-#endif
 
 SMVS_EXPORT int smvs_red_set_streams(int n) { return smvs::g_red_streams.exchange(n == 0 ? 0 : 2); }
 

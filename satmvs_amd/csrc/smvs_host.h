@@ -46,13 +46,5 @@ inline const char* height_gen_check(const smvs_height_gen* g, int D, int H, int 
     return nullptr;
 }
 
-// A/B and tuning switches exist only in tuning builds (tools/ab_build.sh x -DSMVS_TUNING); the shipped library
-// never reads the environment: every switch folds to its default at compile time.
-#ifdef SMVS_TUNING
-#include <stdlib.h>
-inline int tune_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-constexpr int tune_int(const char*, int dflt) { return dflt; }
-#endif
 
 }  // namespace smvs

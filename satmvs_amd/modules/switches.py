@@ -1,6 +1,6 @@
 """Every A/B and debugging switch the Python layer takes from the environment, read in ONE place.
 
-The C library never reads the environment (tuning switches exist only in -DSMVS_TUNING builds); the package around it has a few
+The C library never reads the environment (it has no switches of its own); the package around it has a few
 switches for bisecting the training path against torch's own operators and for forcing the stock PyTorch composites.  They live on
 the `SW` object below: the SMVS_TRAIN_* family is read once, when the package is imported (tests flip the attributes); the three
 SMVS_{RED,COSTREG,FEATNET}_TORCH switches are looked up per forward (tests set them around single forwards).  The arithmetic of the

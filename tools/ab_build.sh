@@ -1,11 +1,9 @@
 #!/bin/bash
 # Build the working tree's library into gpurun_ab/<name>.so (travels with gpurun, git-ignored) for same-box A/B runs:
-#   tools/ab_build.sh cand [-Dflags...] && gpurun -- 'SMVS_LIB_PATH=$GRAFT_REPO_ROOT/gpurun_ab/cand.so python bench.py ...'
+#   tools/ab_build.sh cand [extra hipcc flags...], then run with SMVS_LIB_PATH pointing at the built cand.so
 # AB_SRC=<file.hip>[,<file.hip>...] picks the sources the flags apply to (default costvol.hip,costvol_fused.hip: the exact and the
 # fused instances of the cost-volume kernels live in one source each).
-# Objects of the other sources are cached in gpurun_ab/obj (rebuilt when a source or header is newer);
-# AB_FAST=1 adds -DSMVS_ONLY_BENCH (only the instances the headline bench launches: compiles in seconds, bench.py
-# --no-extra only).
+# Objects of the other sources are cached in obj/ beside it (rebuilt when a source or header is newer).
 set -e
 name=${1:?name}; shift; export AB_FLAGS="$*"
 cd "$(dirname "$0")/.."
@@ -25,7 +23,7 @@ for s in b.SOURCES:
     if not os.path.exists(obj) or any(os.path.getmtime(d) > os.path.getmtime(obj) for d in [src] + hdrs):
         subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", src, "-o", obj], stderr=subprocess.DEVNULL)
     objs.append(obj)
-extra = os.environ.get("AB_FLAGS", "").split() + (["-DSMVS_ONLY_BENCH"] if os.environ.get("AB_FAST") == "1" else [])
+extra = os.environ.get("AB_FLAGS", "").split()
 cvs = []
 for i, v in enumerate(var):
     cv = "gpurun_ab/obj/var%d_$name.o" % i

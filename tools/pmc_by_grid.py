@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Mean PMC values per (kernel, grid size) from a rocprofv3 --pmc run (rocpd sqlite): tells the jobs of the level-batched
-launches apart when they are launched one by one (SMVS_RED_SPLIT_JOBS=1).   python tools/pmc_by_grid.py <dir> [name filter]"""
+launches apart only when they are launched one by one.   python tools/pmc_by_grid.py <dir> [name filter]"""
 import glob, os, sqlite3, sys
 from collections import defaultdict
 for db in sorted(glob.glob(os.path.join(sys.argv[1], "**", "*.db"), recursive=True)):
