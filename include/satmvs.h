@@ -526,11 +526,30 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   two middle values in float64 for even counts), 1 mean (float64 sum in an order fixed by the count), 2 min, 3 max; empty
  *   cells get nodata.  dsm (gh, gw) float32.  The result is bit-identical from run to run and under any permutation of the
  *   points.  workspace: smvs_dsm_workspace_bytes(n, gw, gh) bytes (0 = unsupported sizes).
- * Limits: n < 2^31 per reduce, gw * gh < 2^31 cells, positive sizes and resolutions. */
+ * smvs_rpc_dsm_render: the reverse direction, a DSM rendered into one view's image-space heights.  dsm (gh, gw) float32
+ *   (device) on grid4 (HOST, as above: cell centres on integer u = (E - E0) / xres, v = (N0 - N) / yres); rpc170 (device) the
+ *   view's 170-vector; height (H, W) float32 (device) = view pixels (x0 + j, y0 + i), x = column, y = row (as smvs_rpc_dsm_bin).
+ *   Every step is float64.  S(E, N) = bilinear over the cells floor(u) .. floor(u)+1 x floor(v) .. floor(v)+1, as three lerps
+ *   (a = z00 + du (z01 - z00), b = z10 + du (z11 - z10), S = a + dv (b - a)); DEFINED only where all four cells are on the grid,
+ *   finite and != nodata, never extrapolated.  G(h) = TM_forward(rpc_photo2obj(x, y, h)); f(h) = S(G(h)) - h.
+ *   [h_lo, h_hi] = min / max of the valid cells (the caller's).  D = max(|dE| / xres, |dN| / yres) between G(h_hi) and G(h_lo);
+ *   K = clamp(ceil(2 D), 1, 4096) (a step moves at most half a cell; 4096 is reached only by absurd inputs; NaN D gives 1);
+ *   samples h_k = h_hi - k (h_hi - h_lo) / K, k = 0 .. K - 1, and h_K = h_lo exactly (so ground at the lowest valid cell is
+ *   always reached whatever the rounding of k (h_hi - h_lo) / K); the hit is the first k with f(h_k) defined and >= 0.
+ *   k = 0 -> h_hi.  No hit, or f(h_{k-1}) undefined (the ray left a hole or the grid) -> invalid.  Otherwise B bisection steps
+ *   on [a, b] = [h_k, h_{k-1}], B = clamp(ceil(log2(dh / tol)), 0, 60) with dh = (h_hi - h_lo) / K, computed exactly as the
+ *   least B with dh 2^-B <= tol: m = 0.5 (a + b); f(m) undefined -> invalid; f(m) >= 0 -> a = m, else b = m.  The result is
+ *   0.5 (a + b) of the final bracket, rounded to float32; invalid pixels are NaN.  No atomics: bit-identical from run to run,
+ *   and a tile rendered with its origin equals the same crop of a whole-view render bit for bit.
+ * Limits: n < 2^31 per reduce, gw * gh < 2^31 cells, H * W < 2^31 pixels, x0, y0 >= 0 with x0 + W and y0 + H fitting in an int,
+ * positive sizes and resolutions, h_lo <= h_hi finite, tol > 0 finite. */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
                      int* cell, unsigned* count, double* east, double* north, void* stream);
+int smvs_rpc_dsm_render(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
+                        const double* rpc170, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
+                        float* height, void* stream);
 size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh);
 int smvs_dsm_reduce(const int* cell, const float* height, size_t n, const unsigned* count, int gw, int gh,
                     int mode, float nodata, float* dsm, void* workspace, size_t workspace_bytes, void* stream);

@@ -6,10 +6,13 @@
 //                     -> (E, N) through the TM forward, -> grid cell; counts per cell accumulated with atomics.
 //   smvs_dsm_reduce   exclusive scan of the counts, scatter of the heights into per-cell buckets, sort of every bucket on the
 //                     order-preserving uint32 image of the float, then median / mean / min / max of the sorted bucket.
+//   smvs_rpc_dsm_render  the reverse direction: one lane per pixel of a view marches its ray (x, y, h) down through the
+//                     bilinear surface of a DSM, then bisects the crossing; the first crossing from above is the pixel's height.
 //
 // Determinism: the only order-dependent steps are the atomics (which slot of its bucket a height lands in, which position a cell
 // takes in a tier list).  Every bucket is sorted before it is reduced, equal keys are equal bits, and the reduction order of a
 // bucket depends on its size alone, so the DSM is bit-identical from run to run and under any permutation of points or maps.
+#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
@@ -527,6 +530,109 @@ void dsm_cells_radix(const unsigned* __restrict__ offs, const unsigned* __restri
     }
 }
 
+// ---- render pass: DSM -> one view's image-space heights (include/satmvs.h) -----------------------------
+constexpr int RENDER_TILE = 16;                      // 16 x 16 pixels per workgroup: each wave covers 16 columns x 4 rows
+constexpr int RENDER_MAX_STEPS = 4096, RENDER_MAX_BISECT = 60;
+constexpr unsigned RENDER_MAX_BLOCKS = 1u << 20;     // grid-stride over tiles beyond this
+
+__device__ __forceinline__ bool dsm_cell_valid(float z, float nodata) { return isfinite(z) && z != nodata; }
+
+// S(E, N): bilinear over the cells floor(u) .. floor(u)+1 x floor(v) .. floor(v)+1, written as three lerps so that a flat patch
+// gives its height exactly.  False where one of the four is off the grid, non-finite or nodata (never extrapolated).
+__device__ __forceinline__ bool dsm_surface(const float* __restrict__ z, int gw, int gh, float nodata, const DsmGrid& g,
+                                            double E, double N, double& S)
+{
+    const double u = (E - g.e0) / g.xres, v = (g.n0 - N) / g.yres;
+    const double cu = floor(u), cv = floor(v);
+    if (!(cu >= 0.0 && cu < (double)(gw - 1) && cv >= 0.0 && cv < (double)(gh - 1))) return false;    // NaN fails too
+    const float* p = z + (size_t)(int)cv * gw + (int)cu;
+    const float z00 = p[0], z01 = p[1], z10 = p[gw], z11 = p[gw + 1];
+    if (!(dsm_cell_valid(z00, nodata) && dsm_cell_valid(z01, nodata) && dsm_cell_valid(z10, nodata) && dsm_cell_valid(z11, nodata)))
+        return false;
+    const double du = u - cu, dv = v - cv;
+    const double a = (double)z00 + du * ((double)z01 - (double)z00);
+    const double b = (double)z10 + du * ((double)z11 - (double)z10);
+    S = a + dv * (b - a);
+    return true;
+}
+
+// K = clamp(ceil(2 D), 1, RENDER_MAX_STEPS), D = the ray's travel in cells over [h_lo, h_hi] (NaN -> 1).
+__device__ __forceinline__ int render_march_steps(const DsmGrid& g, double E_hi, double N_hi, double E_lo, double N_lo)
+{
+    const double dE = fabs(E_hi - E_lo) / g.xres, dN = fabs(N_hi - N_lo) / g.yres;
+    const double c = ceil(2.0 * (dE > dN ? dE : dN));
+    return c >= (double)RENDER_MAX_STEPS ? RENDER_MAX_STEPS : c >= 1.0 ? (int)c : 1;
+}
+
+// B = clamp(ceil(log2(dh / tol)), 0, RENDER_MAX_BISECT), exactly: the least b with dh * 2^-b <= tol (halving is exact).
+__device__ __forceinline__ int render_bisect_steps(double dh, double tol)
+{
+    int b = 0;
+    while (dh > tol && b < RENDER_MAX_BISECT) { dh *= 0.5; ++b; }
+    return b;
+}
+
+// One lane per pixel.  The march (h_k = h_hi - k (h_hi - h_lo) / K, h_K = h_lo; first k with f(h_k) = S(G(h_k)) - h_k defined and >= 0)
+// and the bisection of [h_k, h_{k-1}] run as ONE loop whose body is one evaluation photo2obj -> TM -> bilinear; the lane's
+// state picks the next height, so lanes in different phases share the body instead of running it twice under divergence.
+__global__ __launch_bounds__(RENDER_TILE * RENDER_TILE)
+void dsm_render_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, float nodata, TmConst t,
+                       const double* __restrict__ rpc, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
+                       float* __restrict__ out)
+{
+    const unsigned nbx = (unsigned)(W + RENDER_TILE - 1) / RENDER_TILE, nby = (unsigned)(H + RENDER_TILE - 1) / RENDER_TILE;
+    const unsigned ntiles = nbx * nby;
+    const cgeo_t r = as_cgeo(rpc);
+    const RpcInv rn = rpc_inv_image(r);
+    for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int j = (int)(tile % nbx) * RENDER_TILE + (int)(threadIdx.x % RENDER_TILE);
+        const int i = (int)(tile / nbx) * RENDER_TILE + (int)(threadIdx.x / RENDER_TILE);
+        if (i >= H || j >= W) continue;
+        const double x = (double)(x0 + j), y = (double)(y0 + i);
+        double lat, lon, E_lo, N_lo;
+        rpc_photo2obj(launder(r), rn, x, y, h_lo, lat, lon);
+        tm_forward(t, lat, lon, E_lo, N_lo);
+        double h = h_hi, h_prev = h_hi, a = 0.0, b = 0.0, step = 0.0;
+        int k = 0, K = 1, left = -1;                 // left < 0: marching; else bisection steps still to take
+        bool prev_ok = false;
+        float res = __builtin_nanf("");
+        for (;;) {
+            double E, N, S;
+            rpc_photo2obj(launder(r), rn, x, y, h, lat, lon);
+            tm_forward(t, lat, lon, E, N);
+            const bool ok = dsm_surface(z, gw, gh, nodata, g, E, N, S);
+            const bool below = ok && S - h >= 0.0;   // f(h) defined and >= 0
+            if (left < 0) {
+                if (k == 0) {
+                    K = render_march_steps(g, E, N, E_lo, N_lo);
+                    step = (h_hi - h_lo) / (double)K;
+                }
+                if (!below) {
+                    if (k == K) break;               // no sample qualifies: invalid
+                    prev_ok = ok;
+                    h_prev = h;
+                    ++k;
+                    h = (k == K) ? h_lo : h_hi - (double)k * step;     // the last sample is h_lo exactly, whatever the rounding
+                    continue;
+                }
+                if (k == 0) { res = (float)h_hi; break; }
+                if (!prev_ok) break;                 // came out of a hole or off the grid: invalid
+                a = h;
+                b = h_prev;
+                left = render_bisect_steps(step, tol);
+            } else {
+                if (!ok) break;                      // a midpoint where f is undefined: invalid
+                if (below) a = h;
+                else b = h;
+                --left;
+            }
+            if (left == 0) { res = (float)(0.5 * (a + b)); break; }
+            h = 0.5 * (a + b);
+        }
+        out[(size_t)i * W + j] = res;
+    }
+}
+
 // ---- workspace layout --------------------------------------------------------------------------------------------------------
 struct DsmWs { size_t offs, cursor, keys, alt, tiles, lcount, list1, list2, bytes; };
 
@@ -599,6 +705,30 @@ SMVS_EXPORT int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask,
     hipLaunchKernelGGL(dsm_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        height, mask, rpc170, H, W, t, g, gw, gh, cell, count, east, north);
     return check_launch_dsm("dsm_bin");
+}
+
+SMVS_EXPORT int smvs_rpc_dsm_render(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
+                                    const double* rpc170, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
+                                    float* height, void* stream)
+{
+    using namespace smvs;
+    if (!dsm || !grid4 || !tm7 || !rpc170 || !height) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
+    if ((long long)H * W >= (1ll << 31)) return fail(SMVS_ERR_ARG, "view too large: H * W must be below 2^31 pixels");
+    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
+    if (x0 < 0 || y0 < 0) return fail(SMVS_ERR_ARG, "negative origin");
+    if ((long long)x0 + W > INT_MAX || (long long)y0 + H > INT_MAX) return fail(SMVS_ERR_ARG, "origin + size does not fit in an int");
+    const DsmGrid g{grid4[0], grid4[1], grid4[2], grid4[3]};
+    if (!isfinite(g.e0) || !isfinite(g.n0) || !(g.xres > 0.0) || !(g.yres > 0.0) || !isfinite(g.xres) || !isfinite(g.yres))
+        return fail(SMVS_ERR_ARG, "bad grid: E0, N0 finite, xres and yres positive and finite");
+    TmConst t;
+    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
+    if (!isfinite(h_lo) || !isfinite(h_hi) || !(h_lo <= h_hi)) return fail(SMVS_ERR_ARG, "height bracket: h_lo <= h_hi, both finite");
+    if (!(tol > 0.0) || !isfinite(tol)) return fail(SMVS_ERR_ARG, "tol must be positive and finite");
+    const unsigned ntiles = (unsigned)((W + RENDER_TILE - 1) / RENDER_TILE) * (unsigned)((H + RENDER_TILE - 1) / RENDER_TILE);
+    hipLaunchKernelGGL(dsm_render_kernel, dim3(std::min(ntiles, RENDER_MAX_BLOCKS)), dim3(RENDER_TILE * RENDER_TILE), 0,
+                       (hipStream_t)stream, dsm, gw, gh, g, nodata, t, rpc170, H, W, x0, y0, h_lo, h_hi, tol, height);
+    return check_launch_dsm("dsm_render");
 }
 
 SMVS_EXPORT size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh)

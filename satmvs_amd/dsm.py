@@ -4,9 +4,16 @@
     dsm = heights_to_dsm(heights, rpcs, proj, grid)            # (gh, gw) float32, nodata where no point fell
     write_dsm("out.tif", dsm, grid)                            # float32 TIFF + world file (.tfw)
 
+and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
+
+    dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
+    h = render_heights(dsm, grid, rpc, proj, (H, W), origin=(x0, y0))   # (H, W) float32, NaN where the view sees no DSM
+    save_pfm("height.pfm", h)                                  # data_io.save_pfm
+
 The hot path is native (include/satmvs.h, smvs_rpc_dsm_bin / smvs_dsm_reduce): one lane per pixel projects (x, y, h) through
 the inverse RPC and the Transverse Mercator forward into a cell; the reduce sorts every cell's heights and takes the median /
 mean / min / max.  The result is bit-identical from run to run and under any order of the maps.
+smvs_rpc_dsm_render marches every pixel's ray down through the bilinear DSM surface and bisects the first crossing.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -196,6 +203,57 @@ def heights_to_dsm(heights, rpcs, projection, grid, masks=None, mode="median", n
     if as_numpy:
         out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
     return (out, cnt) if return_count else out
+
+
+def _int_pair(v, name):
+    try:
+        a, b = v
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a pair of integers, got %r" % (name, v)) from None
+    if not all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in (a, b)):
+        raise ValueError("%s must be a pair of integers, got %r" % (name, v))
+    return int(a), int(b)
+
+
+def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999.0, tol=1e-3):
+    """Render a DSM into one view: the height each pixel of the view sees (include/satmvs.h
+    smvs_rpc_dsm_render for the exact definition).  dsm (grid.height, grid.width) float32 on `grid`, numpy or a device tensor;
+    cells equal to `nodata` or non-finite are holes (nodata=float("nan") makes NaN alone mean "no value").  rpc: the view's
+    170-vector; shape = (H, W) of the rendered tile, origin = (x0, y0) its upper-left pixel in the view (pixel (i, j) of the tile
+    is view column x0 + j, row y0 + i).  Heights are found to within tol [m].
+    -> (H, W) float32, NaN where the view sees no DSM; numpy if the DSM came as numpy, a device tensor otherwise."""
+    H, W = _int_pair(shape, "shape")
+    x0, y0 = _int_pair(origin, "origin")
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("shape must be positive with H * W below 2^31, got %r" % (tuple(shape),))
+    if x0 < 0 or y0 < 0 or x0 + W > 2 ** 31 - 1 or y0 + H > 2 ** 31 - 1:
+        raise ValueError("origin must be non-negative, with x0 + W and y0 + H below 2^31, got %r" % (tuple(origin),))
+    tol = float(tol)
+    if not (tol > 0.0 and math.isfinite(tol)):
+        raise ValueError("tol must be positive and finite, got %r" % tol)
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm, dtype=np.float32)
+    if tuple(dsm.shape) != (grid.height, grid.width):
+        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
+    r = torch.as_tensor(rpc, dtype=torch.float64).reshape(-1) if not isinstance(rpc, torch.Tensor) else rpc.reshape(-1)
+    if r.numel() != 170:
+        raise ValueError("rpc vectors must hold 170 values, got %d" % r.numel())
+    as_numpy = not isinstance(dsm, torch.Tensor)
+    dev = _dev()
+    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
+    r = r.to(device=dev, dtype=torch.float64).contiguous()
+    valid = torch.isfinite(z) & (z != float(np.float32(nodata)))      # the kernel's test: float32 cells against (float)nodata
+    lo = torch.where(valid, z, torch.full_like(z, math.inf)).amin()
+    hi = torch.where(valid, z, torch.full_like(z, -math.inf)).amax()
+    h_lo, h_hi = float(lo), float(hi)
+    if not math.isfinite(h_lo):
+        raise ValueError("the DSM has no valid cell")
+    out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    grid4, tm7 = grid.grid4(), projection.tm7()
+    with torch.cuda.device(dev):
+        _lib.call("smvs_rpc_dsm_render", _lib.ptr(z), grid.width, grid.height, _vp(grid4), float(nodata), _vp(tm7), _lib.ptr(r),
+                  H, W, x0, y0, h_lo, h_hi, tol, _lib.ptr(out), _lib.current_stream(dev))
+    return out.cpu().numpy() if as_numpy else out
 
 
 def write_dsm(path, dsm, grid):
