@@ -541,8 +541,28 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   least B with dh 2^-B <= tol: m = 0.5 (a + b); f(m) undefined -> invalid; f(m) >= 0 -> a = m, else b = m.  The result is
  *   0.5 (a + b) of the final bracket, rounded to float32; invalid pixels are NaN.  No atomics: bit-identical from run to run,
  *   and a tile rendered with its origin equals the same crop of a whole-view render bit for bit.
+ * smvs_rpc_ortho: one view's image resampled onto the DSM grid (a true orthophoto: occlusion by the DSM itself).  dsm, grid4,
+ *   nodata, tm7, rpc170 as for the render; image (H, W, C) float32 channels-last (device), 1 <= C <= 16, pixel (i, j) = view
+ *   column x0 + j, row y0 + i; ortho (gh, gw, C) float32, source (gh, gw) int32, state (gh, gw) uint8 or null (all device).
+ *   image and ortho go together and may both be null (a visibility-only call); ortho needs source; source or state is given.
+ *   Every step is float64, one lane per cell (r, c):
+ *   1. E = E0 + c xres, N = N0 - r yres; z = the float32 cell.  z not finite or == nodata -> state 0 (no height).
+ *   2. (lat, lon) = TM_inverse(E, N); (x, y) = rpc_obj2photo(lat, lon, z), x = sample = column, y = line = row; u = x - x0,
+ *      v = y - y0.  Unless 0 <= u <= W - 1 and 0 <= v <= H - 1 (NaN fails) -> state 1 (outside the image).
+ *   3. occlusion != 0 only: G(h) = TM_forward(rpc_photo2obj(x, y, h)), f(h) = S(G(h)) - h with the render's surface S.  No
+ *      samples if z >= h_hi.  Else D = max(|dE| / xres, |dN| / yres) between G(z) and G(h_hi), K = clamp(ceil(2 D), 1, 4096)
+ *      (NaN D gives 1), samples h_k = z + k (h_hi - z) / K, k = 1 .. K - 1, and h_K = h_hi exactly.  Some sample with f(h_k)
+ *      defined and > occ_tol -> state 2 (occluded); the lane stops there.  Undefined samples (holes, off the grid) do NOT
+ *      occlude (unlike the render, where leaving a hole invalidates the pixel).
+ *   4. Otherwise state 3 (visible): c0 = min(floor(u), W - 2), du = u - c0 (W = 1: c0 = 0, du = 0, both taps column 0); rows
+ *      alike; a = p00 + du (p01 - p00), b = p10 + du (p11 - p10), value = a + dv (b - a) from float32 taps in float64, rounded
+ *      to float32 per channel.
+ *   5. Mosaic rule: ortho (C values) and source (= view) are written only where the state is 3 and source < 0 on entry.
+ *      Without state, cells with source >= 0 on entry skip steps 2 - 4; state, when given, is written for every cell whatever
+ *      source holds.  No atomics: bit-identical from run to run.
  * Limits: n < 2^31 per reduce, gw * gh < 2^31 cells, H * W < 2^31 pixels, x0, y0 >= 0 with x0 + W and y0 + H fitting in an int,
- * positive sizes and resolutions, h_lo <= h_hi finite, tol > 0 finite. */
+ * positive sizes and resolutions, h_lo <= h_hi finite, tol > 0 finite; smvs_rpc_ortho: h_hi finite, occ_tol >= 0 finite,
+ * view >= 0. */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -550,6 +570,10 @@ int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const doubl
 int smvs_rpc_dsm_render(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
                         const double* rpc170, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
                         float* height, void* stream);
+int smvs_rpc_ortho(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
+                   const double* rpc170, const float* image, int H, int W, int C, int x0, int y0,
+                   double h_hi, int occlusion, double occ_tol, int view,
+                   float* ortho, int* source, unsigned char* state, void* stream);
 size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh);
 int smvs_dsm_reduce(const int* cell, const float* height, size_t n, const unsigned* count, int gw, int gh,
                     int mode, float nodata, float* dsm, void* workspace, size_t workspace_bytes, void* stream);

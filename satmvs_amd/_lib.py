@@ -79,6 +79,7 @@ _SIGNATURES = {
     "smvs_rpc_dsm_bin": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "smvs_dsm_reduce": [_vp, _vp, _sz, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp],
     "smvs_rpc_dsm_render": [_vp, _i, _i, _vp, _f, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp],
+    "smvs_rpc_ortho": [_vp, _i, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i, _vp, _vp, _vp, _vp],
 }
 _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": [_i], "smvs_red_workspace_bytes": [_i] * 4,
                "smvs_red_pred_workspace_bytes": [_i] * 4, "smvs_costreg_packed_floats": [_i],

@@ -8,6 +8,8 @@
 //                     order-preserving uint32 image of the float, then median / mean / min / max of the sorted bucket.
 //   smvs_rpc_dsm_render  the reverse direction: one lane per pixel of a view marches its ray (x, y, h) down through the
 //                     bilinear surface of a DSM, then bisects the crossing; the first crossing from above is the pixel's height.
+//   smvs_rpc_ortho    the orthophoto: one lane per DSM cell projects the cell's point into a view, marches the ray up to test
+//                     occlusion, and samples the image bilinearly; a mosaic fills each cell from the first view that sees it.
 //
 // Determinism: the only order-dependent steps are the atomics (which slot of its bucket a height lands in, which position a cell
 // takes in a tier list).  Every bucket is sorted before it is reduced, equal keys are equal bits, and the reduction order of a
@@ -633,6 +635,99 @@ void dsm_render_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, f
     }
 }
 
+// ---- orthophoto pass: one view's image resampled onto the DSM grid, with occlusion (include/satmvs.h) --
+constexpr int ORTHO_MAX_CHANNELS = 16;
+enum : unsigned char { ORTHO_NO_HEIGHT = 0, ORTHO_OUTSIDE = 1, ORTHO_OCCLUDED = 2, ORTHO_VISIBLE = 3 };
+
+// Whether the ray up from the cell's point (x, y, zc) passes under the surface: samples h_k = zc + k (h_hi - zc) / K,
+// k = 1 .. K - 1, and h_K = h_hi exactly, K from the travel between G(zc) and G(h_hi) as in the render.  A sample occludes where
+// f(h_k) = S(G(h_k)) - h_k is defined and > occ_tol; undefined samples (holes, off the grid) do not.  ONE loop whose body is one
+// evaluation photo2obj -> TM -> bilinear, as in the render: G(zc) first (only for K), then h_K = h_hi (its G sets K; the order
+// of the samples does not change whether one of them occludes), then h_1 .. h_{K-1}.
+__device__ __forceinline__ bool ortho_occluded(const float* __restrict__ z, int gw, int gh, float nodata, const DsmGrid& g,
+                                               const TmConst& t, cgeo_t r, const RpcInv& rn, double x, double y, double zc,
+                                               double h_hi, double occ_tol)
+{
+    if (!(zc < h_hi)) return false;
+    double h = zc, E_z = 0.0, N_z = 0.0, step = 0.0;
+    int k = -1, K = 1;                               // k = -1: G(zc); k = 0: h_K; then k = 1 .. K - 1, K <= RENDER_MAX_STEPS
+    for (;;) {
+        double lat, lon, E, N, S;
+        rpc_photo2obj(launder(r), rn, x, y, h, lat, lon);
+        tm_forward(t, lat, lon, E, N);
+        if (k < 0) {
+            E_z = E;
+            N_z = N;
+            k = 0;
+            h = h_hi;
+            continue;
+        }
+        if (dsm_surface(z, gw, gh, nodata, g, E, N, S) && S - h > occ_tol) return true;
+        if (k == 0) {
+            K = render_march_steps(g, E, N, E_z, N_z);
+            step = (h_hi - zc) / (double)K;
+        }
+        if (++k >= K) return false;
+        h = zc + (double)k * step;
+    }
+}
+
+// One lane per DSM cell, 16 x 16-cell workgroups (neighbouring rays read the same DSM lines), grid-stride past
+// RENDER_MAX_BLOCKS.  Height -> TM inverse -> rpc_obj2photo -> bounds -> occlusion march -> bilinear image sample; ortho and
+// source are written where the cell is visible and source < 0 on entry.  Without a state map, cells already filled by an
+// earlier view are skipped whole.
+__global__ __launch_bounds__(RENDER_TILE * RENDER_TILE)
+void dsm_ortho_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, float nodata, TmConst t,
+                      const double* __restrict__ rpc, const float* __restrict__ image, int H, int W, int C, int x0, int y0,
+                      double h_hi, int occlusion, double occ_tol, int view,
+                      float* __restrict__ ortho, int* __restrict__ source, unsigned char* __restrict__ state)
+{
+    const unsigned nbx = (unsigned)(gw + RENDER_TILE - 1) / RENDER_TILE, nby = (unsigned)(gh + RENDER_TILE - 1) / RENDER_TILE;
+    const unsigned ntiles = nbx * nby;
+    const cgeo_t r = as_cgeo(rpc);
+    const RpcInv rg = rpc_inv_ground(r), ri = rpc_inv_image(r);
+    for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int c = (int)(tile % nbx) * RENDER_TILE + (int)(threadIdx.x % RENDER_TILE);
+        const int row = (int)(tile / nbx) * RENDER_TILE + (int)(threadIdx.x / RENDER_TILE);
+        if (row >= gh || c >= gw) continue;
+        const size_t cell = (size_t)row * gw + c;
+        if (!state && source[cell] >= 0) continue;   // filled by an earlier view; nothing else to write
+        const float zf = z[cell];
+        unsigned char st = ORTHO_NO_HEIGHT;
+        double u = 0.0, v = 0.0;
+        if (dsm_cell_valid(zf, nodata)) {
+            const double E = g.e0 + (double)c * g.xres, N = g.n0 - (double)row * g.yres;
+            double lat, lon, x, y;
+            tm_inverse(t, E, N, lat, lon);
+            rpc_obj2photo(launder(r), rg, lat, lon, (double)zf, x, y);
+            u = x - (double)x0;
+            v = y - (double)y0;
+            if (!(u >= 0.0 && u <= (double)(W - 1) && v >= 0.0 && v <= (double)(H - 1))) st = ORTHO_OUTSIDE;   // NaN fails
+            else if (occlusion && ortho_occluded(z, gw, gh, nodata, g, t, r, ri, x, y, (double)zf, h_hi, occ_tol)) st = ORTHO_OCCLUDED;
+            else st = ORTHO_VISIBLE;
+        }
+        if (state) state[cell] = st;
+        if (st != ORTHO_VISIBLE || !source || source[cell] >= 0) continue;
+        if (ortho) {
+            // pixel centres on integers; the last column / row is reached with du = 1 (dv = 1) from the one before it
+            const int c0 = W > 1 ? min((int)floor(u), W - 2) : 0, r0 = H > 1 ? min((int)floor(v), H - 2) : 0;
+            const int c1 = W > 1 ? c0 + 1 : 0, r1 = H > 1 ? r0 + 1 : 0;
+            const double du = W > 1 ? u - (double)c0 : 0.0, dv = H > 1 ? v - (double)r0 : 0.0;
+            const float* p00 = image + ((size_t)r0 * W + c0) * C;
+            const float* p01 = image + ((size_t)r0 * W + c1) * C;
+            const float* p10 = image + ((size_t)r1 * W + c0) * C;
+            const float* p11 = image + ((size_t)r1 * W + c1) * C;
+            float* o = ortho + cell * C;
+            for (int ch = 0; ch < ORTHO_MAX_CHANNELS && ch < C; ++ch) {
+                const double a = (double)p00[ch] + du * ((double)p01[ch] - (double)p00[ch]);
+                const double b = (double)p10[ch] + du * ((double)p11[ch] - (double)p10[ch]);
+                o[ch] = (float)(a + dv * (b - a));
+            }
+        }
+        source[cell] = view;
+    }
+}
+
 // ---- workspace layout --------------------------------------------------------------------------------------------------------
 struct DsmWs { size_t offs, cursor, keys, alt, tiles, lcount, list1, list2, bytes; };
 
@@ -729,6 +824,37 @@ SMVS_EXPORT int smvs_rpc_dsm_render(const float* dsm, int gw, int gh, const doub
     hipLaunchKernelGGL(dsm_render_kernel, dim3(std::min(ntiles, RENDER_MAX_BLOCKS)), dim3(RENDER_TILE * RENDER_TILE), 0,
                        (hipStream_t)stream, dsm, gw, gh, g, nodata, t, rpc170, H, W, x0, y0, h_lo, h_hi, tol, height);
     return check_launch_dsm("dsm_render");
+}
+
+SMVS_EXPORT int smvs_rpc_ortho(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
+                               const double* rpc170, const float* image, int H, int W, int C, int x0, int y0,
+                               double h_hi, int occlusion, double occ_tol, int view,
+                               float* ortho, int* source, unsigned char* state, void* stream)
+{
+    using namespace smvs;
+    if (!dsm || !grid4 || !tm7 || !rpc170) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if ((image == nullptr) != (ortho == nullptr)) return fail(SMVS_ERR_ARG, "null pointer argument: image and ortho go together");
+    if (ortho && !source) return fail(SMVS_ERR_ARG, "null pointer argument: ortho needs source (the mosaic rule reads it)");
+    if (!source && !state) return fail(SMVS_ERR_ARG, "null pointer argument: nothing to write (give source or state)");
+    if (C < 1 || C > ORTHO_MAX_CHANNELS) return fail(SMVS_ERR_ARG, "channel count C must be in 1 .. %d", ORTHO_MAX_CHANNELS);
+    if (H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
+    if ((long long)H * W >= (1ll << 31)) return fail(SMVS_ERR_ARG, "view too large: H * W must be below 2^31 pixels");
+    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
+    if (x0 < 0 || y0 < 0) return fail(SMVS_ERR_ARG, "negative origin");
+    if ((long long)x0 + W > INT_MAX || (long long)y0 + H > INT_MAX) return fail(SMVS_ERR_ARG, "origin + size does not fit in an int");
+    const DsmGrid g{grid4[0], grid4[1], grid4[2], grid4[3]};
+    if (!isfinite(g.e0) || !isfinite(g.n0) || !(g.xres > 0.0) || !(g.yres > 0.0) || !isfinite(g.xres) || !isfinite(g.yres))
+        return fail(SMVS_ERR_ARG, "bad grid: E0, N0 finite, xres and yres positive and finite");
+    TmConst t;
+    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
+    if (!isfinite(h_hi)) return fail(SMVS_ERR_ARG, "h_hi must be finite");
+    if (!(occ_tol >= 0.0) || !isfinite(occ_tol)) return fail(SMVS_ERR_ARG, "occ_tol must be finite and >= 0");
+    if (view < 0) return fail(SMVS_ERR_ARG, "view must be non-negative");
+    const unsigned ntiles = (unsigned)((gw + RENDER_TILE - 1) / RENDER_TILE) * (unsigned)((gh + RENDER_TILE - 1) / RENDER_TILE);
+    hipLaunchKernelGGL(dsm_ortho_kernel, dim3(std::min(ntiles, RENDER_MAX_BLOCKS)), dim3(RENDER_TILE * RENDER_TILE), 0,
+                       (hipStream_t)stream, dsm, gw, gh, g, nodata, t, rpc170, image, H, W, C, x0, y0, h_hi, occlusion, occ_tol,
+                       view, ortho, source, state);
+    return check_launch_dsm("dsm_ortho");
 }
 
 SMVS_EXPORT size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh)

@@ -10,10 +10,18 @@ and the reverse direction, a DSM rendered into one view's image-space heights (e
     h = render_heights(dsm, grid, rpc, proj, (H, W), origin=(x0, y0))   # (H, W) float32, NaN where the view sees no DSM
     save_pfm("height.pfm", h)                                  # data_io.save_pfm
 
+and the orthophoto, the views' imagery resampled onto the DSM's grid with occlusion (a true orthophoto):
+
+    ortho, src = orthorectify(images, rpcs, dsm, grid, proj, return_source=True)   # (gh, gw, C) float32, NaN where unseen
+    write_ortho("ortho.tif", np.nan_to_num(ortho).clip(0, 255).astype(np.uint8), grid)   # RGB TIFF + world file
+    vis = visibility(dsm, grid, rpcs[0], proj, images[0].shape[:2])           # 0 no height, 1 outside, 2 occluded, 3 visible
+
 The hot path is native (include/satmvs.h, smvs_rpc_dsm_bin / smvs_dsm_reduce): one lane per pixel projects (x, y, h) through
 the inverse RPC and the Transverse Mercator forward into a cell; the reduce sorts every cell's heights and takes the median /
 mean / min / max.  The result is bit-identical from run to run and under any order of the maps.
 smvs_rpc_dsm_render marches every pixel's ray down through the bilinear DSM surface and bisects the first crossing.
+smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
+the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -215,6 +223,17 @@ def _int_pair(v, name):
     return int(a), int(b)
 
 
+def _tile(shape, origin):
+    """(H, W, x0, y0) of a tile of a view, checked as the native entries check them."""
+    H, W = _int_pair(shape, "shape")
+    x0, y0 = _int_pair(origin, "origin")
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("shape must be positive with H * W below 2^31, got %r" % (tuple(shape),))
+    if x0 < 0 or y0 < 0 or x0 + W > 2 ** 31 - 1 or y0 + H > 2 ** 31 - 1:
+        raise ValueError("origin must be non-negative, with x0 + W and y0 + H below 2^31, got %r" % (tuple(origin),))
+    return H, W, x0, y0
+
+
 def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999.0, tol=1e-3):
     """Render a DSM into one view: the height each pixel of the view sees (include/satmvs.h
     smvs_rpc_dsm_render for the exact definition).  dsm (grid.height, grid.width) float32 on `grid`, numpy or a device tensor;
@@ -222,12 +241,7 @@ def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999
     170-vector; shape = (H, W) of the rendered tile, origin = (x0, y0) its upper-left pixel in the view (pixel (i, j) of the tile
     is view column x0 + j, row y0 + i).  Heights are found to within tol [m].
     -> (H, W) float32, NaN where the view sees no DSM; numpy if the DSM came as numpy, a device tensor otherwise."""
-    H, W = _int_pair(shape, "shape")
-    x0, y0 = _int_pair(origin, "origin")
-    if H < 1 or W < 1 or H * W >= 2 ** 31:
-        raise ValueError("shape must be positive with H * W below 2^31, got %r" % (tuple(shape),))
-    if x0 < 0 or y0 < 0 or x0 + W > 2 ** 31 - 1 or y0 + H > 2 ** 31 - 1:
-        raise ValueError("origin must be non-negative, with x0 + W and y0 + H below 2^31, got %r" % (tuple(origin),))
+    H, W, x0, y0 = _tile(shape, origin)
     tol = float(tol)
     if not (tol > 0.0 and math.isfinite(tol)):
         raise ValueError("tol must be positive and finite, got %r" % tol)
@@ -256,6 +270,213 @@ def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999
     return out.cpu().numpy() if as_numpy else out
 
 
+# ---- orthophoto ---------------------------------------------------------------------------------------------------------------
+ORTHO_STATES = ("no height", "outside", "occluded", "visible")     # the state codes 0 .. 3 of visibility() / smvs_rpc_ortho
+MAX_CHANNELS = 16
+
+
+def _dsm_checked(dsm, grid):
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm, dtype=np.float32)
+    if tuple(dsm.shape) != (grid.height, grid.width):
+        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
+    return dsm
+
+
+def _rpc_checked(rpc):
+    r = torch.as_tensor(rpc, dtype=torch.float64).reshape(-1) if not isinstance(rpc, torch.Tensor) else rpc.reshape(-1)
+    if r.numel() != 170:
+        raise ValueError("rpc vectors must hold 170 values, got %d" % r.numel())
+    return r
+
+
+def _occ_tol_checked(occ_tol):
+    t = float(occ_tol)
+    if not (math.isfinite(t) and t >= 0.0):
+        raise ValueError("occ_tol must be finite and >= 0, got %r" % t)
+    return t
+
+
+def _h_hi(z, nodata):
+    """The highest valid cell, reduced on the device (the kernel's validity test: float32 cells against (float)nodata)."""
+    valid = torch.isfinite(z) & (z != float(np.float32(nodata)))
+    h_hi = float(torch.where(valid, z, torch.full_like(z, -math.inf)).amax())
+    if not math.isfinite(h_hi):
+        raise ValueError("the DSM has no valid cell")
+    return h_hi
+
+
+def _ortho_call(z, grid, nodata, tm7, r, image, H, W, C, x0, y0, h_hi, occlusion, occ_tol, view, ortho, source, state):
+    dev = z.device
+    with torch.cuda.device(dev):
+        _lib.call("smvs_rpc_ortho", _lib.ptr(z), grid.width, grid.height, _vp(grid.grid4()), float(nodata), _vp(tm7), _lib.ptr(r),
+                  _lib.ptr(image) if image is not None else None, H, W, C, x0, y0, h_hi, 1 if occlusion else 0, occ_tol, view,
+                  _lib.ptr(ortho) if ortho is not None else None, _lib.ptr(source) if source is not None else None,
+                  _lib.ptr(state) if state is not None else None, _lib.current_stream(dev))
+
+
+def visibility(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999.0, occlusion=True, occ_tol=0.5):
+    """What one view sees of every DSM cell (include/satmvs.h smvs_rpc_ortho for the exact definition):
+    (gh, gw) uint8 with 0 = no height (nodata or non-finite cell), 1 = the cell projects outside the (H, W) = `shape` tile whose
+    upper-left pixel is `origin` = (x0, y0), 2 = occluded (the ray from the cell towards the sensor passes more than occ_tol [m]
+    under the bilinear DSM surface; only with occlusion=True), 3 = visible.  The top of the march, h_hi, is the highest valid
+    cell.  Numpy if the DSM came as numpy, a device tensor otherwise."""
+    H, W, x0, y0 = _tile(shape, origin)
+    occ_tol = _occ_tol_checked(occ_tol)
+    dsm = _dsm_checked(dsm, grid)
+    r = _rpc_checked(rpc)
+    as_numpy = not isinstance(dsm, torch.Tensor)
+    dev = _dev()
+    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
+    r = r.to(device=dev, dtype=torch.float64).contiguous()
+    h_hi = _h_hi(z, nodata)
+    state = torch.empty((grid.height, grid.width), dtype=torch.uint8, device=dev)
+    _ortho_call(z, grid, nodata, projection.tm7(), r, None, H, W, 1, x0, y0, h_hi, occlusion, occ_tol, 0, None, None, state)
+    return state.cpu().numpy() if as_numpy else state
+
+
+def _images_checked(images):
+    """[(H, W, C) arrays or tensors of a real dtype] of one image or a list; every view has the same C, 1 <= C <= 16."""
+    ims = list(images) if isinstance(images, (list, tuple)) else [images]
+    if not ims:
+        raise ValueError("no image")
+    out = []
+    for im in ims:
+        if not isinstance(im, torch.Tensor):
+            im = np.asarray(im)
+            if not (np.issubdtype(im.dtype, np.integer) or np.issubdtype(im.dtype, np.floating) or im.dtype == np.bool_):
+                raise ValueError("images must have a real dtype, got %s" % im.dtype)
+        elif im.is_complex():
+            raise ValueError("images must have a real dtype, got %s" % im.dtype)
+        if im.ndim == 2:
+            im = im[:, :, None]
+        if im.ndim != 3:
+            raise ValueError("images are (H, W) or (H, W, C), got %s" % (tuple(im.shape),))
+        if not 1 <= im.shape[2] <= MAX_CHANNELS:
+            raise ValueError("images must have 1 .. %d channels, got %d" % (MAX_CHANNELS, im.shape[2]))
+        out.append(im)
+    if len({im.shape[2] for im in out}) != 1:
+        raise ValueError("every view must have the same number of channels, got %s" % [im.shape[2] for im in out])
+    return out
+
+
+def _order_checked(order, n):
+    if isinstance(order, str):
+        if order not in ("nadir", "given"):
+            raise ValueError('order must be "nadir", "given" or a permutation of the view indices, got %r' % order)
+        return order
+    try:
+        seq = [int(i) for i in order]
+        ok = all(isinstance(i, (int, np.integer)) and not isinstance(i, bool) for i in order)
+    except (TypeError, ValueError):
+        seq, ok = [], False
+    if not ok or sorted(seq) != list(range(n)):
+        raise ValueError("order must be \"nadir\", \"given\" or a permutation of range(%d), got %r" % (n, order))
+    return seq
+
+
+def nadir_order(rpcs, grid, projection, h_top):
+    """View indices from the most to the least nadir: by the mean ground shift per metre of height, |G(h_top) - G(h_top - 100)|
+    / 100 m with G(h) = TM_forward(photo2obj(x, y, h)), at the grid's centre and the four points a quarter of the grid away from
+    it along the axes, (x, y) being each point's pixel at h_top - 100.  Ties go by index.  Host float64 RPCs (rpc_synth) and the
+    device TM (projection.proj)."""
+    from . import rpc_synth
+    ec = grid.e0 + 0.5 * (grid.width - 1) * grid.xres
+    nc = grid.n0 - 0.5 * (grid.height - 1) * grid.yres
+    qe, qn = 0.25 * grid.width * grid.xres, 0.25 * grid.height * grid.yres
+    en = np.array([[ec, nc], [ec - qe, nc], [ec + qe, nc], [ec, nc - qn], [ec, nc + qn]], np.float64)
+    ll = projection.proj(en, reverse=True)
+    h0, h1 = h_top - 100.0, h_top
+    pts = []
+    for rpc in rpcs:
+        rpc = np.asarray(torch.as_tensor(rpc).detach().cpu(), np.float64).reshape(-1)
+        x, y = rpc_synth.obj2photo(rpc, ll[:, 0], ll[:, 1], np.full(len(ll), h0))
+        for h in (h0, h1):
+            lat, lon = rpc_synth.photo2obj(rpc, x, y, np.full(len(ll), h))
+            pts.append(np.stack([lat, lon], -1))
+    g = projection.proj(np.stack(pts)).reshape(len(rpcs), 2, len(ll), 2)
+    shift = np.hypot(g[:, 1, :, 0] - g[:, 0, :, 0], g[:, 1, :, 1] - g[:, 0, :, 1]).mean(axis=1) / (h1 - h0)
+    return sorted(range(len(rpcs)), key=lambda i: (shift[i], i))
+
+
+def orthorectify(images, rpcs, dsm, grid, projection, origins=None, nodata=-999.0, occlusion=True, occ_tol=0.5, order="nadir",
+                 fill=float("nan"), return_source=False):
+    """A true orthophoto: the views' images resampled onto the DSM's grid, each cell from the first view, in `order`, that sees
+    it (visibility() state 3), bilinearly (pixel centres on integers); cells no view sees keep `fill`.  images: one image or a
+    list, each (H, W) or (H, W, C) of any real dtype (taken as float32), the same C <= 16 for all; rpcs: one 170-vector per
+    view; origins: the (x0, y0) of each image in its view (None: all (0, 0)).  order: "nadir" (nadir_order: the least ground
+    shift per metre of height first), "given", or a permutation of the view indices.  No blending between views.
+    -> (gh, gw, C) float32 and, with return_source, (gh, gw) int32 = the index of the view in `images` that filled each cell
+    (-1: none); numpy if the DSM came as numpy, device tensors otherwise."""
+    ims = _images_checked(images)
+    n = len(ims)
+    if isinstance(rpcs, (list, tuple)):
+        rs = list(rpcs)
+    elif isinstance(rpcs, (np.ndarray, torch.Tensor)) and rpcs.ndim == 2:
+        rs = [rpcs[i] for i in range(rpcs.shape[0])]
+    else:
+        rs = [rpcs]
+    if len(rs) != n:
+        raise ValueError("one RPC per image: %d images, %d rpcs" % (n, len(rs)))
+    rs = [_rpc_checked(r) for r in rs]
+    if origins is None:
+        origins = [(0, 0)] * n
+    elif n == 1 and len(origins) == 2 and all(isinstance(t, (int, np.integer)) for t in origins):
+        origins = [origins]
+    if len(origins) != n:
+        raise ValueError("one origin per image: %d images, %d origins" % (n, len(origins)))
+    tiles = [_tile(im.shape[:2], o) for im, o in zip(ims, origins)]
+    occ_tol = _occ_tol_checked(occ_tol)
+    seq = _order_checked(order, n)
+    fill = float(fill)
+    dsm = _dsm_checked(dsm, grid)
+    as_numpy = not isinstance(dsm, torch.Tensor)
+    dev = _dev()
+    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
+    h_hi = _h_hi(z, nodata)
+    if seq == "given":
+        seq = list(range(n))
+    elif seq == "nadir":
+        seq = nadir_order(rs, grid, projection, h_hi)
+    C = int(ims[0].shape[2])
+    ortho = torch.full((grid.height, grid.width, C), fill, dtype=torch.float32, device=dev)
+    source = torch.full((grid.height, grid.width), -1, dtype=torch.int32, device=dev)
+    tm7 = projection.tm7()
+    for v in seq:
+        im = ims[v] if isinstance(ims[v], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ims[v]))
+        im = im.to(device=dev, dtype=torch.float32).contiguous()
+        r = rs[v].to(device=dev, dtype=torch.float64).contiguous()
+        H, W, x0, y0 = tiles[v]
+        _ortho_call(z, grid, nodata, tm7, r, im, H, W, C, x0, y0, h_hi, occlusion, occ_tol, v, ortho, source, None)
+    if as_numpy:
+        ortho, source = ortho.cpu().numpy(), source.cpu().numpy()
+    return (ortho, source) if return_source else ortho
+
+
+def _write_tfw(path, grid):
+    text = str(grid.xres) + "\n0\n0\n" + str(-grid.yres) + "\n" + str(grid.e0) + "\n" + str(grid.n0)
+    with open(os.path.splitext(path)[0] + ".tfw", "w") as f:
+        f.write(text)
+
+
+def write_ortho(path, ortho, grid):
+    """An orthophoto as a TIFF (Pillow) plus the world file (.tfw) of write_dsm: uint8 (gh, gw), (gh, gw, 1) or (gh, gw, 3) as
+    L or RGB, float32 (gh, gw) or (gh, gw, 1) as F.  Anything else raises ValueError (convert first, e.g.
+    np.nan_to_num(o).clip(0, 255).astype(np.uint8))."""
+    from PIL import Image
+    a = ortho.detach().cpu().numpy() if isinstance(ortho, torch.Tensor) else np.asarray(ortho)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[:2] != (grid.height, grid.width):
+        raise ValueError("ortho shape %s differs from the grid's (%d, %d[, C])" % (a.shape, grid.height, grid.width))
+    C = a.shape[2]
+    if not ((a.dtype == np.uint8 and C in (1, 3)) or (a.dtype == np.float32 and C == 1)):
+        raise ValueError("write_ortho writes uint8 with 1 or 3 channels or float32 with 1, got %s with %d" % (a.dtype, C))
+    Image.fromarray(np.ascontiguousarray(a[:, :, 0] if C == 1 else a)).save(path, format="TIFF")
+    _write_tfw(path, grid)
+    return path
+
+
 def write_dsm(path, dsm, grid):
     """A float32 TIFF (Pillow) and, beside it, the world file (.tfw) in the six-line form of the reference's
     gdal_create_dsm_file (dataset/data_io.py:289-296): xres, 0, 0, -yres, E and N of the centre of the upper-left cell."""
@@ -265,9 +486,7 @@ def write_dsm(path, dsm, grid):
     if a.shape != (grid.height, grid.width):
         raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (a.shape, grid.height, grid.width))
     Image.fromarray(a, mode="F").save(path, format="TIFF")
-    text = str(grid.xres) + "\n0\n0\n" + str(-grid.yres) + "\n" + str(grid.e0) + "\n" + str(grid.n0)
-    with open(os.path.splitext(path)[0] + ".tfw", "w") as f:
-        f.write(text)
+    _write_tfw(path, grid)
     return path
 
 
