@@ -562,7 +562,27 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *      source holds.  No atomics: bit-identical from run to run.
  * Limits: n < 2^31 per reduce, gw * gh < 2^31 cells, H * W < 2^31 pixels, x0, y0 >= 0 with x0 + W and y0 + H fitting in an int,
  * positive sizes and resolutions, h_lo <= h_hi finite, tol > 0 finite; smvs_rpc_ortho: h_hi finite, occ_tol >= 0 finite,
- * view >= 0. */
+ * view >= 0.
+ *
+ * Cleaning a DSM (csrc/dsm_post.hip).  dsm, out (gh, gw) float32 (device), out distinct from dsm (aliasing is rejected); both
+ * operations read dsm only, so no result depends on the order in which cells are processed.  A cell is valid iff it is finite
+ * and != nodata, as above.  Every output is bit-identical from run to run.
+ * smvs_dsm_despike: for every valid cell, V = the valid cells of the (2 radius + 1)^2 window around it clipped at the grid
+ *   border (the centre included), n = |V|.  n < min_valid -> removed.  Otherwise m = the median of V as in smvs_dsm_reduce
+ *   (v[n / 2] of the sorted values, or (float)(0.5 ((double)v[n / 2 - 1] + (double)v[n / 2])) for even n) and the cell is
+ *   removed iff |(double)z - (double)m| > thresh.  Removed cells are written as nodata; every other cell, valid or not, is
+ *   copied bit for bit.  removed (gh, gw) uint8 or null: 1 where a cell was removed, else 0.
+ *   radius 1, 2 or 3; thresh finite and >= 0; 1 <= min_valid <= (2 radius + 1)^2.
+ * smvs_dsm_fill: eight directions (dcol, drow), rows running south, in this order: E (1,0), NE (1,-1), N (0,-1), NW (-1,-1),
+ *   W (-1,0), SW (-1,1), S (0,1), SE (1,1).  For an invalid cell p the hit of direction d is the first cell p + k d,
+ *   1 <= k <= max_steps, on the grid and valid in dsm: its float32 height z_d and k_d.  hits = the number of directions with a
+ *   hit.  The cell is filled iff hits >= min_hits, otherwise copied; valid cells are copied.  The value, over the hit
+ *   directions in the order above: method 0 (inverse distance) d2 = (double)k_d^2, doubled on a diagonal, w = 1.0 / d2,
+ *   num = sum of w (double)z_d, den = sum of w, both from 0.0, value = (float)(num / den), IEEE float64 without contraction;
+ *   method 1 (nearest) z_d of the smallest d2; method 2 (min) the lowest z_d; ties keep the earlier direction.
+ *   hits (gh, gw) uint8 or null: 255 where the input cell was valid, else the number of hits.
+ *   1 <= max_steps <= 4096, 1 <= min_hits <= 8; workspace: smvs_dsm_fill_workspace_bytes(gw, gh, max_steps) bytes (0 =
+ *   unsupported arguments), distinct from the other buffers. */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -577,6 +597,11 @@ int smvs_rpc_ortho(const float* dsm, int gw, int gh, const double* grid4, float 
 size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh);
 int smvs_dsm_reduce(const int* cell, const float* height, size_t n, const unsigned* count, int gw, int gh,
                     int mode, float nodata, float* dsm, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_despike(const float* dsm, int gw, int gh, float nodata, int radius, double thresh, int min_valid,
+                     float* out, unsigned char* removed, void* stream);
+size_t smvs_dsm_fill_workspace_bytes(int gw, int gh, int max_steps);
+int smvs_dsm_fill(const float* dsm, int gw, int gh, float nodata, int max_steps, int min_hits, int method,
+                  float* out, unsigned char* hits, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "dsm_common.h"
 #include "smvs_device.h"
 #include "smvs_host.h"
 
@@ -192,17 +193,6 @@ constexpr int TIER1_MAX = 4096;       // one workgroup per cell, bitonic sort in
 constexpr int TIER1_THREADS = 256, TIER2_THREADS = 1024, TIER2_WAVES = TIER2_THREADS / 64;
 constexpr int TIER1_BLOCKS = 2048, TIER2_BLOCKS = 256;
 
-__device__ __forceinline__ unsigned f2key(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float key2f(unsigned k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // Bucket of cell c: [lo, lo + m) of the key array.  Clamped so that counts which do not match the cells (or that wrap) can
 // neither read nor write outside the arrays: m never exceeds the slots the scatter could fill.
 __device__ __forceinline__ unsigned bucket(const unsigned* __restrict__ offs, const unsigned* __restrict__ cursor, int c,
@@ -344,27 +334,6 @@ __device__ __forceinline__ float reduce_sorted(int mode, unsigned m, double sum,
     if (mode == 1) return (float)(sum / (double)m);
     if (m & 1u) return key2f(get(m / 2));
     return (float)(0.5 * ((double)key2f(get(m / 2 - 1)) + (double)key2f(get(m / 2))));
-}
-
-// Bitonic sorting network over a register array, every index a compile-time constant (template recursion: a loop nest of this
-// depth is not always unrolled, and one dynamic index sends the whole array to scratch).
-template <int N, int SIZE, int STRIDE>
-__device__ __forceinline__ void bitonic_net(unsigned (&v)[N])
-{
-    if constexpr (SIZE <= N) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const int p = k ^ STRIDE;
-            if (p > k) {
-                const unsigned a = v[k], b = v[p];
-                const bool up = (k & SIZE) == 0;
-                v[k] = up ? min(a, b) : max(a, b);
-                v[p] = up ? max(a, b) : min(a, b);
-            }
-        }
-        if constexpr (STRIDE > 1) bitonic_net<N, SIZE, STRIDE / 2>(v);
-        else bitonic_net<N, SIZE * 2, SIZE>(v);
-    }
 }
 
 // tier 0 and classification: one lane per cell.  Empty cells get nodata; buckets of up to TIER0_MAX keys are sorted by a bitonic
@@ -536,8 +505,6 @@ void dsm_cells_radix(const unsigned* __restrict__ offs, const unsigned* __restri
 constexpr int RENDER_TILE = 16;                      // 16 x 16 pixels per workgroup: each wave covers 16 columns x 4 rows
 constexpr int RENDER_MAX_STEPS = 4096, RENDER_MAX_BISECT = 60;
 constexpr unsigned RENDER_MAX_BLOCKS = 1u << 20;     // grid-stride over tiles beyond this
-
-__device__ __forceinline__ bool dsm_cell_valid(float z, float nodata) { return isfinite(z) && z != nodata; }
 
 // S(E, N): bilinear over the cells floor(u) .. floor(u)+1 x floor(v) .. floor(v)+1, written as three lerps so that a flat patch
 // gives its height exactly.  False where one of the four is off the grid, non-finite or nodata (never extrapolated).
@@ -731,8 +698,6 @@ void dsm_ortho_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, fl
 // ---- workspace layout --------------------------------------------------------------------------------------------------------
 struct DsmWs { size_t offs, cursor, keys, alt, tiles, lcount, list1, list2, bytes; };
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static DsmWs dsm_ws(size_t n, size_t ncells)
 {
     DsmWs w;
@@ -749,20 +714,6 @@ static DsmWs dsm_ws(size_t n, size_t ncells)
     w.list2 = o;  o += align256(l2 * 4);
     w.bytes = o;
     return w;
-}
-
-static int check_launch_dsm(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
-    return SMVS_OK;
-}
-
-static const char* grid_check(int gw, int gh)
-{
-    if (gw < 1 || gh < 1) return "non-positive grid size";
-    if ((long long)gw * gh >= (1ll << 31)) return "grid too large: gw * gh must be below 2^31 cells";
-    return nullptr;
 }
 
 }  // namespace smvs

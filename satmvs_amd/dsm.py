@@ -4,6 +4,11 @@
     dsm = heights_to_dsm(heights, rpcs, proj, grid)            # (gh, gw) float32, nodata where no point fell
     write_dsm("out.tif", dsm, grid)                            # float32 TIFF + world file (.tfw)
 
+and its clean-up, before the DSM is rendered or carries an orthophoto (both out of place, reading the input grid only):
+
+    dsm = despike(dsm, radius=2, thresh=10.0, min_valid=3)     # cells far from their window's median, or nearly alone -> nodata
+    dsm = fill_voids(dsm, max_steps=32, min_hits=3)            # voids seen from >= 3 of 8 directions <- inverse-distance mean
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -20,6 +25,8 @@ The hot path is native (include/satmvs.h, smvs_rpc_dsm_bin / smvs_dsm_reduce): o
 the inverse RPC and the Transverse Mercator forward into a cell; the reduce sorts every cell's heights and takes the median /
 mean / min / max.  The result is bit-identical from run to run and under any order of the maps.
 smvs_rpc_dsm_render marches every pixel's ray down through the bilinear DSM surface and bisects the first crossing.
+smvs_dsm_despike takes the median of every cell's window with a sorting network in registers over a tile staged in LDS;
+smvs_dsm_fill finds the eight directional hits of every void cell as states carried along columns, diagonals and rows.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -268,6 +275,95 @@ def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999
         _lib.call("smvs_rpc_dsm_render", _lib.ptr(z), grid.width, grid.height, _vp(grid4), float(nodata), _vp(tm7), _lib.ptr(r),
                   H, W, x0, y0, h_lo, h_hi, tol, _lib.ptr(out), _lib.current_stream(dev))
     return out.cpu().numpy() if as_numpy else out
+
+
+# ---- clean-up: speckle removal and void filling ---------------------------------------------------------------------------------
+FILL_METHODS = {"idw": 0, "nearest": 1, "min": 2}
+MAX_FILL_STEPS = 4096
+
+
+def _int_checked(v, name, lo, hi):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+def _grid_checked(dsm):
+    """A (gh, gw) float32 grid, numpy or tensor, checked before any device work: no conversion of other dtypes, the
+    operations copy bits."""
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm)
+    if dsm.ndim != 2:
+        raise ValueError("a DSM is (gh, gw), got shape %s" % (tuple(dsm.shape),))
+    if dsm.dtype not in (np.float32, torch.float32):
+        raise ValueError("a DSM is float32, got %s" % (dsm.dtype,))
+    gh, gw = int(dsm.shape[0]), int(dsm.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("a DSM has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    return dsm
+
+
+def _grid_on_device(dsm):
+    """(contiguous device tensor, whether the caller gave numpy)."""
+    as_numpy = not isinstance(dsm, torch.Tensor)
+    dev = _dev() if as_numpy or not dsm.is_cuda else dsm.device
+    z = (torch.from_numpy(np.ascontiguousarray(dsm)) if as_numpy else dsm).to(device=dev).contiguous()
+    return z, as_numpy
+
+
+def despike(dsm, nodata=-999.0, radius=2, thresh=10.0, min_valid=3, return_removed=False):
+    """Remove speckles from a DSM (include/satmvs.h smvs_dsm_despike): a valid cell becomes `nodata` where
+    the (2 radius + 1)^2 window around it (clipped at the border, the cell included) holds fewer than min_valid valid cells, or
+    where the cell lies more than thresh [m] from the window's median; every other cell is copied bit for bit.  dsm (gh, gw)
+    float32, numpy or a device tensor, left untouched; radius 1, 2 or 3; thresh finite and >= 0; 1 <= min_valid <= window size.
+    -> the cleaned (gh, gw) float32 (and, with return_removed, a uint8 map of the removed cells); numpy if the DSM came as numpy,
+    device tensors otherwise."""
+    dsm = _grid_checked(dsm)
+    radius = _int_checked(radius, "radius", 1, 3)
+    min_valid = _int_checked(min_valid, "min_valid", 1, (2 * radius + 1) ** 2)
+    thresh = float(thresh)
+    if not (math.isfinite(thresh) and thresh >= 0.0):
+        raise ValueError("thresh must be finite and >= 0, got %r" % thresh)
+    z, as_numpy = _grid_on_device(dsm)
+    gh, gw = z.shape
+    out = torch.empty_like(z)
+    removed = torch.empty((gh, gw), dtype=torch.uint8, device=z.device) if return_removed else None
+    with torch.cuda.device(z.device):
+        _lib.call("smvs_dsm_despike", _lib.ptr(z), gw, gh, float(nodata), radius, thresh, min_valid, _lib.ptr(out),
+                  _lib.ptr(removed) if removed is not None else None, _lib.current_stream(z.device))
+    if as_numpy:
+        out, removed = out.cpu().numpy(), removed.cpu().numpy() if removed is not None else None
+    return (out, removed) if return_removed else out
+
+
+def fill_voids(dsm, nodata=-999.0, max_steps=32, min_hits=3, method="idw", return_hits=False):
+    """Fill the voids of a DSM (include/satmvs.h smvs_dsm_fill): every invalid cell looks E, NE, N, NW, W,
+    SW, S, SE for the first valid cell within max_steps cells; with at least min_hits such hits it takes their inverse-distance
+    mean ("idw", float64, weights 1 / distance^2), the nearest of them ("nearest") or the lowest ("min", the ground-side fill for
+    occlusion shadows beside buildings); ties keep the earlier direction.  Cells with fewer hits stay as they are, valid cells
+    are copied bit for bit, and only the input is read, so filled cells never feed other cells.  dsm (gh, gw) float32, numpy or
+    a device tensor, left untouched; 1 <= max_steps <= 4096; 1 <= min_hits <= 8.
+    -> the filled (gh, gw) float32 (and, with return_hits, a uint8 map: 255 where the input cell was valid, else its number of
+    hits); numpy if the DSM came as numpy, device tensors otherwise."""
+    dsm = _grid_checked(dsm)
+    if method not in FILL_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(FILL_METHODS), method))
+    max_steps = _int_checked(max_steps, "max_steps", 1, MAX_FILL_STEPS)
+    min_hits = _int_checked(min_hits, "min_hits", 1, 8)
+    z, as_numpy = _grid_on_device(dsm)
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_fill_workspace_bytes(gw, gh, max_steps)
+    if nbytes == 0:
+        raise ValueError("unsupported fill: %d x %d cells, max_steps %d" % (gw, gh, max_steps))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    out = torch.empty_like(z)
+    hits = torch.empty((gh, gw), dtype=torch.uint8, device=z.device) if return_hits else None
+    with torch.cuda.device(z.device):
+        _lib.call("smvs_dsm_fill", _lib.ptr(z), gw, gh, float(nodata), max_steps, min_hits, FILL_METHODS[method], _lib.ptr(out),
+                  _lib.ptr(hits) if hits is not None else None, _lib.ptr(ws), nbytes, _lib.current_stream(z.device))
+    if as_numpy:
+        out, hits = out.cpu().numpy(), hits.cpu().numpy() if hits is not None else None
+    return (out, hits) if return_hits else out
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
