@@ -582,7 +582,29 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   method 1 (nearest) z_d of the smallest d2; method 2 (min) the lowest z_d; ties keep the earlier direction.
  *   hits (gh, gw) uint8 or null: 255 where the input cell was valid, else the number of hits.
  *   1 <= max_steps <= 4096, 1 <= min_hits <= 8; workspace: smvs_dsm_fill_workspace_bytes(gw, gh, max_steps) bytes (0 =
- *   unsupported arguments), distinct from the other buffers. */
+ *   unsupported arguments), distinct from the other buffers.
+ *
+ * Ground extraction (csrc/dsm_morph.hip).  dsm (gh, gw) float32 (device), read only; a cell is valid iff it is finite and
+ * != nodata, as above.  Values are ordered by their keys (a float's bits, complemented if negative, else with the sign bit
+ * set): the order of <, with -0.0 below +0.0, so "lowest" and "highest" name one bit pattern.
+ *   Window of a cell = the (2 r + 1)^2 square around it clipped at the grid border.  A field F is a value or "none" per cell
+ *   (the field of a grid: its valid cells).  erode(F, r)(p) = the lowest value of F in p's window, dilate(F, r)(p) = the
+ *   highest, "none" iff the window holds no value: cells without a value are transparent, and the result is defined at every
+ *   cell whose window holds one, valid in the grid or not.  open(F, r) = dilate(erode(F, r), r), close(F, r) =
+ *   erode(dilate(F, r), r).  Clipped windows are symmetric (q in p's window iff p in q's), so open(F, r)(p) <= F(p) <=
+ *   close(F, r)(p) wherever F has a value.
+ * smvs_dsm_morph: op 0 erode, 1 dilate, 2 open, 3 close of the grid's field with radius r; out (gh, gw) float32 gets the
+ *   result at valid cells (it is defined there: a valid cell is in its own window) and the input's bits at invalid cells.
+ * smvs_dsm_ground: the progressive morphological filter over n_levels windows.  radii (int) and thresholds (double) are HOST
+ *   arrays of n_levels entries.  S_0 = the grid's field, every valid cell classed ground.  For k = 0 .. n_levels - 1:
+ *   O_k = open(S_k, radii[k]); a valid cell still classed ground with (double)S_k(p) - (double)O_k(p) > thresholds[k] is
+ *   classed removed at level k; S_(k+1) = O_k at the valid cells, none elsewhere.  cls (gh, gw) uint8: 0 invalid input cell,
+ *   1 ground, 2 + k removed at level k.  dtm (gh, gw) float32: the input's bits at ground and at invalid cells, nodata at
+ *   removed cells.  The levels run on the stream without host synchronisation.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): 1 <= radius, radii[k] <= 256, radii strictly increasing,
+ *   1 <= n_levels <= 16, thresholds finite and >= 0, gw * gh < 2^31; out / dtm / cls / workspace distinct from dsm and from
+ *   each other; workspace: smvs_dsm_morph_workspace_bytes(gw, gh, the largest radius) bytes (0 = unsupported arguments).
+ *   No atomics, every value a selection: bit-identical from run to run and to the numpy statement of these rules. */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -602,6 +624,11 @@ int smvs_dsm_despike(const float* dsm, int gw, int gh, float nodata, int radius,
 size_t smvs_dsm_fill_workspace_bytes(int gw, int gh, int max_steps);
 int smvs_dsm_fill(const float* dsm, int gw, int gh, float nodata, int max_steps, int min_hits, int method,
                   float* out, unsigned char* hits, void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_morph_workspace_bytes(int gw, int gh, int max_radius);
+int smvs_dsm_morph(const float* dsm, int gw, int gh, float nodata, int radius, int op, float* out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_ground(const float* dsm, int gw, int gh, float nodata, const int* radii, const double* thresholds, int n_levels,
+                    float* dtm, unsigned char* cls, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -82,13 +82,16 @@ _SIGNATURES = {
     "smvs_rpc_ortho": [_vp, _i, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i, _vp, _vp, _vp, _vp],
     "smvs_dsm_despike": [_vp, _i, _i, _f, _i, C.c_double, _i, _vp, _vp, _vp],
     "smvs_dsm_fill": [_vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_morph": [_vp, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp],
+    "smvs_dsm_ground": [_vp, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
 }
 _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": [_i], "smvs_red_workspace_bytes": [_i] * 4,
                "smvs_red_pred_workspace_bytes": [_i] * 4, "smvs_costreg_packed_floats": [_i],
                "smvs_costreg_workspace_bytes": [_i] * 5, "smvs_featnet_packed_floats": [_i] * 2,
                "smvs_featnet_workspace_bytes": [_i] * 5, "smvs_conv3x3_packed_floats": [_i] * 2,
                "smvs_conv3d_packed_floats": [_i] * 2, "smvs_conv3d_wgrad_workspace_floats": [_i] * 6,
-               "smvs_dsm_workspace_bytes": [_sz, _i, _i], "smvs_dsm_fill_workspace_bytes": [_i] * 3}
+               "smvs_dsm_workspace_bytes": [_sz, _i, _i], "smvs_dsm_fill_workspace_bytes": [_i] * 3,
+               "smvs_dsm_morph_workspace_bytes": [_i] * 3}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",
                                                                     "smvs_set_arith", "smvs_get_arith"])
 ARITH_MODES = {"exact": 0, "fused": 1}      # SMVS_ARITH_EXACT / SMVS_ARITH_FUSED of include/satmvs.h

@@ -1,7 +1,8 @@
-// dsm_common.h -- what the DSM sources (dsm.hip, dsm_post.hip) share: the validity test of a cell, the order-preserving
-// uint32 image of a float, the register sorting network, and the host-side grid and launch checks.
+// dsm_common.h -- what the DSM sources (dsm.hip, dsm_post.hip, dsm_morph.hip) share: the validity test of a cell, the
+// order-preserving uint32 image of a float, the register sorting network, and the host-side grid, aliasing and launch checks.
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #include "smvs_host.h"
 
@@ -49,6 +50,13 @@ static int check_launch_dsm(const char* what)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
     return SMVS_OK;
+}
+
+// Whether two buffers share a byte (the out-of-place entries reject aliased arguments).
+static bool dsm_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
 }
 
 static const char* grid_check(int gw, int gh)

@@ -227,12 +227,6 @@ void dsm_fill_combine(const float* __restrict__ in, int gw, int gh, float nodata
 // the bands fit the launch grid.
 static int fill_band(int gh, int max_steps) { return std::max({FILL_MIN_BAND, max_steps, (gh + 65534) / 65535}); }
 
-static bool overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 }  // namespace smvs
 
 extern "C" {
@@ -248,8 +242,8 @@ SMVS_EXPORT int smvs_dsm_despike(const float* dsm, int gw, int gh, float nodata,
     const int window = (2 * radius + 1) * (2 * radius + 1);
     if (min_valid < 1 || min_valid > window) return fail(SMVS_ERR_ARG, "min_valid must be in 1 .. %d (the window of radius %d)", window, radius);
     const size_t ncells = (size_t)gw * gh;
-    if (overlap(dsm, ncells * 4, out, ncells * 4)) return fail(SMVS_ERR_ARG, "out aliases dsm: the operation is out of place");
-    if (removed && (overlap(dsm, ncells * 4, removed, ncells) || overlap(out, ncells * 4, removed, ncells)))
+    if (dsm_overlap(dsm, ncells * 4, out, ncells * 4)) return fail(SMVS_ERR_ARG, "out aliases dsm: the operation is out of place");
+    if (removed && (dsm_overlap(dsm, ncells * 4, removed, ncells) || dsm_overlap(out, ncells * 4, removed, ncells)))
         return fail(SMVS_ERR_ARG, "removed aliases dsm or out");
     const unsigned ntiles = (unsigned)((gw + SPIKE_TW - 1) / SPIKE_TW) * (unsigned)((gh + SPIKE_TH - 1) / SPIKE_TH);
     const dim3 grid(std::min(ntiles, POST_MAX_BLOCKS)), block(SPIKE_THREADS);
@@ -277,12 +271,12 @@ SMVS_EXPORT int smvs_dsm_fill(const float* dsm, int gw, int gh, float nodata, in
     if (min_hits < 1 || min_hits > 8) return fail(SMVS_ERR_ARG, "min_hits must be in 1 .. 8");
     if (method < 0 || method > 2) return fail(SMVS_ERR_ARG, "method must be 0 (idw), 1 (nearest) or 2 (min)");
     const size_t ncells = (size_t)gw * gh;
-    if (overlap(dsm, ncells * 4, out, ncells * 4)) return fail(SMVS_ERR_ARG, "out aliases dsm: the operation is out of place");
-    if (hits && (overlap(dsm, ncells * 4, hits, ncells) || overlap(out, ncells * 4, hits, ncells)))
+    if (dsm_overlap(dsm, ncells * 4, out, ncells * 4)) return fail(SMVS_ERR_ARG, "out aliases dsm: the operation is out of place");
+    if (hits && (dsm_overlap(dsm, ncells * 4, hits, ncells) || dsm_overlap(out, ncells * 4, hits, ncells)))
         return fail(SMVS_ERR_ARG, "hits aliases dsm or out");
     const size_t need = smvs_dsm_fill_workspace_bytes(gw, gh, max_steps);
     if (workspace_bytes < need) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    if (overlap(dsm, ncells * 4, workspace, need) || overlap(out, ncells * 4, workspace, need) || (hits && overlap(hits, ncells, workspace, need)))
+    if (dsm_overlap(dsm, ncells * 4, workspace, need) || dsm_overlap(out, ncells * 4, workspace, need) || (hits && dsm_overlap(hits, ncells, workspace, need)))
         return fail(SMVS_ERR_ARG, "workspace aliases dsm, out or hits");
     hipStream_t s = (hipStream_t)stream;
     unsigned short* planes = (unsigned short*)workspace;

@@ -9,6 +9,12 @@ and its clean-up, before the DSM is rendered or carries an orthophoto (both out 
     dsm = despike(dsm, radius=2, thresh=10.0, min_valid=3)     # cells far from their window's median, or nearly alone -> nodata
     dsm = fill_voids(dsm, max_steps=32, min_hits=3)            # voids seen from >= 3 of 8 directions <- inverse-distance mean
 
+and the split into terrain and what stands on it (progressive morphological filter, then the same void filling):
+
+    dtm = extract_dtm(dsm, grid, max_radius=16)                # bare ground: buildings and trees removed and interpolated over
+    above = ndsm(dsm, dtm)                                     # heights above ground, >= 0; nodata where either has none
+    opened = morph(dsm, radius=8, op="open")                   # the building block: erode / dilate / open / close
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -27,6 +33,8 @@ mean / min / max.  The result is bit-identical from run to run and under any ord
 smvs_rpc_dsm_render marches every pixel's ray down through the bilinear DSM surface and bisects the first crossing.
 smvs_dsm_despike takes the median of every cell's window with a sorting network in registers over a tile staged in LDS;
 smvs_dsm_fill finds the eight directional hits of every void cell as states carried along columns, diagonals and rows.
+smvs_dsm_morph / smvs_dsm_ground take window minima and maxima as row and column passes over order-preserving keys, each a
+doubling in LDS whose cost does not grow with the radius but with its logarithm.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -364,6 +372,135 @@ def fill_voids(dsm, nodata=-999.0, max_steps=32, min_hits=3, method="idw", retur
     if as_numpy:
         out, hits = out.cpu().numpy(), hits.cpu().numpy() if hits is not None else None
     return (out, hits) if return_hits else out
+
+
+# ---- ground extraction: morphology, the progressive morphological filter, DTM and nDSM ------------------------------------------
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}
+MAX_MORPH_RADIUS = 256
+MAX_GROUND_LEVELS = 16
+GROUND_CLASSES = ("invalid", "ground")                            # 0, 1; 2 + k = removed at level k of the schedule
+
+
+def _morph_workspace(z, max_radius):
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_morph_workspace_bytes(gw, gh, max_radius)
+    if nbytes == 0:
+        raise ValueError("unsupported morphology: %d x %d cells, radius %d" % (gw, gh, max_radius))
+    return torch.empty(nbytes, dtype=torch.uint8, device=z.device), nbytes
+
+
+def morph(dsm, radius, op, nodata=-999.0):
+    """Grey-scale morphology with a (2 radius + 1)^2 square clipped at the grid border (include/satmvs.h smvs_dsm_morph,
+    DESIGN.md section 9): op "erode" = the lowest valid cell of the window, "dilate" = the highest, "open" = the dilation of
+    the erosion, "close" = the erosion of the dilation.  Invalid cells are transparent to the windows and are copied bit for
+    bit; of two zeros -0.0 is the lower.  dsm (gh, gw) float32, numpy or a device tensor, left untouched; 1 <= radius <= 256.
+    -> (gh, gw) float32; numpy if the DSM came as numpy, a device tensor otherwise."""
+    dsm = _grid_checked(dsm)
+    radius = _int_checked(radius, "radius", 1, MAX_MORPH_RADIUS)
+    if op not in MORPH_OPS:
+        raise ValueError("op must be one of %s, got %r" % (sorted(MORPH_OPS), op))
+    z, as_numpy = _grid_on_device(dsm)
+    gh, gw = z.shape
+    ws, nbytes = _morph_workspace(z, radius)
+    out = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _lib.call("smvs_dsm_morph", _lib.ptr(z), gw, gh, float(nodata), radius, MORPH_OPS[op], _lib.ptr(out), _lib.ptr(ws), nbytes,
+                  _lib.current_stream(z.device))
+    return out.cpu().numpy() if as_numpy else out
+
+
+def ground_schedule(cell, max_radius=16, slope=0.3, dh0=1.5, dh_max=6.0):
+    """The window radii [cells] and height thresholds [m] of the progressive morphological filter (Zhang et al. 2003): radii
+    1, 2, 4, ... below max_radius, then max_radius; w_k = 2 r_k + 1; t_0 = dh0, t_k = min(dh_max, slope (w_k - w_(k-1)) cell +
+    dh0), in float64.  cell [m] > 0; slope [m/m], dh0, dh_max [m] finite and >= 0.  -> (list of int, list of float)."""
+    max_radius = _int_checked(max_radius, "max_radius", 1, MAX_MORPH_RADIUS)
+    cell, slope, dh0, dh_max = float(cell), float(slope), float(dh0), float(dh_max)
+    if not (math.isfinite(cell) and cell > 0.0):
+        raise ValueError("cell must be positive and finite, got %r" % cell)
+    for name, v in (("slope", slope), ("dh0", dh0), ("dh_max", dh_max)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError("%s must be finite and >= 0, got %r" % (name, v))
+    radii, r = [], 1
+    while r < max_radius:
+        radii.append(r)
+        r *= 2
+    radii.append(max_radius)
+    thresholds = [dh0]
+    for k in range(1, len(radii)):
+        thresholds.append(min(dh_max, slope * float((2 * radii[k] + 1) - (2 * radii[k - 1] + 1)) * cell + dh0))
+    return radii, thresholds
+
+
+def _schedule_checked(radii, thresholds):
+    radii, thresholds = list(radii), [float(t) for t in thresholds]
+    if not 1 <= len(radii) <= MAX_GROUND_LEVELS or len(thresholds) != len(radii):
+        raise ValueError("a schedule has 1 .. %d radii and as many thresholds, got %d and %d" % (MAX_GROUND_LEVELS, len(radii), len(thresholds)))
+    radii = [_int_checked(r, "radius", 1, MAX_MORPH_RADIUS) for r in radii]
+    if any(b <= a for a, b in zip(radii, radii[1:])):
+        raise ValueError("radii must be strictly increasing, got %r" % (radii,))
+    if not all(math.isfinite(t) and t >= 0.0 for t in thresholds):
+        raise ValueError("thresholds must be finite and >= 0, got %r" % (thresholds,))
+    return radii, thresholds
+
+
+def ground_filter(dsm, cell=None, nodata=-999.0, max_radius=16, slope=0.3, dh0=1.5, dh_max=6.0, return_class=False, schedule=None):
+    """The progressive morphological ground filter (include/satmvs.h smvs_dsm_ground): the surface is
+    opened with the growing windows of ground_schedule(cell, max_radius, slope, dh0, dh_max); a valid cell that level k's
+    opening lowers by more than t_k is removed at level k, and the next level works on the opened surface.  cell: the cell
+    size [m].  schedule = (radii, thresholds) replaces the schedule of the parameters (cell is not needed then).  The defaults
+    are a choice for 5 m grids, not tuned on real data.  dsm (gh, gw) float32, numpy or a device tensor, left
+    untouched.
+    -> dtm (gh, gw) float32: the input's bits at ground cells, nodata at removed cells, invalid cells copied (and, with
+    return_class, cls uint8: 0 invalid input, 1 ground, 2 + k removed at level k); numpy if the DSM came as numpy."""
+    dsm = _grid_checked(dsm)
+    if schedule is not None:
+        radii, thresholds = _schedule_checked(*schedule)
+    else:
+        if cell is None:
+            raise ValueError("ground_filter needs the cell size [m] (or a schedule)")
+        radii, thresholds = ground_schedule(cell, max_radius, slope, dh0, dh_max)
+    z, as_numpy = _grid_on_device(dsm)
+    gh, gw = z.shape
+    ws, nbytes = _morph_workspace(z, radii[-1])
+    dtm = torch.empty_like(z)
+    cls = torch.empty((gh, gw), dtype=torch.uint8, device=z.device)
+    r_arr, t_arr = np.asarray(radii, np.int32), np.asarray(thresholds, np.float64)
+    with torch.cuda.device(z.device):
+        _lib.call("smvs_dsm_ground", _lib.ptr(z), gw, gh, float(nodata), _vp(r_arr), _vp(t_arr), len(radii), _lib.ptr(dtm), _lib.ptr(cls),
+                  _lib.ptr(ws), nbytes, _lib.current_stream(z.device))
+    if as_numpy:
+        dtm, cls = dtm.cpu().numpy(), cls.cpu().numpy()
+    return (dtm, cls) if return_class else dtm
+
+
+def extract_dtm(dsm, grid, nodata=-999.0, max_radius=16, slope=0.3, dh0=1.5, dh_max=6.0, max_steps=256, min_hits=3, return_class=False):
+    """A DTM from a DSM: ground_filter with cell = max(grid.xres, grid.yres), then fill_voids(method="idw") under what was
+    removed.  The fill also closes voids the input already had within max_steps cells, which is what a DTM wants; voids out of
+    reach stay.  -> dtm (gh, gw) float32 (and the filter's cls with return_class)."""
+    if tuple(dsm.shape) != (grid.height, grid.width):
+        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
+    max_steps = _int_checked(max_steps, "max_steps", 1, MAX_FILL_STEPS)
+    min_hits = _int_checked(min_hits, "min_hits", 1, 8)
+    holes, cls = ground_filter(dsm, max(float(grid.xres), float(grid.yres)), nodata, max_radius, slope, dh0, dh_max, return_class=True)
+    dtm = fill_voids(holes, nodata=nodata, max_steps=max_steps, min_hits=min_hits, method="idw")
+    return (dtm, cls) if return_class else dtm
+
+
+def ndsm(dsm, dtm, nodata=-999.0, clamp=True):
+    """Heights above ground: float32 dsm - dtm where both are valid (one IEEE operation), max(., 0) with clamp, nodata
+    elsewhere.  Torch operators on whatever device the inputs are on (numpy in, numpy out)."""
+    as_numpy = not isinstance(dsm, torch.Tensor)
+    a = torch.as_tensor(np.asarray(dsm) if as_numpy else dsm)
+    b = torch.as_tensor(np.asarray(dtm) if not isinstance(dtm, torch.Tensor) else dtm).to(a.device)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("ndsm takes two float32 grids of one shape, got %s %s and %s %s" % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    nd = float(np.float32(nodata))
+    both = torch.isfinite(a) & (a != nd) & torch.isfinite(b) & (b != nd)
+    d = a - b
+    if clamp:
+        d = torch.where(d > 0.0, d, torch.zeros_like(d))                  # every zero leaves as +0.0
+    out = torch.where(both, d, torch.full_like(d, nd))
+    return out.cpu().numpy() if as_numpy else out
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
