@@ -19,7 +19,11 @@ namespace smvs {
 __device__ __forceinline__ float remap_linear_const(const float* __restrict__ img, int H, int W, float fx, float fy, float border)
 {
     // cv::remap, INTER_LINEAR on CV_32F: fixed-point coordinates with INTER_BITS = 5
-    const int sx = __float2int_rn(fx * 32.0f), sy = __float2int_rn(fy * 32.0f);
+    const float px = fx * 32.0f, py = fy * 32.0f;
+    // cvRound of a NaN or of a value beyond the integer range is the most negative integer on the reference's hosts: all
+    // four taps fall outside and the weights sum to one.  __float2int_rn alone turns NaN into 0, i.e. into source pixel (0, 0).
+    if (!(fabsf(px) < 2147483648.0f && fabsf(py) < 2147483648.0f)) return border;
+    const int sx = __float2int_rn(px), sy = __float2int_rn(py);
     const int ix = sx >> 5, iy = sy >> 5;
     const float ax = (float)(sx & 31) * (1.0f / 32.0f), ay = (float)(sy & 31) * (1.0f / 32.0f);
     auto at = [&](int y, int x) { return (x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : border; };

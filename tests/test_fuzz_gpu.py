@@ -54,3 +54,10 @@ def test_fuzz_training_operators_3d_vs_float64():
     """smvs_conv3d_fwd / its adjoint / smvs_conv3d_wgrad and smvs_batchnorm_train_* on random layers against float64 (round 5)."""
     last = _run("fuzz_train3d.py", 60, 14)
     assert last.startswith("60 cases, worst relative error"), last
+
+
+def test_fuzz_consistency_filters_vs_oracle():
+    """smvs_rpc_geo_consistency / smvs_pinhole_geo_consistency on random reference and source sizes, geometries, thresholds and
+    shares of NaN / border-valued / blunder pixels: every stage and end to end (tests/filter_scene.py)."""
+    last = _run("fuzz_filter.py", 20, 16)
+    assert last.startswith("20 rounds, 0 mismatching checks"), last
