@@ -287,8 +287,7 @@ ORC_API int orc_homo_compose(const double *src_proj, const double *ref_proj, dou
     return 0;
 }
 
-static inline void homo_chain(const double *P /* composed 4x4 */, int x, int y, double depth,
-                              int H, int W, float *gx, float *gy)
+static inline void homo_uv(const double *P /* composed 4x4 */, int x, int y, double depth, double *u_out, double *v_out)
 {
     /* warping.py:28-38: rot @ (x,y,1) * depth + trans, perspective divide and normalisation all in
      * float64, cast to float32 at the end. */
@@ -299,7 +298,15 @@ static inline void homo_chain(const double *P /* composed 4x4 */, int x, int y, 
     double X = rx * depth + P[3];
     double Y = ry * depth + P[7];
     double Z = rz * depth + P[11];
-    double u = X / Z, v = Y / Z;
+    *u_out = X / Z;
+    *v_out = Y / Z;
+}
+
+static inline void homo_chain(const double *P /* composed 4x4 */, int x, int y, double depth,
+                              int H, int W, float *gx, float *gy)
+{
+    double u, v;
+    homo_uv(P, x, y, depth, &u, &v);
     *gx = (float)(u / ((W - 1) / 2.0) - 1.0);
     *gy = (float)(v / ((H - 1) / 2.0) - 1.0);
 }
@@ -321,6 +328,23 @@ static inline tap_t make_tap_norm(float gx, float gy, int H, int W)
     t.y0 = (yin0 || yin1) ? (int)yn : 0;
     t.m_nw = xin0 && yin0; t.m_ne = xin1 && yin0; t.m_sw = xin0 && yin1; t.m_se = xin1 && yin1;
     return t;
+}
+
+/* Projection-only variant of the pinhole chain: the float32 normalised grid coordinates fed to the sampler and the float64
+ * source pixel coordinates (u, v) they are made of, (B,D,H,W) each -- the counterpart of orc_rpc_warp_coords, for tests
+ * that tie a differing voxel to its coordinate. */
+ORC_API void orc_homo_warp_coords(const double *proj, const float *depth, int depth_is_4d, float *gx, float *gy,
+                                  double *u, double *v, int B, int D, int H, int W)
+{
+    for (int b = 0; b < B; ++b)
+        for (int d = 0; d < D; ++d)
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) {
+                    size_t i = (((size_t)b * D + d) * H + y) * W + x;
+                    double h = height_at(depth, depth_is_4d, b, d, y, x, D, H, W);
+                    homo_chain(proj + (size_t)b * 16, x, y, h, H, W, &gx[i], &gy[i]);
+                    homo_uv(proj + (size_t)b * 16, x, y, h, &u[i], &v[i]);
+                }
 }
 
 /* homo_warping with the composed matrix `proj` (B,4,4) = src_proj @ inv(ref_proj). */

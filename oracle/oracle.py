@@ -110,6 +110,19 @@ def homo_compose(src_proj, ref_proj):
     return out
 
 
+def homo_warp_coords(src_proj, ref_proj, depth, H, W, pixels=False):
+    """The float32 normalised grid (gx, gy), each (B,D,H,W), that homo_warping samples at -- orc_homo_warp_coords; with
+    `pixels` also the float64 source pixel coordinates (u, v) it is made of."""
+    proj = homo_compose(src_proj, ref_proj)
+    B = proj.shape[0]
+    D = depth.shape[1]
+    depth, is4 = _depth_args(depth, B, D, H, W)
+    gx, gy = np.empty((B, D, H, W), np.float32), np.empty((B, D, H, W), np.float32)
+    u, v = np.empty((B, D, H, W), np.float64), np.empty((B, D, H, W), np.float64)
+    lib().orc_homo_warp_coords(_p(proj), _p(depth), is4, _p(gx), _p(gy), _p(u), _p(v), B, D, H, W)
+    return (gx, gy, u, v) if pixels else (gx, gy)
+
+
 def homo_warping(src_fea, src_proj, ref_proj, depth):
     src_fea = _f32(src_fea)
     B, Cc, H, W = src_fea.shape

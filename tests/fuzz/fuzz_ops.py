@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Random shapes through the smaller operators of the path against the CPU oracle: rpc_warping / homo_warping (bits), softmax and
-window regressions, streaming regression, in-kernel height hypotheses (bits).   python tests/fuzz/fuzz_ops.py [n] [seed]"""
+"""Random shapes through the smaller operators of the path against the CPU oracle: rpc_warping / homo_warping (bits; a differing voxel
+must be explained by its float32 coordinate, tests/ops_scene.py::explain_warp) and their backwards (float64 scatter, float32 summation
+bound), softmax and window regressions, streaming regression, in-kernel height hypotheses (bits).   python tests/fuzz/fuzz_ops.py [n] [seed]"""
 import os, sys
 import numpy as np
 import torch
@@ -10,7 +11,7 @@ from oracle import oracle as orc
 from satmvs_amd.modules import module as M
 from satmvs_amd.modules import warping
 from satmvs_amd.modules.depth_range import GeneratedHeights
-import test_hip_parity as T
+import ops_scene as osn
 
 orc.build()
 dev = torch.device("cuda:0")
@@ -19,20 +20,34 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 bad = 0
 for it in range(n):
-    C = int(rng.integers(1, 20)); D = int(rng.integers(1, 18)); H = int(rng.integers(3, 90)); W = int(rng.integers(3, 150)); B = int(rng.integers(1, 3))
+    C = int(rng.integers(1, 41)); D = int(rng.integers(1, 81)); H = int(rng.integers(1, 90)); W = int(rng.integers(1, 150)); B = int(rng.integers(1, 4))
+    while C > 1 and B * C * D * H * W > 1.5e6:                   # the float64 references run on the CPU: thin the channels of the large draws
+        C = max(1, C // 2)
     jitter = bool(rng.random() < 0.6)
-    # ---- warps (bit comparison)
+    # ---- warps: forward (bits, every difference explained) and backward (float64 scatter of the oracle's taps)
     for geo in ("rpc", "pinhole"):
-        feats, gp, depth = T._inputs(B, 2, C, D, H, W, seed=int(rng.integers(0, 10000)), jitter=jitter, geo=geo)
+        seed = int(rng.integers(0, 10000))
+        fea, src, ref, depth = osn.scene(geo, B, C, D, H, W, seed=seed, per_pixel=jitter)
+        f = t(fea).requires_grad_(True)
         if geo == "rpc":
-            got = warping.rpc_warping(t(feats[1]), t(gp[:, 1]), t(gp[:, 0]), t(depth), None).cpu().numpy()
-            want = orc.rpc_warping(feats[1], gp[:, 1], gp[:, 0], depth)
+            out = warping.rpc_warping(f, t(src), t(ref), t(depth), None)
+            want = orc.rpc_warping(fea, src, ref, depth)
         else:
-            got = warping.homo_warping(t(feats[1]), t(gp[:, 1]), t(gp[:, 0]), t(depth)).cpu().numpy()
-            want = orc.homo_warping(feats[1], gp[:, 1], gp[:, 0], depth)
-        nb = int((got != want).sum())
-        if nb > max(1, 1e-4 * got.size):
-            bad += 1; print("MISMATCH warp %s it=%d B=%d C=%d D=%d H=%d W=%d jitter=%s: %d of %d" % (geo, it, B, C, D, H, W, jitter, nb, got.size))
+            out = warping.homo_warping(f, t(src), t(ref), t(depth))
+            want = orc.homo_warping(fea, src, ref, depth)
+        got = out.detach().cpu().numpy()
+        msgs, nb = osn.explain_warp(orc, geo, got, want, fea, src, ref, depth)
+        if msgs:
+            bad += 1; print("MISMATCH warp %s it=%d B=%d C=%d D=%d H=%d W=%d jitter=%s seed=%d: %s" % (geo, it, B, C, D, H, W, jitter, seed, msgs[0]))
+            continue
+        vox = ((got.view(np.uint32) != want.view(np.uint32)) & ~(np.isnan(got) & np.isnan(want))).any(1)
+        gout = np.random.default_rng(seed).standard_normal(got.shape).astype(np.float32)
+        gout[np.broadcast_to(vox[:, None], gout.shape)] = 0.0    # a voxel whose forward differs has other taps than the oracle's: out of both sides
+        out.backward(t(gout))
+        off, wts = osn.taps_from_grid(*osn.oracle_grid(orc, geo, src, ref, depth, H, W), H, W)
+        msgs, worst, nmax = osn.check_backward(f.grad.cpu().numpy(), gout, off, wts, H, W, "backward")
+        if msgs:
+            bad += 1; print("MISMATCH warp backward %s it=%d B=%d C=%d D=%d H=%d W=%d jitter=%s seed=%d: %s" % (geo, it, B, C, D, H, W, jitter, seed, msgs[0]))
     # ---- regressions
     reg = (rng.standard_normal((B, D, H, W)) * 3).astype(np.float32)
     dvals = depth if depth.ndim == 4 else depth
