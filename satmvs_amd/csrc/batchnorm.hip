@@ -235,9 +235,7 @@ extern "C" SMVS_EXPORT int smvs_batchnorm_train_fwd(const float* x, const float*
     const dim3 grid((unsigned)(a.nchunk * B), (unsigned)C);
     hipLaunchKernelGGL(bn_stats_kernel<false>, grid, dim3(BN_BLOCK), 0, st, a);
     hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(BN_BLOCK), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "batchnorm_train_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("batchnorm_train_fwd");
 }
 
 extern "C" SMVS_EXPORT int smvs_batchnorm_train_bwd(const float* dy, const float* x, const float* gamma, const float* beta,
@@ -258,7 +256,5 @@ extern "C" SMVS_EXPORT int smvs_batchnorm_train_bwd(const float* dy, const float
     const dim3 grid((unsigned)(a.nchunk * B), (unsigned)C);
     hipLaunchKernelGGL(bn_stats_kernel<true>, grid, dim3(BN_BLOCK), 0, st, a);
     hipLaunchKernelGGL(bn_bwd_dx_kernel, grid, dim3(BN_BLOCK), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "batchnorm_train_bwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("batchnorm_train_bwd");
 }

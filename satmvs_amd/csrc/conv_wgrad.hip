@@ -501,9 +501,7 @@ static int wgrad_launch(const float* x, const float* dy, float* dw, float* db, i
     if (units >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
     if (stride == 1) hipLaunchKernelGGL(conv3x3_wgrad_kernel<1>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
     else             hipLaunchKernelGGL(conv3x3_wgrad_kernel<2>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3x3_wgrad launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3x3_wgrad");
 }
 
 extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db,
@@ -621,7 +619,5 @@ extern "C" SMVS_EXPORT int smvs_conv3d_wgrad(const float* window, const float* g
         else             hipLaunchKernelGGL((conv3d_wgrad_kernel<2, 8>), grd, dim3(256), 0, (hipStream_t)stream, p);
     }
     if (workspace) hipLaunchKernelGGL(conv3d_wgrad_fold_kernel, dim3((unsigned)(p.ncp * p.ncog * 3)), dim3(192), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3d_wgrad launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3d_wgrad");
 }

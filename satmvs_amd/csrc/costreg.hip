@@ -528,9 +528,7 @@ SMVS_EXPORT int smvs_costreg_pack_weights(const float* const* params, int C, flo
                            i < 10 ? q[3] : q[0], i < 10 ? q[4] : q[0], packed + lay.scale[i], packed + lay.shift[i],
                            L[i].cout, cp, L[i].bn);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "costreg_pack_weights launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("costreg_pack_weights");
 }
 
 // vol (B,C,D,H,W) variance volume -> out (B,1,D,H,W) regularised cost.  D, H, W multiples of 8.
@@ -566,9 +564,7 @@ SMVS_EXPORT int smvs_costreg_fwd(const float* packed, const float* vol, float* o
         cr_launch_layer(l, s.in, packed + lay.w[s.layer], packed + lay.scale[s.layer], packed + lay.shift[s.layer],
                         cr_use_mfma(l) ? packed + lay.wm[s.layer] : nullptr, s.skip, s.out, B, dims[s.lin], dims[s.lout], st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "costreg_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("costreg_fwd");
 }
 
 // ---- single layers: the TRAINING forward of CostRegNet's convolutions and their input gradients (include/satmvs.h) ----------------------
@@ -594,9 +590,7 @@ SMVS_EXPORT int smvs_conv3d_pack(const float* w, float* packed, int cin, int cou
         const int nm = (int)mfma_packed_floats(cin, cout, 27);
         hipLaunchKernelGGL(mfma_pack_kernel, dim3((nm + 255) / 256), dim3(256), 0, st, w, packed + n + 2 * cp, cin, cout, 27, layout == 2);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3d_pack launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3d_pack");
 }
 
 SMVS_EXPORT int smvs_conv3d_fwd(int kind, const float* in, const float* packed, const float* skip, float* out, int B, int Cin, int Cout,
@@ -620,9 +614,7 @@ SMVS_EXPORT int smvs_conv3d_fwd(int kind, const float* in, const float* packed, 
     const int cp = ncog * CR_COT;
     const bool mf = kind != 2 && mfma_conv_ok(Cin, 0, Cout);
     cr_launch_layer(l, in, packed, packed + n, packed + n + cp, mf ? packed + n + 2 * cp : nullptr, skip, out, B, di, dout, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3d_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3d_fwd");
 }
 
 }  // extern "C"

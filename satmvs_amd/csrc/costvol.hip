@@ -164,9 +164,7 @@ SMVS_EXPORT int smvs_rpc_plane_coef(const double* rpc, const float* depth, int d
     const int n = B * (d_end - d_begin) * n_src * 4;
     hipLaunchKernelGGL(rpc_plane_coef_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, rpc, depth,
                        (depth_is_4d & ~SMVS_CALL_ARITH_MASK) ? 1 : 0, plane_coef, B, n_src, D, (size_t)H * W, d_begin, d_end - d_begin);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "rpc_plane_coef launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("rpc_plane_coef");
 }
 
 SMVS_EXPORT int smvs_rpc_costvol_fwd_pc(const float* ref_fea, const float* const* src_fea, int n_src,

@@ -6,111 +6,19 @@
 //                     -> (E, N) through the TM forward, -> grid cell; counts per cell accumulated with atomics.
 //   smvs_dsm_reduce   exclusive scan of the counts, scatter of the heights into per-cell buckets, sort of every bucket on the
 //                     order-preserving uint32 image of the float, then median / mean / min / max of the sorted bucket.
-//   smvs_rpc_dsm_render  the reverse direction: one lane per pixel of a view marches its ray (x, y, h) down through the
-//                     bilinear surface of a DSM, then bisects the crossing; the first crossing from above is the pixel's height.
-//   smvs_rpc_ortho    the orthophoto: one lane per DSM cell projects the cell's point into a view, marches the ray up to test
-//                     occlusion, and samples the image bilinearly; a mosaic fills each cell from the first view that sees it.
 //
 // Determinism: the only order-dependent steps are the atomics (which slot of its bucket a height lands in, which position a cell
 // takes in a tier list).  Every bucket is sorted before it is reduced, equal keys are equal bits, and the reduction order of a
 // bucket depends on its size alone, so the DSM is bit-identical from run to run and under any permutation of points or maps.
-#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
 
-#include "dsm_common.h"
+#include "dsm_geo.h"
 #include "smvs_device.h"
 #include "smvs_host.h"
 
 namespace smvs {
-
-// ---- Transverse Mercator ---------------------------------------------------------------------------------------------------
-// Constants of one projection, derived once on the host (IEEE float64, no contraction) in the operation order of the reference's
-// numpy code, so host-side mirrors reproduce the same bits.
-struct TmConst {
-    double a, e2, sec_e, sece2, k0, fe, fn, lat0, lon0;
-    double m1, m2, m3, m4, m0;          // meridional arc: M = a (m1 phi - m2 sin 2phi + m3 sin 4phi - m4 sin 6phi)
-    double e1, f1, f2, f3, f4;          // footpoint latitude series of the inverse
-};
-
-static const double TM_PI = 3.14159265358979323846;
-
-static bool tm_setup(const double* tm7, TmConst& t)
-{
-    const double a = tm7[0], inv_f = tm7[1];
-    if (!(a > 0.0) || !(inv_f > 1.0) || !(tm7[4] > 0.0) || !isfinite(a) || !isfinite(inv_f)) return false;
-    for (int i = 2; i < 7; ++i)
-        if (!isfinite(tm7[i])) return false;
-    const double f = 1.0 / inv_f;
-    const double e = sqrt(2 * f - f * f);
-    t.a = a;
-    t.e2 = e * e;
-    t.sec_e = sqrt((e * e) / (1 - e * e));
-    t.sece2 = t.sec_e * t.sec_e;
-    t.lat0 = tm7[2] / 180 * TM_PI;
-    t.lon0 = tm7[3] / 180 * TM_PI;
-    t.k0 = tm7[4];
-    t.fe = tm7[5];
-    t.fn = tm7[6];
-    const double e2 = t.e2, e4 = e2 * e2, e6 = e2 * e2 * e2;
-    t.m1 = 1 - e2 / 4 - 3 * e4 / 64 - 5 * e6 / 256;
-    t.m2 = 3 * e2 / 8 + 3 * e4 / 32 + 45 * e6 / 1024;
-    t.m3 = 15 * e4 / 256 + 45 * e6 / 1024;
-    t.m4 = 35 * e6 / 3072;
-    t.m0 = a * (t.m1 * t.lat0 - t.m2 * sin(2 * t.lat0) + t.m3 * sin(4 * t.lat0) - t.m4 * sin(6 * t.lat0));
-    const double r = sqrt(1 - e * e);
-    const double e1 = (1 - r) / (1 + r), e1s = e1 * e1;
-    t.e1 = e1;
-    t.f1 = 3 * e1 / 2 - 27 * e1s * e1 / 32;
-    t.f2 = 21 * e1s / 16 - 55 * e1s * e1s / 32;
-    t.f3 = 151 * e1s * e1 / 96;
-    t.f4 = 1097 * e1s * e1s / 512;
-    return true;
-}
-
-// (lat, lon) [deg] -> (E, N) [m]; Snyder (8-9), (8-10), (3-21), (4-20), (8-12..8-15).
-__device__ __forceinline__ void tm_forward(const TmConst& t, double lat_deg, double lon_deg, double& E, double& N)
-{
-    const double phi = lat_deg / 180 * TM_PI, lam = lon_deg / 180 * TM_PI;
-    double s, c;
-    sincos(phi, &s, &c);
-    const double tn = tan(phi);
-    const double T = tn * tn;
-    const double C = t.e2 * c * c / (1 - t.e2);
-    const double A = (lam - t.lon0) * c;
-    const double nu = t.a / sqrt(1 - t.e2 * s * s);
-    const double M = t.a * (t.m1 * phi - t.m2 * sin(2 * phi) + t.m3 * sin(4 * phi) - t.m4 * sin(6 * phi));
-    const double A2 = A * A, A3 = A * A * A;
-    E = t.fe + t.k0 * nu * (A + (1 - T + C) * A3 / 6 + (5 - 18 * T + T * T + 72 * C - 58 * t.sec_e * t.sec_e) * A2 * A3 / 120);
-    N = t.fn + t.k0 * (M - t.m0 + nu * tn * (A2 / 2 + (5 - T + 9 * C + 4 * C * C) * A2 * A2 / 24 +
-                                              (61 - 58 * T + T * T + 600 * C - 330 * t.sec_e * t.sec_e) * A3 * A3 / 720));
-}
-
-// (E, N) [m] -> (lat, lon) [deg]; Snyder (8-20), (7-19), (3-26), (8-21..8-26).
-__device__ __forceinline__ void tm_inverse(const TmConst& t, double E, double N, double& lat_deg, double& lon_deg)
-{
-    const double M1 = t.m0 + (N - t.fn) / t.k0;
-    const double mu = M1 / (t.a * t.m1);
-    const double phi1 = mu + t.f1 * sin(2 * mu) + t.f2 * sin(4 * mu) + t.f3 * sin(6 * mu) + t.f4 * sin(8 * mu);
-    double s1, c1;
-    sincos(phi1, &s1, &c1);
-    const double tn1 = tan(phi1);
-    const double q = sqrt(1 - t.e2 * s1 * s1);
-    const double nu1 = t.a / q;
-    const double rho1 = t.a * (1 - t.e2) / (q * q * q);
-    const double T1 = tn1 * tn1;
-    double C1 = t.sec_e * c1;
-    C1 = C1 * C1;
-    const double D = (E - t.fe) / (nu1 * t.k0);
-    const double D2 = D * D, D3 = D2 * D;
-    const double phi = phi1 - (nu1 * tn1 / rho1) * (D2 / 2 - (5 + 3 * T1 + 10 * C1 - 4 * C1 * C1 - 9 * t.sece2) * D2 * D2 / 24 +
-                                                   (61 + 90 * T1 + 298 * C1 + 45 * T1 * T1 - 252 * t.sece2 - 3 * C1 * C1) * D3 * D3 / 720);
-    const double lam = t.lon0 + (D - (1 + 2 * T1 + C1) * D3 / 6 +
-                                 (5 - 2 * C1 + 28 * T1 - 3 * C1 * C1 + 8 * t.sece2 + 24 * T1 * T1) * D2 * D3 / 120) / c1;
-    lat_deg = phi * 180 / TM_PI;
-    lon_deg = lam * 180 / TM_PI;
-}
 
 __global__ __launch_bounds__(256)
 void tm_project_kernel(TmConst t, const double* __restrict__ a, const double* __restrict__ b,
@@ -153,8 +61,6 @@ __device__ __forceinline__ unsigned run_head(unsigned long long heads)
 }
 
 // ---- bin pass --------------------------------------------------------------------------------------------------------------
-struct DsmGrid { double e0, n0, xres, yres; };
-
 __global__ __launch_bounds__(256)
 void dsm_bin_kernel(const float* __restrict__ height, const unsigned char* __restrict__ mask, const double* __restrict__ rpc,
                     int H, int W, TmConst t, DsmGrid g, int gw, int gh,
@@ -501,200 +407,6 @@ void dsm_cells_radix(const unsigned* __restrict__ offs, const unsigned* __restri
     }
 }
 
-// ---- render pass: DSM -> one view's image-space heights (include/satmvs.h) -----------------------------
-constexpr int RENDER_TILE = 16;                      // 16 x 16 pixels per workgroup: each wave covers 16 columns x 4 rows
-constexpr int RENDER_MAX_STEPS = 4096, RENDER_MAX_BISECT = 60;
-constexpr unsigned RENDER_MAX_BLOCKS = 1u << 20;     // grid-stride over tiles beyond this
-
-// S(E, N): bilinear over the cells floor(u) .. floor(u)+1 x floor(v) .. floor(v)+1, written as three lerps so that a flat patch
-// gives its height exactly.  False where one of the four is off the grid, non-finite or nodata (never extrapolated).
-__device__ __forceinline__ bool dsm_surface(const float* __restrict__ z, int gw, int gh, float nodata, const DsmGrid& g,
-                                            double E, double N, double& S)
-{
-    const double u = (E - g.e0) / g.xres, v = (g.n0 - N) / g.yres;
-    const double cu = floor(u), cv = floor(v);
-    if (!(cu >= 0.0 && cu < (double)(gw - 1) && cv >= 0.0 && cv < (double)(gh - 1))) return false;    // NaN fails too
-    const float* p = z + (size_t)(int)cv * gw + (int)cu;
-    const float z00 = p[0], z01 = p[1], z10 = p[gw], z11 = p[gw + 1];
-    if (!(dsm_cell_valid(z00, nodata) && dsm_cell_valid(z01, nodata) && dsm_cell_valid(z10, nodata) && dsm_cell_valid(z11, nodata)))
-        return false;
-    const double du = u - cu, dv = v - cv;
-    const double a = (double)z00 + du * ((double)z01 - (double)z00);
-    const double b = (double)z10 + du * ((double)z11 - (double)z10);
-    S = a + dv * (b - a);
-    return true;
-}
-
-// K = clamp(ceil(2 D), 1, RENDER_MAX_STEPS), D = the ray's travel in cells over [h_lo, h_hi] (NaN -> 1).
-__device__ __forceinline__ int render_march_steps(const DsmGrid& g, double E_hi, double N_hi, double E_lo, double N_lo)
-{
-    const double dE = fabs(E_hi - E_lo) / g.xres, dN = fabs(N_hi - N_lo) / g.yres;
-    const double c = ceil(2.0 * (dE > dN ? dE : dN));
-    return c >= (double)RENDER_MAX_STEPS ? RENDER_MAX_STEPS : c >= 1.0 ? (int)c : 1;
-}
-
-// B = clamp(ceil(log2(dh / tol)), 0, RENDER_MAX_BISECT), exactly: the least b with dh * 2^-b <= tol (halving is exact).
-__device__ __forceinline__ int render_bisect_steps(double dh, double tol)
-{
-    int b = 0;
-    while (dh > tol && b < RENDER_MAX_BISECT) { dh *= 0.5; ++b; }
-    return b;
-}
-
-// One lane per pixel.  The march (h_k = h_hi - k (h_hi - h_lo) / K, h_K = h_lo; first k with f(h_k) = S(G(h_k)) - h_k defined and >= 0)
-// and the bisection of [h_k, h_{k-1}] run as ONE loop whose body is one evaluation photo2obj -> TM -> bilinear; the lane's
-// state picks the next height, so lanes in different phases share the body instead of running it twice under divergence.
-__global__ __launch_bounds__(RENDER_TILE * RENDER_TILE)
-void dsm_render_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, float nodata, TmConst t,
-                       const double* __restrict__ rpc, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
-                       float* __restrict__ out)
-{
-    const unsigned nbx = (unsigned)(W + RENDER_TILE - 1) / RENDER_TILE, nby = (unsigned)(H + RENDER_TILE - 1) / RENDER_TILE;
-    const unsigned ntiles = nbx * nby;
-    const cgeo_t r = as_cgeo(rpc);
-    const RpcInv rn = rpc_inv_image(r);
-    for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int j = (int)(tile % nbx) * RENDER_TILE + (int)(threadIdx.x % RENDER_TILE);
-        const int i = (int)(tile / nbx) * RENDER_TILE + (int)(threadIdx.x / RENDER_TILE);
-        if (i >= H || j >= W) continue;
-        const double x = (double)(x0 + j), y = (double)(y0 + i);
-        double lat, lon, E_lo, N_lo;
-        rpc_photo2obj(launder(r), rn, x, y, h_lo, lat, lon);
-        tm_forward(t, lat, lon, E_lo, N_lo);
-        double h = h_hi, h_prev = h_hi, a = 0.0, b = 0.0, step = 0.0;
-        int k = 0, K = 1, left = -1;                 // left < 0: marching; else bisection steps still to take
-        bool prev_ok = false;
-        float res = __builtin_nanf("");
-        for (;;) {
-            double E, N, S;
-            rpc_photo2obj(launder(r), rn, x, y, h, lat, lon);
-            tm_forward(t, lat, lon, E, N);
-            const bool ok = dsm_surface(z, gw, gh, nodata, g, E, N, S);
-            const bool below = ok && S - h >= 0.0;   // f(h) defined and >= 0
-            if (left < 0) {
-                if (k == 0) {
-                    K = render_march_steps(g, E, N, E_lo, N_lo);
-                    step = (h_hi - h_lo) / (double)K;
-                }
-                if (!below) {
-                    if (k == K) break;               // no sample qualifies: invalid
-                    prev_ok = ok;
-                    h_prev = h;
-                    ++k;
-                    h = (k == K) ? h_lo : h_hi - (double)k * step;     // the last sample is h_lo exactly, whatever the rounding
-                    continue;
-                }
-                if (k == 0) { res = (float)h_hi; break; }
-                if (!prev_ok) break;                 // came out of a hole or off the grid: invalid
-                a = h;
-                b = h_prev;
-                left = render_bisect_steps(step, tol);
-            } else {
-                if (!ok) break;                      // a midpoint where f is undefined: invalid
-                if (below) a = h;
-                else b = h;
-                --left;
-            }
-            if (left == 0) { res = (float)(0.5 * (a + b)); break; }
-            h = 0.5 * (a + b);
-        }
-        out[(size_t)i * W + j] = res;
-    }
-}
-
-// ---- orthophoto pass: one view's image resampled onto the DSM grid, with occlusion (include/satmvs.h) --
-constexpr int ORTHO_MAX_CHANNELS = 16;
-enum : unsigned char { ORTHO_NO_HEIGHT = 0, ORTHO_OUTSIDE = 1, ORTHO_OCCLUDED = 2, ORTHO_VISIBLE = 3 };
-
-// Whether the ray up from the cell's point (x, y, zc) passes under the surface: samples h_k = zc + k (h_hi - zc) / K,
-// k = 1 .. K - 1, and h_K = h_hi exactly, K from the travel between G(zc) and G(h_hi) as in the render.  A sample occludes where
-// f(h_k) = S(G(h_k)) - h_k is defined and > occ_tol; undefined samples (holes, off the grid) do not.  ONE loop whose body is one
-// evaluation photo2obj -> TM -> bilinear, as in the render: G(zc) first (only for K), then h_K = h_hi (its G sets K; the order
-// of the samples does not change whether one of them occludes), then h_1 .. h_{K-1}.
-__device__ __forceinline__ bool ortho_occluded(const float* __restrict__ z, int gw, int gh, float nodata, const DsmGrid& g,
-                                               const TmConst& t, cgeo_t r, const RpcInv& rn, double x, double y, double zc,
-                                               double h_hi, double occ_tol)
-{
-    if (!(zc < h_hi)) return false;
-    double h = zc, E_z = 0.0, N_z = 0.0, step = 0.0;
-    int k = -1, K = 1;                               // k = -1: G(zc); k = 0: h_K; then k = 1 .. K - 1, K <= RENDER_MAX_STEPS
-    for (;;) {
-        double lat, lon, E, N, S;
-        rpc_photo2obj(launder(r), rn, x, y, h, lat, lon);
-        tm_forward(t, lat, lon, E, N);
-        if (k < 0) {
-            E_z = E;
-            N_z = N;
-            k = 0;
-            h = h_hi;
-            continue;
-        }
-        if (dsm_surface(z, gw, gh, nodata, g, E, N, S) && S - h > occ_tol) return true;
-        if (k == 0) {
-            K = render_march_steps(g, E, N, E_z, N_z);
-            step = (h_hi - zc) / (double)K;
-        }
-        if (++k >= K) return false;
-        h = zc + (double)k * step;
-    }
-}
-
-// One lane per DSM cell, 16 x 16-cell workgroups (neighbouring rays read the same DSM lines), grid-stride past
-// RENDER_MAX_BLOCKS.  Height -> TM inverse -> rpc_obj2photo -> bounds -> occlusion march -> bilinear image sample; ortho and
-// source are written where the cell is visible and source < 0 on entry.  Without a state map, cells already filled by an
-// earlier view are skipped whole.
-__global__ __launch_bounds__(RENDER_TILE * RENDER_TILE)
-void dsm_ortho_kernel(const float* __restrict__ z, int gw, int gh, DsmGrid g, float nodata, TmConst t,
-                      const double* __restrict__ rpc, const float* __restrict__ image, int H, int W, int C, int x0, int y0,
-                      double h_hi, int occlusion, double occ_tol, int view,
-                      float* __restrict__ ortho, int* __restrict__ source, unsigned char* __restrict__ state)
-{
-    const unsigned nbx = (unsigned)(gw + RENDER_TILE - 1) / RENDER_TILE, nby = (unsigned)(gh + RENDER_TILE - 1) / RENDER_TILE;
-    const unsigned ntiles = nbx * nby;
-    const cgeo_t r = as_cgeo(rpc);
-    const RpcInv rg = rpc_inv_ground(r), ri = rpc_inv_image(r);
-    for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int c = (int)(tile % nbx) * RENDER_TILE + (int)(threadIdx.x % RENDER_TILE);
-        const int row = (int)(tile / nbx) * RENDER_TILE + (int)(threadIdx.x / RENDER_TILE);
-        if (row >= gh || c >= gw) continue;
-        const size_t cell = (size_t)row * gw + c;
-        if (!state && source[cell] >= 0) continue;   // filled by an earlier view; nothing else to write
-        const float zf = z[cell];
-        unsigned char st = ORTHO_NO_HEIGHT;
-        double u = 0.0, v = 0.0;
-        if (dsm_cell_valid(zf, nodata)) {
-            const double E = g.e0 + (double)c * g.xres, N = g.n0 - (double)row * g.yres;
-            double lat, lon, x, y;
-            tm_inverse(t, E, N, lat, lon);
-            rpc_obj2photo(launder(r), rg, lat, lon, (double)zf, x, y);
-            u = x - (double)x0;
-            v = y - (double)y0;
-            if (!(u >= 0.0 && u <= (double)(W - 1) && v >= 0.0 && v <= (double)(H - 1))) st = ORTHO_OUTSIDE;   // NaN fails
-            else if (occlusion && ortho_occluded(z, gw, gh, nodata, g, t, r, ri, x, y, (double)zf, h_hi, occ_tol)) st = ORTHO_OCCLUDED;
-            else st = ORTHO_VISIBLE;
-        }
-        if (state) state[cell] = st;
-        if (st != ORTHO_VISIBLE || !source || source[cell] >= 0) continue;
-        if (ortho) {
-            // pixel centres on integers; the last column / row is reached with du = 1 (dv = 1) from the one before it
-            const int c0 = W > 1 ? min((int)floor(u), W - 2) : 0, r0 = H > 1 ? min((int)floor(v), H - 2) : 0;
-            const int c1 = W > 1 ? c0 + 1 : 0, r1 = H > 1 ? r0 + 1 : 0;
-            const double du = W > 1 ? u - (double)c0 : 0.0, dv = H > 1 ? v - (double)r0 : 0.0;
-            const float* p00 = image + ((size_t)r0 * W + c0) * C;
-            const float* p01 = image + ((size_t)r0 * W + c1) * C;
-            const float* p10 = image + ((size_t)r1 * W + c0) * C;
-            const float* p11 = image + ((size_t)r1 * W + c1) * C;
-            float* o = ortho + cell * C;
-            for (int ch = 0; ch < ORTHO_MAX_CHANNELS && ch < C; ++ch) {
-                const double a = (double)p00[ch] + du * ((double)p01[ch] - (double)p00[ch]);
-                const double b = (double)p10[ch] + du * ((double)p11[ch] - (double)p10[ch]);
-                o[ch] = (float)(a + dv * (b - a));
-            }
-        }
-        source[cell] = view;
-    }
-}
-
 // ---- workspace layout --------------------------------------------------------------------------------------------------------
 struct DsmWs { size_t offs, cursor, keys, alt, tiles, lcount, list1, list2, bytes; };
 
@@ -727,10 +439,10 @@ SMVS_EXPORT int smvs_tm_project(const double* tm7, const double* a, const double
     if (!tm7 || !a || !b || !o0 || !o1) return fail(SMVS_ERR_ARG, "null pointer argument");
     if (dir != 0 && dir != 1) return fail(SMVS_ERR_ARG, "dir must be 0 (lat/lon -> E/N) or 1 (E/N -> lat/lon)");
     TmConst t;
-    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
+    if (const char* msg = tm_parse(tm7, t)) return fail(SMVS_ERR_ARG, "%s", msg);
     if (n == 0) return SMVS_OK;
     hipLaunchKernelGGL(tm_project_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, a, b, o0, o1, n, dir);
-    return check_launch_dsm("tm_project");
+    return check_launch("tm_project");
 }
 
 SMVS_EXPORT int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
@@ -742,70 +454,14 @@ SMVS_EXPORT int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask,
     if ((east == nullptr) != (north == nullptr)) return fail(SMVS_ERR_ARG, "east and north go together");
     if (H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
     if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
-    const DsmGrid g{grid4[0], grid4[1], grid4[2], grid4[3]};
-    if (!isfinite(g.e0) || !isfinite(g.n0) || !(g.xres > 0.0) || !(g.yres > 0.0) || !isfinite(g.xres) || !isfinite(g.yres))
-        return fail(SMVS_ERR_ARG, "bad grid: E0, N0 finite, xres and yres positive and finite");
+    DsmGrid g;
+    if (const char* msg = dsm_grid_parse(grid4, g)) return fail(SMVS_ERR_ARG, "%s", msg);
     TmConst t;
-    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
+    if (const char* msg = tm_parse(tm7, t)) return fail(SMVS_ERR_ARG, "%s", msg);
     const size_t n = (size_t)H * W;
     hipLaunchKernelGGL(dsm_bin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        height, mask, rpc170, H, W, t, g, gw, gh, cell, count, east, north);
-    return check_launch_dsm("dsm_bin");
-}
-
-SMVS_EXPORT int smvs_rpc_dsm_render(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
-                                    const double* rpc170, int H, int W, int x0, int y0, double h_lo, double h_hi, double tol,
-                                    float* height, void* stream)
-{
-    using namespace smvs;
-    if (!dsm || !grid4 || !tm7 || !rpc170 || !height) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if (H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if ((long long)H * W >= (1ll << 31)) return fail(SMVS_ERR_ARG, "view too large: H * W must be below 2^31 pixels");
-    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
-    if (x0 < 0 || y0 < 0) return fail(SMVS_ERR_ARG, "negative origin");
-    if ((long long)x0 + W > INT_MAX || (long long)y0 + H > INT_MAX) return fail(SMVS_ERR_ARG, "origin + size does not fit in an int");
-    const DsmGrid g{grid4[0], grid4[1], grid4[2], grid4[3]};
-    if (!isfinite(g.e0) || !isfinite(g.n0) || !(g.xres > 0.0) || !(g.yres > 0.0) || !isfinite(g.xres) || !isfinite(g.yres))
-        return fail(SMVS_ERR_ARG, "bad grid: E0, N0 finite, xres and yres positive and finite");
-    TmConst t;
-    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
-    if (!isfinite(h_lo) || !isfinite(h_hi) || !(h_lo <= h_hi)) return fail(SMVS_ERR_ARG, "height bracket: h_lo <= h_hi, both finite");
-    if (!(tol > 0.0) || !isfinite(tol)) return fail(SMVS_ERR_ARG, "tol must be positive and finite");
-    const unsigned ntiles = (unsigned)((W + RENDER_TILE - 1) / RENDER_TILE) * (unsigned)((H + RENDER_TILE - 1) / RENDER_TILE);
-    hipLaunchKernelGGL(dsm_render_kernel, dim3(std::min(ntiles, RENDER_MAX_BLOCKS)), dim3(RENDER_TILE * RENDER_TILE), 0,
-                       (hipStream_t)stream, dsm, gw, gh, g, nodata, t, rpc170, H, W, x0, y0, h_lo, h_hi, tol, height);
-    return check_launch_dsm("dsm_render");
-}
-
-SMVS_EXPORT int smvs_rpc_ortho(const float* dsm, int gw, int gh, const double* grid4, float nodata, const double* tm7,
-                               const double* rpc170, const float* image, int H, int W, int C, int x0, int y0,
-                               double h_hi, int occlusion, double occ_tol, int view,
-                               float* ortho, int* source, unsigned char* state, void* stream)
-{
-    using namespace smvs;
-    if (!dsm || !grid4 || !tm7 || !rpc170) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if ((image == nullptr) != (ortho == nullptr)) return fail(SMVS_ERR_ARG, "null pointer argument: image and ortho go together");
-    if (ortho && !source) return fail(SMVS_ERR_ARG, "null pointer argument: ortho needs source (the mosaic rule reads it)");
-    if (!source && !state) return fail(SMVS_ERR_ARG, "null pointer argument: nothing to write (give source or state)");
-    if (C < 1 || C > ORTHO_MAX_CHANNELS) return fail(SMVS_ERR_ARG, "channel count C must be in 1 .. %d", ORTHO_MAX_CHANNELS);
-    if (H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if ((long long)H * W >= (1ll << 31)) return fail(SMVS_ERR_ARG, "view too large: H * W must be below 2^31 pixels");
-    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
-    if (x0 < 0 || y0 < 0) return fail(SMVS_ERR_ARG, "negative origin");
-    if ((long long)x0 + W > INT_MAX || (long long)y0 + H > INT_MAX) return fail(SMVS_ERR_ARG, "origin + size does not fit in an int");
-    const DsmGrid g{grid4[0], grid4[1], grid4[2], grid4[3]};
-    if (!isfinite(g.e0) || !isfinite(g.n0) || !(g.xres > 0.0) || !(g.yres > 0.0) || !isfinite(g.xres) || !isfinite(g.yres))
-        return fail(SMVS_ERR_ARG, "bad grid: E0, N0 finite, xres and yres positive and finite");
-    TmConst t;
-    if (!tm_setup(tm7, t)) return fail(SMVS_ERR_ARG, "bad projection parameters (a > 0, inverse flattening > 1, k0 > 0, all finite)");
-    if (!isfinite(h_hi)) return fail(SMVS_ERR_ARG, "h_hi must be finite");
-    if (!(occ_tol >= 0.0) || !isfinite(occ_tol)) return fail(SMVS_ERR_ARG, "occ_tol must be finite and >= 0");
-    if (view < 0) return fail(SMVS_ERR_ARG, "view must be non-negative");
-    const unsigned ntiles = (unsigned)((gw + RENDER_TILE - 1) / RENDER_TILE) * (unsigned)((gh + RENDER_TILE - 1) / RENDER_TILE);
-    hipLaunchKernelGGL(dsm_ortho_kernel, dim3(std::min(ntiles, RENDER_MAX_BLOCKS)), dim3(RENDER_TILE * RENDER_TILE), 0,
-                       (hipStream_t)stream, dsm, gw, gh, g, nodata, t, rpc170, image, H, W, C, x0, y0, h_hi, occlusion, occ_tol,
-                       view, ortho, source, state);
-    return check_launch_dsm("dsm_ortho");
+    return check_launch("dsm_bin");
 }
 
 SMVS_EXPORT size_t smvs_dsm_workspace_bytes(size_t n, int gw, int gh)
@@ -840,25 +496,25 @@ SMVS_EXPORT int smvs_dsm_reduce(const int* cell, const float* height, size_t n, 
     const unsigned ntiles = (unsigned)((ncells + SCAN_TILE - 1) / SCAN_TILE);
     int rc;
     hipLaunchKernelGGL(dsm_scan_tiles, dim3(ntiles), dim3(SCAN_THREADS), 0, s, count, nc, tiles);
-    if ((rc = check_launch_dsm("dsm_scan_tiles"))) return rc;
+    if ((rc = check_launch("dsm_scan_tiles"))) return rc;
     hipLaunchKernelGGL(dsm_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, s, tiles, ntiles, offs, nc, lcount);
-    if ((rc = check_launch_dsm("dsm_scan_sums"))) return rc;
+    if ((rc = check_launch("dsm_scan_sums"))) return rc;
     hipLaunchKernelGGL(dsm_scan_cells, dim3(ntiles), dim3(SCAN_THREADS), 0, s, count, nc, tiles, offs, cursor);
-    if ((rc = check_launch_dsm("dsm_scan_cells"))) return rc;
+    if ((rc = check_launch("dsm_scan_cells"))) return rc;
     if (n > 0) {
         hipLaunchKernelGGL(dsm_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cell, height, nn, nc, offs, cursor, keys);
-        if ((rc = check_launch_dsm("dsm_scatter"))) return rc;
+        if ((rc = check_launch("dsm_scatter"))) return rc;
     }
     hipLaunchKernelGGL(dsm_cells_small, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, s,
                        offs, cursor, keys, nn, nc, mode, nodata, dsm, lcount, list1, list2);
-    if ((rc = check_launch_dsm("dsm_cells_small"))) return rc;
+    if ((rc = check_launch("dsm_cells_small"))) return rc;
     if (n > (size_t)TIER0_MAX) {
         hipLaunchKernelGGL(dsm_cells_bitonic, dim3(TIER1_BLOCKS), dim3(TIER1_THREADS), 0, s, offs, cursor, keys, nn, mode, dsm, lcount, list1);
-        if ((rc = check_launch_dsm("dsm_cells_bitonic"))) return rc;
+        if ((rc = check_launch("dsm_cells_bitonic"))) return rc;
     }
     if (n > (size_t)TIER1_MAX) {
         hipLaunchKernelGGL(dsm_cells_radix, dim3(TIER2_BLOCKS), dim3(TIER2_THREADS), 0, s, offs, cursor, keys, alt, nn, mode, dsm, lcount, list2);
-        if ((rc = check_launch_dsm("dsm_cells_radix"))) return rc;
+        if ((rc = check_launch("dsm_cells_radix"))) return rc;
     }
     return SMVS_OK;
 }

@@ -1,5 +1,5 @@
-// dsm_common.h -- what the DSM sources (dsm.hip, dsm_post.hip, dsm_morph.hip) share: the validity test of a cell, the
-// order-preserving uint32 image of a float, the register sorting network, and the host-side grid, aliasing and launch checks.
+// dsm_common.h -- what the DSM sources (dsm.hip, dsm_render.hip, dsm_post.hip, dsm_morph.hip) share: the validity test of a cell,
+// the order-preserving uint32 image of a float, the register sorting network, and the host-side grid-size and aliasing checks.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -44,13 +44,6 @@ __device__ __forceinline__ void bitonic_net(unsigned (&v)[N])
 }
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static int check_launch_dsm(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
-    return SMVS_OK;
-}
 
 // Whether two buffers share a byte (the out-of-place entries reject aliased arguments).
 static bool dsm_overlap(const void* a, size_t na, const void* b, size_t nb)

@@ -133,7 +133,7 @@ static int morph_launch(MorphPass a, bool cols, hipStream_t s)
         a.seg = MORPH_ROW_CELLS - 2 * a.radius;
         const unsigned nseg = (unsigned)((a.gw + a.seg - 1) / a.seg);
         hipLaunchKernelGGL((dsm_morph_pass<1, MORPH_ROW_CELLS, false, MORPH_THREADS>), dim3(nseg * (unsigned)a.gh), dim3(MORPH_THREADS), 0, s, a);
-        return check_launch_dsm("dsm_morph_pass (rows)");
+        return check_launch("dsm_morph_pass (rows)");
     }
     const bool small = a.radius <= MORPH_COL_SMALL_RADIUS;
     a.seg = (small ? MORPH_COL_SMALL : MORPH_COL_LARGE) - 2 * a.radius;
@@ -141,7 +141,7 @@ static int morph_launch(MorphPass a, bool cols, hipStream_t s)
     const dim3 grid(nseg * (unsigned)((a.gw + MORPH_COL_NL - 1) / MORPH_COL_NL));
     if (small) hipLaunchKernelGGL((dsm_morph_pass<MORPH_COL_NL, MORPH_COL_SMALL * MORPH_COL_NL, true, MORPH_THREADS>), grid, dim3(MORPH_THREADS), 0, s, a);
     else hipLaunchKernelGGL((dsm_morph_pass<MORPH_COL_NL, MORPH_COL_LARGE * MORPH_COL_NL, true, MORPH_THREADS_LARGE>), grid, dim3(MORPH_THREADS_LARGE), 0, s, a);
-    return check_launch_dsm("dsm_morph_pass (columns)");
+    return check_launch("dsm_morph_pass (columns)");
 }
 
 // The four passes of an opening of the surface `in_mode` describes (a closing with the complements swapped): rows and columns

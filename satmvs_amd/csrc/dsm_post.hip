@@ -251,7 +251,7 @@ SMVS_EXPORT int smvs_dsm_despike(const float* dsm, int gw, int gh, float nodata,
     if (radius == 1) hipLaunchKernelGGL(dsm_despike_kernel<1>, grid, block, 0, s, dsm, gw, gh, nodata, thresh, min_valid, out, removed);
     else if (radius == 2) hipLaunchKernelGGL(dsm_despike_kernel<2>, grid, block, 0, s, dsm, gw, gh, nodata, thresh, min_valid, out, removed);
     else hipLaunchKernelGGL(dsm_despike_kernel<3>, grid, block, 0, s, dsm, gw, gh, nodata, thresh, min_valid, out, removed);
-    return check_launch_dsm("dsm_despike");
+    return check_launch("dsm_despike");
 }
 
 SMVS_EXPORT size_t smvs_dsm_fill_workspace_bytes(int gw, int gh, int max_steps)
@@ -287,11 +287,11 @@ SMVS_EXPORT int smvs_dsm_fill(const float* dsm, int gw, int gh, float nodata, in
     int rc;
     hipLaunchKernelGGL(dsm_fill_march, dim3((unsigned)((lanes + FILL_THREADS - 1) / FILL_THREADS), (unsigned)nbands, FILL_PLANES),
                        dim3(FILL_THREADS), 0, s, dsm, gw, gh, nodata, max_steps, band, planes, plane_stride);
-    if ((rc = check_launch_dsm("dsm_fill_march"))) return rc;
+    if ((rc = check_launch("dsm_fill_march"))) return rc;
     const unsigned ntiles = (unsigned)((gw + FILL_THREADS - 1) / FILL_THREADS) * (unsigned)gh;
     hipLaunchKernelGGL(dsm_fill_combine, dim3(std::min(ntiles, POST_MAX_BLOCKS)), dim3(FILL_THREADS), 0, s,
                        dsm, gw, gh, nodata, max_steps, min_hits, method, planes, plane_stride, out, hits);
-    return check_launch_dsm("dsm_fill_combine");
+    return check_launch("dsm_fill_combine");
 }
 
 }  // extern "C"

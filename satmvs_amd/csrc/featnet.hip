@@ -358,9 +358,7 @@ SMVS_EXPORT int smvs_featnet_pack_weights(const float* const* params, int base_c
                            mode == 1 ? q[3] : q[0], mode == 1 ? q[4] : q[0], packed + lay.scale[i], packed + lay.shift[i],
                            L[i].cout, cp, mode);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "featnet_pack_weights launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("featnet_pack_weights");
 }
 
 // imgs (N,3,H,W) -> stage1 (N,4c,H/4,W/4), stage2 (N,2c,H/2,W/2), stage3 (N,c,H,W).  N = samples x views;
@@ -408,9 +406,7 @@ SMVS_EXPORT int smvs_featnet_fwd(const float* packed, const float* imgs, float* 
         a.Hi = H >> s.lin; a.Wi = W >> s.lin; a.Ho = H >> s.lout; a.Wo = W >> s.lout;
         fn_launch(L[i], a, N, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "featnet_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("featnet_fwd");
 }
 
 }  // extern "C"

@@ -123,9 +123,7 @@ SMVS_EXPORT int smvs_pinhole_geo_consistency(const float* depth_ref, const float
     const size_t n = (size_t)H * W;
     hipLaunchKernelGGL(pinhole_geo_consistency_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        depth_ref, depth_src, mats, H, W, Hs, Ws, p_thre, (float)relative_d_thre, mask, depth_reproj, x_src, y_src, x_back, y_back);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "pinhole_geo_consistency launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("pinhole_geo_consistency");
 }
 
 SMVS_EXPORT int smvs_rpc_geo_consistency(const float* depth_ref, const double* rpc_ref, const float* depth_src,
@@ -142,9 +140,7 @@ SMVS_EXPORT int smvs_rpc_geo_consistency(const float* depth_ref, const double* r
     hipLaunchKernelGGL(geo_consistency_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        depth_ref, rpc_ref, depth_src, rpc_src, H, W, Hs, Ws, p_ratio, d_ratio, mask, depth_reproj,
                        x_src, y_src, x_back, y_back);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "geo_consistency launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("geo_consistency");
 }
 
 }  // extern "C"

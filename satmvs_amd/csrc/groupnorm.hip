@@ -284,9 +284,7 @@ static int gn_fwd(const float* x, long long xbs, const float* gamma, const float
     hipLaunchKernelGGL(gn1_stats_kernel, dim3((unsigned)nblk, B), dim3(GN_THREADS), 0, st, x, xbs, n, workspace);
     hipLaunchKernelGGL(gn1_apply_kernel, dim3((HW + GN_ELEMS - 1) / GN_ELEMS, B * C), dim3(GN_THREADS), 0, st, x, xbs, gamma, beta, gamma2, beta2,
                        workspace, nblk, eps, act, y, mean_rstd, C, HW, ep);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "groupnorm1_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("groupnorm1_fwd");
 }
 
 static int gn_bwd(const float* dy, const float* x, long long xbs, const float* y, const float* gamma, const float* gamma2, const float* mean_rstd, int act,
@@ -307,9 +305,7 @@ static int gn_bwd(const float* dy, const float* x, long long xbs, const float* y
     hipLaunchKernelGGL(gn1_bwd_rows_kernel, grid, dim3(GN_THREADS), 0, st, dy, x, xbs, yy, mean_rstd, act, rows, C, HW);
     hipLaunchKernelGGL(gn1_bwd_dx_kernel, grid, dim3(GN_THREADS), 0, st, dy, x, xbs, yy, gamma, gamma2, mean_rstd, rows, act, dx, dxbs, dgamma, dbeta,
                        dgamma2, dbeta2, B, C, HW);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "groupnorm1_bwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("groupnorm1_bwd");
 }
 
 }  // namespace smvs
@@ -470,9 +466,7 @@ extern "C" SMVS_EXPORT int smvs_gru_mul_cat_bwd_acc(float* dcat, const float* r,
     const long long nx = (long long)Cx * HW, nh = (long long)Ch * HW;
     hipLaunchKernelGGL(gru_mul_cat_bwd_acc_kernel, dim3((unsigned)((nh + GE_THREADS - 1) / GE_THREADS), B), dim3(GE_THREADS), 0, (hipStream_t)stream,
                        dcat, r, h, dh_acc, dr, nx, nh);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "gru_mul_cat_bwd_acc launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("gru_mul_cat_bwd_acc");
 }
 
 extern "C" SMVS_EXPORT int smvs_gru_blend_fwd(const float* u, const float* h, const float* y, float* out, long long n, void* stream)
@@ -483,9 +477,7 @@ extern "C" SMVS_EXPORT int smvs_gru_blend_fwd(const float* u, const float* h, co
     if ((((uintptr_t)u) | ((uintptr_t)h) | ((uintptr_t)y) | ((uintptr_t)out)) & 15) return fail(SMVS_ERR_ARG, "pointers must be 16-byte aligned");
     const long long n4 = n / 4, nb = (n4 + GE_THREADS - 1) / GE_THREADS;
     hipLaunchKernelGGL(gru_blend_fwd_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(GE_THREADS), 0, (hipStream_t)stream, u, h, y, out, n4, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "gru_blend_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("gru_blend_fwd");
 }
 
 extern "C" SMVS_EXPORT int smvs_gru_blend_bwd(const float* dy, const float* u, const float* h, const float* y, float* du, float* dh, float* dcand,
@@ -498,9 +490,7 @@ extern "C" SMVS_EXPORT int smvs_gru_blend_bwd(const float* dy, const float* u, c
         return fail(SMVS_ERR_ARG, "pointers must be 16-byte aligned");
     const long long n4 = n / 4, nb = (n4 + GE_THREADS - 1) / GE_THREADS;
     hipLaunchKernelGGL(gru_blend_bwd_kernel, dim3((unsigned)(nb > 0 ? nb : 1)), dim3(GE_THREADS), 0, (hipStream_t)stream, dy, u, h, y, du, dh, dcand, n4, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "gru_blend_bwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("gru_blend_bwd");
 }
 
 extern "C" SMVS_EXPORT int smvs_gru_mul_cat_fwd(const float* x, const float* r, const float* h, float* out, int B, int Cx, int Ch, int HW, void* stream)
@@ -511,9 +501,7 @@ extern "C" SMVS_EXPORT int smvs_gru_mul_cat_fwd(const float* x, const float* r, 
     const long long nx = (long long)Cx * HW, nh = (long long)Ch * HW;
     hipLaunchKernelGGL(gru_mul_cat_fwd_kernel, dim3((unsigned)((nx + nh + GE_THREADS - 1) / GE_THREADS), B), dim3(GE_THREADS), 0, (hipStream_t)stream,
                        x, r, h, out, nx, nh);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "gru_mul_cat_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("gru_mul_cat_fwd");
 }
 
 extern "C" SMVS_EXPORT int smvs_gru_mul_cat_bwd(const float* dcat, const float* r, const float* h, float* dr, float* dh, int B, int Cx, int Ch, int HW,
@@ -525,7 +513,5 @@ extern "C" SMVS_EXPORT int smvs_gru_mul_cat_bwd(const float* dcat, const float* 
     const long long nx = (long long)Cx * HW, nh = (long long)Ch * HW;
     hipLaunchKernelGGL(gru_mul_cat_bwd_kernel, dim3((unsigned)((nh + GE_THREADS - 1) / GE_THREADS), B), dim3(GE_THREADS), 0, (hipStream_t)stream,
                        dcat, r, h, dr, dh, nx, nh);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "gru_mul_cat_bwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("gru_mul_cat_bwd");
 }

@@ -1230,9 +1230,7 @@ static int red_run_planes(const RedRun& r, int d_begin, int d_end)
     }
     // join: the caller's stream continues only after the last plane's decoder (which implies the rest)
     if (multi) (void)hipStreamWaitEvent(r.main, P.done[(nplanes - 1) % RING], 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "red planes launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("red planes");
 }
 
 }  // namespace smvs
@@ -1299,9 +1297,7 @@ SMVS_EXPORT int smvs_red_pack_weights(const float* const* params, int C, float* 
     for (int i = 0; i < 3; ++i) pack(params[43 + i], L.up_w[i], up_in[i], up_out[i], 1);
     pack(params[46], L.up2d_w, 8, 1, 2);
     copy(params[47], L.up2d_b, 1);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "red_pack_weights launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("red_pack_weights");
 }
 
 // ---- a single 3x3 / pad 1 layer of the regulariser as a stand-alone call (training path) --------------------------------------
@@ -1341,9 +1337,7 @@ SMVS_EXPORT int smvs_conv3x3_pack(const float* w, float* packed, int cin, int co
         const int nm = (int)mfma_packed_floats(cin, cout, 9);
         hipLaunchKernelGGL(mfma_pack_kernel, dim3((nm + 255) / 256), dim3(256), 0, st, w, packed + n, cin, cout, 9, layout == 2 ? 1 : 0);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3x3_pack launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3x3_pack");
 }
 
 SMVS_EXPORT int smvs_conv3x3_fwd(int kind, const float* xA, int CA, const float* xB, int CB, const float* packed, const float* bias, const float* init,
@@ -1368,9 +1362,7 @@ SMVS_EXPORT int smvs_conv3x3_fwd(int kind, const float* xA, int CA, const float*
         const bool mf = mfma_conv_ok(Cin, 0, Cout) && CA % 2 == 0 && (!bias || ((uintptr_t)bias & 15) == 0);
         launch_conv(kind == 1 ? 2 : 1, a, B, (hipStream_t)stream, mf ? packed + packed_conv_floats(Cin, Cout) : nullptr);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "conv3x3_fwd launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("conv3x3_fwd");
 }
 
 // One plane of the recurrent regulariser.  cost (B,C,H,W) is the variance plane (the network consumes

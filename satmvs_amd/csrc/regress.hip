@@ -179,13 +179,6 @@ char* last_error_buf()
     return buf;
 }
 
-static int check_launch(const char* what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
-    return SMVS_OK;
-}
-
 }  // namespace smvs
 
 extern "C" {

@@ -25,6 +25,14 @@ inline int fail(int code, const char* fmt, ...)
     return code;
 }
 
+// After a kernel launch: SMVS_OK, or SMVS_ERR_LAUNCH with "<what> launch: <the runtime's message>".
+inline int check_launch(const char* what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
+    return SMVS_OK;
+}
+
 // smvs_height_gen (C ABI) -> device-side HeightGen for a stage of size H x W; returns a message on bad arguments
 struct HeightGenHost { const float* prev; int hp, wp, ih, iw, scale; float c, ndm1; const float *var, *rmin, *rmax; };
 inline const char* height_gen_check(const smvs_height_gen* g, int D, int H, int W, HeightGenHost& o)

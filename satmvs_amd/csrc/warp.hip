@@ -117,9 +117,7 @@ static int warp_launch(int geo, bool bwd, const float* fea, float* out, const do
     else if (geo == 0)    hipLaunchKernelGGL((warp_kernel<0, true>), grd, blk, 0, st, p);
     else if (!bwd)        hipLaunchKernelGGL((warp_kernel<1, false>), grd, blk, 0, st, p);
     else                  hipLaunchKernelGGL((warp_kernel<1, true>), grd, blk, 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SMVS_ERR_LAUNCH, "warp launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return check_launch("warp");
 }
 
 // ---- src_proj @ inverse(ref_proj), warping.py:19 ------------------------------------------------------
@@ -192,9 +190,7 @@ SMVS_EXPORT int smvs_homo_compose(const double* src_proj, const double* ref_proj
     if (n < 1) return smvs::fail(SMVS_ERR_ARG, "non-positive matrix count");
     hipLaunchKernelGGL(smvs::homo_compose_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        src_proj, ref_proj, out, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return smvs::fail(SMVS_ERR_LAUNCH, "homo_compose launch: %s", hipGetErrorString(e));
-    return SMVS_OK;
+    return smvs::check_launch("homo_compose");
 }
 
 }  // extern "C"

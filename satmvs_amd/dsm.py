@@ -80,6 +80,53 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _to_device(x, dtype=None, dev=None):
+    """(contiguous device tensor, whether the caller gave numpy).  dev=None: a device tensor stays where it is and anything
+    else goes to the current device; dtype=None: the dtype is kept."""
+    as_numpy = not isinstance(x, torch.Tensor)
+    if dev is None:
+        dev = _dev() if as_numpy or not x.is_cuda else x.device
+    t = torch.from_numpy(np.ascontiguousarray(x)) if as_numpy else x
+    return t.to(device=dev, dtype=dtype).contiguous(), as_numpy
+
+
+def _back(as_numpy, *results):
+    """The way back from _to_device: the results (None stays None) as numpy if the caller gave numpy; a single one bare."""
+    out = tuple(t.cpu().numpy() if as_numpy and t is not None else t for t in results)
+    return out[0] if len(out) == 1 else out
+
+
+def _on_grid(a, grid):
+    if tuple(a.shape) != (grid.height, grid.width):
+        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(a.shape), grid.height, grid.width))
+    return a
+
+
+# A DSM argument follows one of two dtype policies.  Render, orthophoto and production compute new values from the heights,
+# so they CONVERT whatever real dtype comes to float32 (_dsm_converted, and _maps for the height maps).  Clean-up and
+# morphology copy cells bit for bit, so they REJECT anything that is not float32 already (_dsm_bits): a silent conversion
+# would change the bits they promise to keep.
+def _dsm_converted(dsm, grid):
+    """The DSM of `grid`, numpy taken as float32 (a tensor is converted on its way to the device)."""
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm, dtype=np.float32)
+    return _on_grid(dsm, grid)
+
+
+def _dsm_bits(dsm):
+    """A (gh, gw) float32 grid, numpy or tensor, checked before any device work and never converted."""
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm)
+    if dsm.ndim != 2:
+        raise ValueError("a DSM is (gh, gw), got shape %s" % (tuple(dsm.shape),))
+    if dsm.dtype not in (np.float32, torch.float32):
+        raise ValueError("a DSM is float32, got %s" % (dsm.dtype,))
+    gh, gw = int(dsm.shape[0]), int(dsm.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("a DSM has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    return dsm
+
+
 def _as_list(x, n=None):
     if x is None:
         return [None] * n
@@ -90,18 +137,45 @@ def _as_list(x, n=None):
     return [x]
 
 
+def _rpc_list(rpcs):
+    """One RPC, a list of RPCs, or an array of RPCs along its first axis -> a list."""
+    if isinstance(rpcs, (list, tuple)):
+        return list(rpcs)
+    if isinstance(rpcs, (np.ndarray, torch.Tensor)) and rpcs.ndim >= 2:
+        return [rpcs[i] for i in range(rpcs.shape[0])]
+    return [rpcs]
+
+
+def _rpc_checked(rpc):
+    r = torch.as_tensor(rpc, dtype=torch.float64).reshape(-1) if not isinstance(rpc, torch.Tensor) else rpc.reshape(-1)
+    if r.numel() != 170:
+        raise ValueError("rpc vectors must hold 170 values, got %d" % r.numel())
+    return r
+
+
+def _valid_range(z, nodata, lower=True):
+    """(lowest, highest) valid cell, reduced on the device (the kernel's validity test: float32 cells against (float)nodata).
+    lower=False leaves the lowest out (None) for the callers that march upwards only."""
+    valid = torch.isfinite(z) & (z != float(np.float32(nodata)))
+    h_hi = float(torch.where(valid, z, torch.full_like(z, -math.inf)).amax())
+    if not math.isfinite(h_hi):
+        raise ValueError("the DSM has no valid cell")
+    h_lo = float(torch.where(valid, z, torch.full_like(z, math.inf)).amin()) if lower else None
+    return h_lo, h_hi
+
+
 def _maps(heights, rpcs, masks, dev):
     hs = _as_list(heights)
-    rs = _as_list(rpcs) if not (isinstance(rpcs, (np.ndarray, torch.Tensor)) and rpcs.ndim == 1) else [rpcs]
+    rs = _rpc_list(rpcs)
     ms = _as_list(masks, len(hs))
     if len(rs) != len(hs) or len(ms) != len(hs):
         raise ValueError("one RPC (and one mask, if any) per height map: %d maps, %d rpcs, %d masks" % (len(hs), len(rs), len(ms)))
     out = []
     for h, r, m in zip(hs, rs, ms):
-        h = torch.as_tensor(h).to(device=dev, dtype=torch.float32).contiguous()
+        h, _ = _to_device(h, torch.float32, dev)
         if h.ndim != 2:
             raise ValueError("height maps are (H, W), got %s" % (tuple(h.shape),))
-        r = torch.as_tensor(r).to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        r = _to_device(r, torch.float64, dev)[0].reshape(-1)
         if r.numel() != 170:
             raise ValueError("rpc vectors must hold 170 values")
         if m is not None:
@@ -113,18 +187,17 @@ def _maps(heights, rpcs, masks, dev):
     return out
 
 
-def _vp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+def _call(dev, name, *args):
+    """One native call on dev's current stream: tensors go as device pointers, numpy arrays as host pointers, None as NULL."""
+    args = [_lib.ptr(a) if isinstance(a, torch.Tensor) else a.ctypes.data_as(ctypes.c_void_p) if isinstance(a, np.ndarray) else a
+            for a in args]
+    with torch.cuda.device(dev):
+        _lib.call(name, *args, _lib.current_stream(dev))
 
 
 def _bin(h, r, m, tm7, grid4, gw, gh, cell, count, east=None, north=None):
-    dev = h.device
     H, W = h.shape
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_dsm_bin", _lib.ptr(h), _lib.ptr(m) if m is not None else None, _lib.ptr(r), H, W,
-                  _vp(tm7), _vp(grid4), gw, gh, _lib.ptr(cell), _lib.ptr(count),
-                  _lib.ptr(east) if east is not None else None, _lib.ptr(north) if north is not None else None,
-                  _lib.current_stream(dev))
+    _call(h.device, "smvs_rpc_dsm_bin", h, m, r, H, W, tm7, grid4, gw, gh, cell, count, east, north)
 
 
 def project_to_map(heights, rpcs, projection, masks=None):
@@ -193,9 +266,7 @@ def reduce_cells(cell, height, count, grid, mode="median", nodata=-999.0):
         raise ValueError("unsupported DSM size: %d points, %d x %d cells (limits: 2^31 points, 2^31 cells)" % (n, gw, gh))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty((gh, gw), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("smvs_dsm_reduce", _lib.ptr(cell), _lib.ptr(height), n, _lib.ptr(count), gw, gh, MODES[mode],
-                  float(nodata), _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.current_stream(dev))
+    _call(dev, "smvs_dsm_reduce", cell, height, n, count, gw, gh, MODES[mode], float(nodata), out, ws, nbytes)
     return out
 
 
@@ -222,9 +293,7 @@ def heights_to_dsm(heights, rpcs, projection, grid, masks=None, mode="median", n
         _bin(h, r, m, tm7, grid4, gw, gh, cell[at:at + h.numel()], count)
         at += h.numel()
     out = reduce_cells(cell, flat, count, grid, mode, nodata)
-    cnt = count.reshape(gh, gw)
-    if as_numpy:
-        out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
+    out, cnt = _back(as_numpy, out, count.reshape(gh, gw))
     return (out, cnt) if return_count else out
 
 
@@ -260,29 +329,16 @@ def render_heights(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999
     tol = float(tol)
     if not (tol > 0.0 and math.isfinite(tol)):
         raise ValueError("tol must be positive and finite, got %r" % tol)
-    if not isinstance(dsm, torch.Tensor):
-        dsm = np.asarray(dsm, dtype=np.float32)
-    if tuple(dsm.shape) != (grid.height, grid.width):
-        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
-    r = torch.as_tensor(rpc, dtype=torch.float64).reshape(-1) if not isinstance(rpc, torch.Tensor) else rpc.reshape(-1)
-    if r.numel() != 170:
-        raise ValueError("rpc vectors must hold 170 values, got %d" % r.numel())
-    as_numpy = not isinstance(dsm, torch.Tensor)
+    dsm = _dsm_converted(dsm, grid)
+    r = _rpc_checked(rpc)
     dev = _dev()
-    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
-    r = r.to(device=dev, dtype=torch.float64).contiguous()
-    valid = torch.isfinite(z) & (z != float(np.float32(nodata)))      # the kernel's test: float32 cells against (float)nodata
-    lo = torch.where(valid, z, torch.full_like(z, math.inf)).amin()
-    hi = torch.where(valid, z, torch.full_like(z, -math.inf)).amax()
-    h_lo, h_hi = float(lo), float(hi)
-    if not math.isfinite(h_lo):
-        raise ValueError("the DSM has no valid cell")
+    z, as_numpy = _to_device(dsm, torch.float32, dev)
+    r, _ = _to_device(r, torch.float64, dev)
+    h_lo, h_hi = _valid_range(z, nodata)
     out = torch.empty((H, W), dtype=torch.float32, device=dev)
-    grid4, tm7 = grid.grid4(), projection.tm7()
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_dsm_render", _lib.ptr(z), grid.width, grid.height, _vp(grid4), float(nodata), _vp(tm7), _lib.ptr(r),
-                  H, W, x0, y0, h_lo, h_hi, tol, _lib.ptr(out), _lib.current_stream(dev))
-    return out.cpu().numpy() if as_numpy else out
+    _call(dev, "smvs_rpc_dsm_render", z, grid.width, grid.height, grid.grid4(), float(nodata), projection.tm7(), r,
+          H, W, x0, y0, h_lo, h_hi, tol, out)
+    return _back(as_numpy, out)
 
 
 # ---- clean-up: speckle removal and void filling ---------------------------------------------------------------------------------
@@ -296,29 +352,6 @@ def _int_checked(v, name, lo, hi):
     return int(v)
 
 
-def _grid_checked(dsm):
-    """A (gh, gw) float32 grid, numpy or tensor, checked before any device work: no conversion of other dtypes, the
-    operations copy bits."""
-    if not isinstance(dsm, torch.Tensor):
-        dsm = np.asarray(dsm)
-    if dsm.ndim != 2:
-        raise ValueError("a DSM is (gh, gw), got shape %s" % (tuple(dsm.shape),))
-    if dsm.dtype not in (np.float32, torch.float32):
-        raise ValueError("a DSM is float32, got %s" % (dsm.dtype,))
-    gh, gw = int(dsm.shape[0]), int(dsm.shape[1])
-    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
-        raise ValueError("a DSM has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
-    return dsm
-
-
-def _grid_on_device(dsm):
-    """(contiguous device tensor, whether the caller gave numpy)."""
-    as_numpy = not isinstance(dsm, torch.Tensor)
-    dev = _dev() if as_numpy or not dsm.is_cuda else dsm.device
-    z = (torch.from_numpy(np.ascontiguousarray(dsm)) if as_numpy else dsm).to(device=dev).contiguous()
-    return z, as_numpy
-
-
 def despike(dsm, nodata=-999.0, radius=2, thresh=10.0, min_valid=3, return_removed=False):
     """Remove speckles from a DSM (include/satmvs.h smvs_dsm_despike): a valid cell becomes `nodata` where
     the (2 radius + 1)^2 window around it (clipped at the border, the cell included) holds fewer than min_valid valid cells, or
@@ -326,21 +359,18 @@ def despike(dsm, nodata=-999.0, radius=2, thresh=10.0, min_valid=3, return_remov
     float32, numpy or a device tensor, left untouched; radius 1, 2 or 3; thresh finite and >= 0; 1 <= min_valid <= window size.
     -> the cleaned (gh, gw) float32 (and, with return_removed, a uint8 map of the removed cells); numpy if the DSM came as numpy,
     device tensors otherwise."""
-    dsm = _grid_checked(dsm)
+    dsm = _dsm_bits(dsm)
     radius = _int_checked(radius, "radius", 1, 3)
     min_valid = _int_checked(min_valid, "min_valid", 1, (2 * radius + 1) ** 2)
     thresh = float(thresh)
     if not (math.isfinite(thresh) and thresh >= 0.0):
         raise ValueError("thresh must be finite and >= 0, got %r" % thresh)
-    z, as_numpy = _grid_on_device(dsm)
+    z, as_numpy = _to_device(dsm)
     gh, gw = z.shape
     out = torch.empty_like(z)
     removed = torch.empty((gh, gw), dtype=torch.uint8, device=z.device) if return_removed else None
-    with torch.cuda.device(z.device):
-        _lib.call("smvs_dsm_despike", _lib.ptr(z), gw, gh, float(nodata), radius, thresh, min_valid, _lib.ptr(out),
-                  _lib.ptr(removed) if removed is not None else None, _lib.current_stream(z.device))
-    if as_numpy:
-        out, removed = out.cpu().numpy(), removed.cpu().numpy() if removed is not None else None
+    _call(z.device, "smvs_dsm_despike", z, gw, gh, float(nodata), radius, thresh, min_valid, out, removed)
+    out, removed = _back(as_numpy, out, removed)
     return (out, removed) if return_removed else out
 
 
@@ -353,12 +383,12 @@ def fill_voids(dsm, nodata=-999.0, max_steps=32, min_hits=3, method="idw", retur
     a device tensor, left untouched; 1 <= max_steps <= 4096; 1 <= min_hits <= 8.
     -> the filled (gh, gw) float32 (and, with return_hits, a uint8 map: 255 where the input cell was valid, else its number of
     hits); numpy if the DSM came as numpy, device tensors otherwise."""
-    dsm = _grid_checked(dsm)
+    dsm = _dsm_bits(dsm)
     if method not in FILL_METHODS:
         raise ValueError("method must be one of %s, got %r" % (sorted(FILL_METHODS), method))
     max_steps = _int_checked(max_steps, "max_steps", 1, MAX_FILL_STEPS)
     min_hits = _int_checked(min_hits, "min_hits", 1, 8)
-    z, as_numpy = _grid_on_device(dsm)
+    z, as_numpy = _to_device(dsm)
     gh, gw = z.shape
     nbytes = _lib.load().smvs_dsm_fill_workspace_bytes(gw, gh, max_steps)
     if nbytes == 0:
@@ -366,11 +396,8 @@ def fill_voids(dsm, nodata=-999.0, max_steps=32, min_hits=3, method="idw", retur
     ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
     out = torch.empty_like(z)
     hits = torch.empty((gh, gw), dtype=torch.uint8, device=z.device) if return_hits else None
-    with torch.cuda.device(z.device):
-        _lib.call("smvs_dsm_fill", _lib.ptr(z), gw, gh, float(nodata), max_steps, min_hits, FILL_METHODS[method], _lib.ptr(out),
-                  _lib.ptr(hits) if hits is not None else None, _lib.ptr(ws), nbytes, _lib.current_stream(z.device))
-    if as_numpy:
-        out, hits = out.cpu().numpy(), hits.cpu().numpy() if hits is not None else None
+    _call(z.device, "smvs_dsm_fill", z, gw, gh, float(nodata), max_steps, min_hits, FILL_METHODS[method], out, hits, ws, nbytes)
+    out, hits = _back(as_numpy, out, hits)
     return (out, hits) if return_hits else out
 
 
@@ -395,18 +422,16 @@ def morph(dsm, radius, op, nodata=-999.0):
     the erosion, "close" = the erosion of the dilation.  Invalid cells are transparent to the windows and are copied bit for
     bit; of two zeros -0.0 is the lower.  dsm (gh, gw) float32, numpy or a device tensor, left untouched; 1 <= radius <= 256.
     -> (gh, gw) float32; numpy if the DSM came as numpy, a device tensor otherwise."""
-    dsm = _grid_checked(dsm)
+    dsm = _dsm_bits(dsm)
     radius = _int_checked(radius, "radius", 1, MAX_MORPH_RADIUS)
     if op not in MORPH_OPS:
         raise ValueError("op must be one of %s, got %r" % (sorted(MORPH_OPS), op))
-    z, as_numpy = _grid_on_device(dsm)
+    z, as_numpy = _to_device(dsm)
     gh, gw = z.shape
     ws, nbytes = _morph_workspace(z, radius)
     out = torch.empty_like(z)
-    with torch.cuda.device(z.device):
-        _lib.call("smvs_dsm_morph", _lib.ptr(z), gw, gh, float(nodata), radius, MORPH_OPS[op], _lib.ptr(out), _lib.ptr(ws), nbytes,
-                  _lib.current_stream(z.device))
-    return out.cpu().numpy() if as_numpy else out
+    _call(z.device, "smvs_dsm_morph", z, gw, gh, float(nodata), radius, MORPH_OPS[op], out, ws, nbytes)
+    return _back(as_numpy, out)
 
 
 def ground_schedule(cell, max_radius=16, slope=0.3, dh0=1.5, dh_max=6.0):
@@ -452,24 +477,21 @@ def ground_filter(dsm, cell=None, nodata=-999.0, max_radius=16, slope=0.3, dh0=1
     untouched.
     -> dtm (gh, gw) float32: the input's bits at ground cells, nodata at removed cells, invalid cells copied (and, with
     return_class, cls uint8: 0 invalid input, 1 ground, 2 + k removed at level k); numpy if the DSM came as numpy."""
-    dsm = _grid_checked(dsm)
+    dsm = _dsm_bits(dsm)
     if schedule is not None:
         radii, thresholds = _schedule_checked(*schedule)
     else:
         if cell is None:
             raise ValueError("ground_filter needs the cell size [m] (or a schedule)")
         radii, thresholds = ground_schedule(cell, max_radius, slope, dh0, dh_max)
-    z, as_numpy = _grid_on_device(dsm)
+    z, as_numpy = _to_device(dsm)
     gh, gw = z.shape
     ws, nbytes = _morph_workspace(z, radii[-1])
     dtm = torch.empty_like(z)
     cls = torch.empty((gh, gw), dtype=torch.uint8, device=z.device)
     r_arr, t_arr = np.asarray(radii, np.int32), np.asarray(thresholds, np.float64)
-    with torch.cuda.device(z.device):
-        _lib.call("smvs_dsm_ground", _lib.ptr(z), gw, gh, float(nodata), _vp(r_arr), _vp(t_arr), len(radii), _lib.ptr(dtm), _lib.ptr(cls),
-                  _lib.ptr(ws), nbytes, _lib.current_stream(z.device))
-    if as_numpy:
-        dtm, cls = dtm.cpu().numpy(), cls.cpu().numpy()
+    _call(z.device, "smvs_dsm_ground", z, gw, gh, float(nodata), r_arr, t_arr, len(radii), dtm, cls, ws, nbytes)
+    dtm, cls = _back(as_numpy, dtm, cls)
     return (dtm, cls) if return_class else dtm
 
 
@@ -477,8 +499,7 @@ def extract_dtm(dsm, grid, nodata=-999.0, max_radius=16, slope=0.3, dh0=1.5, dh_
     """A DTM from a DSM: ground_filter with cell = max(grid.xres, grid.yres), then fill_voids(method="idw") under what was
     removed.  The fill also closes voids the input already had within max_steps cells, which is what a DTM wants; voids out of
     reach stay.  -> dtm (gh, gw) float32 (and the filter's cls with return_class)."""
-    if tuple(dsm.shape) != (grid.height, grid.width):
-        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
+    _on_grid(dsm, grid)
     max_steps = _int_checked(max_steps, "max_steps", 1, MAX_FILL_STEPS)
     min_hits = _int_checked(min_hits, "min_hits", 1, 8)
     holes, cls = ground_filter(dsm, max(float(grid.xres), float(grid.yres)), nodata, max_radius, slope, dh0, dh_max, return_class=True)
@@ -499,28 +520,12 @@ def ndsm(dsm, dtm, nodata=-999.0, clamp=True):
     d = a - b
     if clamp:
         d = torch.where(d > 0.0, d, torch.zeros_like(d))                  # every zero leaves as +0.0
-    out = torch.where(both, d, torch.full_like(d, nd))
-    return out.cpu().numpy() if as_numpy else out
+    return _back(as_numpy, torch.where(both, d, torch.full_like(d, nd)))
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
 ORTHO_STATES = ("no height", "outside", "occluded", "visible")     # the state codes 0 .. 3 of visibility() / smvs_rpc_ortho
 MAX_CHANNELS = 16
-
-
-def _dsm_checked(dsm, grid):
-    if not isinstance(dsm, torch.Tensor):
-        dsm = np.asarray(dsm, dtype=np.float32)
-    if tuple(dsm.shape) != (grid.height, grid.width):
-        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (tuple(dsm.shape), grid.height, grid.width))
-    return dsm
-
-
-def _rpc_checked(rpc):
-    r = torch.as_tensor(rpc, dtype=torch.float64).reshape(-1) if not isinstance(rpc, torch.Tensor) else rpc.reshape(-1)
-    if r.numel() != 170:
-        raise ValueError("rpc vectors must hold 170 values, got %d" % r.numel())
-    return r
 
 
 def _occ_tol_checked(occ_tol):
@@ -530,22 +535,9 @@ def _occ_tol_checked(occ_tol):
     return t
 
 
-def _h_hi(z, nodata):
-    """The highest valid cell, reduced on the device (the kernel's validity test: float32 cells against (float)nodata)."""
-    valid = torch.isfinite(z) & (z != float(np.float32(nodata)))
-    h_hi = float(torch.where(valid, z, torch.full_like(z, -math.inf)).amax())
-    if not math.isfinite(h_hi):
-        raise ValueError("the DSM has no valid cell")
-    return h_hi
-
-
 def _ortho_call(z, grid, nodata, tm7, r, image, H, W, C, x0, y0, h_hi, occlusion, occ_tol, view, ortho, source, state):
-    dev = z.device
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_ortho", _lib.ptr(z), grid.width, grid.height, _vp(grid.grid4()), float(nodata), _vp(tm7), _lib.ptr(r),
-                  _lib.ptr(image) if image is not None else None, H, W, C, x0, y0, h_hi, 1 if occlusion else 0, occ_tol, view,
-                  _lib.ptr(ortho) if ortho is not None else None, _lib.ptr(source) if source is not None else None,
-                  _lib.ptr(state) if state is not None else None, _lib.current_stream(dev))
+    _call(z.device, "smvs_rpc_ortho", z, grid.width, grid.height, grid.grid4(), float(nodata), tm7, r, image, H, W, C, x0, y0,
+          h_hi, 1 if occlusion else 0, occ_tol, view, ortho, source, state)
 
 
 def visibility(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999.0, occlusion=True, occ_tol=0.5):
@@ -556,16 +548,15 @@ def visibility(dsm, grid, rpc, projection, shape, origin=(0, 0), nodata=-999.0, 
     cell.  Numpy if the DSM came as numpy, a device tensor otherwise."""
     H, W, x0, y0 = _tile(shape, origin)
     occ_tol = _occ_tol_checked(occ_tol)
-    dsm = _dsm_checked(dsm, grid)
+    dsm = _dsm_converted(dsm, grid)
     r = _rpc_checked(rpc)
-    as_numpy = not isinstance(dsm, torch.Tensor)
     dev = _dev()
-    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
-    r = r.to(device=dev, dtype=torch.float64).contiguous()
-    h_hi = _h_hi(z, nodata)
+    z, as_numpy = _to_device(dsm, torch.float32, dev)
+    r, _ = _to_device(r, torch.float64, dev)
+    _, h_hi = _valid_range(z, nodata, lower=False)
     state = torch.empty((grid.height, grid.width), dtype=torch.uint8, device=dev)
     _ortho_call(z, grid, nodata, projection.tm7(), r, None, H, W, 1, x0, y0, h_hi, occlusion, occ_tol, 0, None, None, state)
-    return state.cpu().numpy() if as_numpy else state
+    return _back(as_numpy, state)
 
 
 def _images_checked(images):
@@ -643,12 +634,7 @@ def orthorectify(images, rpcs, dsm, grid, projection, origins=None, nodata=-999.
     (-1: none); numpy if the DSM came as numpy, device tensors otherwise."""
     ims = _images_checked(images)
     n = len(ims)
-    if isinstance(rpcs, (list, tuple)):
-        rs = list(rpcs)
-    elif isinstance(rpcs, (np.ndarray, torch.Tensor)) and rpcs.ndim == 2:
-        rs = [rpcs[i] for i in range(rpcs.shape[0])]
-    else:
-        rs = [rpcs]
+    rs = _rpc_list(rpcs)
     if len(rs) != n:
         raise ValueError("one RPC per image: %d images, %d rpcs" % (n, len(rs)))
     rs = [_rpc_checked(r) for r in rs]
@@ -662,11 +648,10 @@ def orthorectify(images, rpcs, dsm, grid, projection, origins=None, nodata=-999.
     occ_tol = _occ_tol_checked(occ_tol)
     seq = _order_checked(order, n)
     fill = float(fill)
-    dsm = _dsm_checked(dsm, grid)
-    as_numpy = not isinstance(dsm, torch.Tensor)
+    dsm = _dsm_converted(dsm, grid)
     dev = _dev()
-    z = torch.as_tensor(dsm).to(device=dev, dtype=torch.float32).contiguous()
-    h_hi = _h_hi(z, nodata)
+    z, as_numpy = _to_device(dsm, torch.float32, dev)
+    _, h_hi = _valid_range(z, nodata, lower=False)
     if seq == "given":
         seq = list(range(n))
     elif seq == "nadir":
@@ -676,13 +661,11 @@ def orthorectify(images, rpcs, dsm, grid, projection, origins=None, nodata=-999.
     source = torch.full((grid.height, grid.width), -1, dtype=torch.int32, device=dev)
     tm7 = projection.tm7()
     for v in seq:
-        im = ims[v] if isinstance(ims[v], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ims[v]))
-        im = im.to(device=dev, dtype=torch.float32).contiguous()
-        r = rs[v].to(device=dev, dtype=torch.float64).contiguous()
+        im, _ = _to_device(ims[v], torch.float32, dev)
+        r, _ = _to_device(rs[v], torch.float64, dev)
         H, W, x0, y0 = tiles[v]
         _ortho_call(z, grid, nodata, tm7, r, im, H, W, C, x0, y0, h_hi, occlusion, occ_tol, v, ortho, source, None)
-    if as_numpy:
-        ortho, source = ortho.cpu().numpy(), source.cpu().numpy()
+    ortho, source = _back(as_numpy, ortho, source)
     return (ortho, source) if return_source else ortho
 
 
@@ -716,8 +699,7 @@ def write_dsm(path, dsm, grid):
     from PIL import Image
     a = dsm.detach().cpu().numpy() if isinstance(dsm, torch.Tensor) else np.asarray(dsm)
     a = np.ascontiguousarray(a, dtype=np.float32)
-    if a.shape != (grid.height, grid.width):
-        raise ValueError("dsm shape %s differs from the grid's (%d, %d)" % (a.shape, grid.height, grid.width))
+    _on_grid(a, grid)
     Image.fromarray(a, mode="F").save(path, format="TIFF")
     _write_tfw(path, grid)
     return path

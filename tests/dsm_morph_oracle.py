@@ -7,22 +7,9 @@ A field is a uint32 array of keys: key(z) orders like z, with -0.0 below +0.0, a
 of a window is the highest of the complements, so there is one window operation, the maximum, with 0 as its identity."""
 import numpy as np
 
+from dsm_testkit import f2key, key2f, same_bits, valid  # noqa: F401  (re-exported)
+
 OPS = ("erode", "dilate", "open", "close")
-
-
-def valid(z, nodata):
-    z = np.asarray(z, np.float32)
-    return np.isfinite(z) & (z != np.float32(nodata))
-
-
-def f2key(z):
-    u = np.ascontiguousarray(z, np.float32).view(np.uint32)
-    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
-
-
-def key2f(k):
-    k = np.ascontiguousarray(k, np.uint32)
-    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7fffffff), ~k).astype(np.uint32).view(np.float32)
 
 
 def keys_of(z, nodata):
@@ -172,11 +159,6 @@ def ground_brute(dsm, radii, thresholds, nodata=-999.0):
 
 
 # ---- what the tests compare and build scenes from ----------------------------------------------------------------------------
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def scene(gh, gw, seed=0, voids=0.1):
     """Terrain with blocks, both zeros, +-inf and NaN cells, a nodata hole and random voids (NaN and nodata mixed)."""
     rng = np.random.default_rng(seed)

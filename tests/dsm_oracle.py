@@ -2,6 +2,8 @@
 code (pinned against tests/golden/tm.npz), the bin rule and a per-cell reduce by np.lexsort."""
 import numpy as np
 
+from dsm_testkit import f2key as keys  # noqa: F401  (re-exported)
+
 PI = 3.14159265358979323846
 
 
@@ -72,11 +74,6 @@ def cells(east, north, grid4, gw, gh):
     out = np.full(np.shape(east), -1, np.int64)
     out[ok] = (row[ok].astype(np.int64) * gw + col[ok].astype(np.int64))
     return out
-
-
-def keys(h):
-    u = np.asarray(h, np.float32).view(np.uint32)
-    return np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint32)
 
 
 def reduce(cell, height, ncells, mode, nodata):

@@ -8,14 +8,12 @@ fill():    the directional search as shifted-array passes: step k looks, for eve
            the reaches, not max_steps per cell."""
 import numpy as np
 
+import dsm_testkit as kit
+from dsm_testkit import same_bits, valid  # noqa: F401  (re-exported)
+
 # (dcol, drow), rows running south: E, NE, N, NW, W, SW, S, SE
 DIRS = ((1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0), (-1, 1), (0, 1), (1, 1))
 METHODS = ("idw", "nearest", "min")
-
-
-def valid(z, nodata):
-    z = np.asarray(z, np.float32)
-    return np.isfinite(z) & (z != np.float32(nodata))
 
 
 def median_of_sorted(v, n):
@@ -168,25 +166,7 @@ def fill_brute(dsm, nodata=-999.0, max_steps=32, min_hits=3, method="idw"):
 
 
 # ---- what the tests compare and build scenes from ----------------------------------------------------------------------------
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def scene(gh, gw, seed=0, voids=0.1, salt=0.02):
-    """The render tests' scene on a (gh, gw) grid of 5 m cells: terrain, two blocks, a NaN hole and a nodata hole, plus seeded
-    salt noise of both signs (30 - 80 m) and random voids (NaN and nodata mixed)."""
-    rng = np.random.default_rng(seed)
+    """dsm_testkit.scene on a (gh, gw) grid of 5 m cells, with seeded salt noise and random voids."""
     rows, cols = np.mgrid[0:gh, 0:gw].astype(np.float64)
-    E, N = 5.0 * cols, -5.0 * rows
-    z = (130.0 + 20.0 * np.sin(E / 53.0) * np.cos(N / 71.0)).astype(np.float32)
-    r0, c0 = gh // 2 - 3, gw // 2 - 3
-    z[max(r0, 0):r0 + 6, max(c0, 0):c0 + 6] += 40.0
-    z[max(r0 - 12, 0):max(r0 - 8, 0), c0 + 10:c0 + 14] += 25.0
-    spikes = rng.random((gh, gw)) < salt
-    z[spikes] += (rng.uniform(30.0, 80.0, (gh, gw)) * rng.choice([-1.0, 1.0], (gh, gw)))[spikes].astype(np.float32)
-    z[max(r0, 0):r0 + 3, c0 + 6:c0 + 8] = np.nan
-    z[r0 + 6:r0 + 8, max(c0, 0):c0 + 4] = -999.0
-    gone = rng.random((gh, gw)) < voids
-    z[gone] = np.where(rng.random((gh, gw)) < 0.5, np.float32(np.nan), np.float32(-999.0))[gone]
-    return z
+    return kit.scene(5.0 * cols, -5.0 * rows, seed=seed, voids=voids, salt=salt)

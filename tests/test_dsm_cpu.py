@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import dsm_oracle as orc
+from dsm_testkit import lib  # noqa: F401  (fixtures)
 
 
 @pytest.mark.parametrize("name", ["whu", "example"])
@@ -85,13 +86,6 @@ def test_metrics_known_answers():
     assert m["completeness"] == pytest.approx(3 / 5)
     assert m["mae"] == pytest.approx(3.0) and m["rmse"] == pytest.approx(np.sqrt(65 / 3))
     assert m["<2.5"] == pytest.approx(2 / 3) and m["<7.5"] == pytest.approx(2 / 3)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from satmvs_amd import _lib, build
-    build.build()
-    return _lib.load()
 
 
 def test_dsm_entries_reject_bad_arguments_without_a_gpu(lib):

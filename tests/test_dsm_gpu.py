@@ -6,17 +6,11 @@ import pytest
 import torch
 
 import dsm_oracle as orc
+from dsm_testkit import dev  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 MODES = ("median", "mean", "min", "max")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("the GPU suite needs an MI355X")
-    return torch.device("cuda", 0)
 
 
 def _ulp_diff(a, b):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import dsm_morph_oracle as mo
+from dsm_testkit import lib  # noqa: F401  (fixtures)
 
 ND = np.float32(-999.0)
 
@@ -141,13 +142,6 @@ def test_ndsm():
 
 
 # ---- argument checks -----------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from satmvs_amd import _lib, build
-    build.build()
-    return _lib.load()
-
-
 def test_morph_entries_reject_bad_arguments_without_a_gpu(lib):
     from satmvs_amd import _lib
     a, b, m, w = C.c_void_p(1 << 20), C.c_void_p(2 << 20), C.c_void_p(3 << 20), C.c_void_p(4 << 20)

@@ -12,26 +12,13 @@ import torch
 import dsm_morph_oracle as mo
 import dsm_post_oracle as po
 import dsm_render_oracle as ro
+from dsm_testkit import dev, same as _same  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ND = np.float32(-999.0)
 SIZES = [(1, 1), (1, 70), (67, 3), (128, 160), (257, 301)]                 # those of test_dsm_post_gpu
 RADII = [1, 2, 3, 7, 16, 64, 256]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("the GPU suite needs an MI355X")
-    return torch.device("cuda", 0)
-
-
-def _same(got, want, what):
-    """Equal bits (so equal NaN positions and payloads) for float32 grids, equal values for uint8 maps."""
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    g, w = (got.view(np.uint32), want.view(np.uint32)) if got.dtype == np.float32 else (got, want)
-    assert np.array_equal(g, w), (what, int((g != w).sum()), np.argwhere(g != w)[:5].tolist())
 
 
 def _morph_all(z, radii=RADII, nodata=-999.0):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import dsm_post_oracle as po
+from dsm_testkit import lib  # noqa: F401  (fixtures)
 
 ND = np.float32(-999.0)
 
@@ -156,13 +157,6 @@ def test_crop_property_of_the_oracle():
 
 
 # ---- argument checks -----------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from satmvs_amd import _lib, build
-    build.build()
-    return _lib.load()
-
-
 def test_despike_entry_rejects_bad_arguments_without_a_gpu(lib):
     from satmvs_amd import _lib
     a, b, m = C.c_void_p(1 << 20), C.c_void_p(2 << 20), C.c_void_p(3 << 20)

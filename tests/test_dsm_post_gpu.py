@@ -8,29 +8,12 @@ import torch
 
 import dsm_post_oracle as po
 import dsm_render_oracle as ro
+from dsm_testkit import dev, same as _same  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ND = np.float32(-999.0)
 SIZES = [(1, 1), (1, 70), (67, 3), (128, 160), (257, 301)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("the GPU suite needs an MI355X")
-    return torch.device("cuda", 0)
-
-
-def _same(got, want, what):
-    """Equal bits (so equal NaN positions and payloads) for float32 grids, equal values for uint8 maps."""
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    if got.dtype == np.float32:
-        g, w = got.view(np.uint32), want.view(np.uint32)
-        assert np.array_equal(np.isnan(got), np.isnan(want)), what
-    else:
-        g, w = got, want
-    assert np.array_equal(g, w), (what, int((g != w).sum()), np.argwhere(g != w)[:5].tolist())
 
 
 def _despike_both(z, **kw):

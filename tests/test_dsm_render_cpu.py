@@ -6,19 +6,10 @@ import numpy as np
 import pytest
 
 import dsm_render_oracle as ro
+from dsm_testkit import lib, tilted_fixture, tm7  # noqa: F401  (fixtures)
 
 H, W = 24, 32
-
-
-@pytest.fixture(scope="module")
-def tm7():
-    from satmvs_amd.transverse_mercator import whu_tlc_projection
-    return whu_tlc_projection().tm7()
-
-
-@pytest.fixture(scope="module")
-def tilted():
-    return ro.view_rpc(H, W, 0.4, seed=3)
+tilted = tilted_fixture(H, W, seed=3)
 
 
 def test_constant_dsm_renders_the_constant(tm7, tilted):
@@ -93,13 +84,6 @@ def test_ray_entering_the_grid_just_before_the_hit_is_invalid(tm7, tilted):
     assert np.isnan(o["height"][entering]).all()
     assert (np.abs(o["height"][seen] - 100.0) <= 1e-3).all()
     assert (o["K"] == K).all()
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from satmvs_amd import _lib, build
-    build.build()
-    return _lib.load()
 
 
 def test_render_entry_rejects_bad_arguments_without_a_gpu(lib, tm7):

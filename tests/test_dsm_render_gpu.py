@@ -6,34 +6,17 @@ import pytest
 import torch
 
 import dsm_render_oracle as ro
+from dsm_testkit import dev, proj, scene, views_fixture  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 H, W = 128, 160
 TOL = 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("the GPU suite needs an MI355X")
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def proj():
-    from satmvs_amd.transverse_mercator import whu_tlc_projection
-    return whu_tlc_projection()
-
-
-@pytest.fixture(scope="module")
-def views():
-    return {s: ro.view_rpc(H, W, s, seed=11) for s in (0.0, 0.4, -0.4)}
+views = views_fixture(H, W, seed=11)
 
 
 def _terrain(grid, base=130.0, amp=20.0):
-    E, N = ro.cell_centres(grid)
-    return (base + amp * np.sin(E / 53.0) * np.cos(N / 71.0)).astype(np.float32)
+    return scene(*ro.cell_centres(grid), blocks=False, holes=False, base=base, amp=amp)
 
 
 def _agree(got, o, tol=TOL):

@@ -9,19 +9,10 @@ import pytest
 
 import dsm_render_oracle as ro
 import ortho_oracle as oo
+from dsm_testkit import lib, tilted_fixture, tm7  # noqa: F401  (fixtures)
 
 H, W = 24, 32
-
-
-@pytest.fixture(scope="module")
-def tm7():
-    from satmvs_amd.transverse_mercator import whu_tlc_projection
-    return whu_tlc_projection().tm7()
-
-
-@pytest.fixture(scope="module")
-def tilted():
-    return ro.view_rpc(H, W, 0.4, seed=3)
+tilted = tilted_fixture(H, W, seed=3)
 
 
 def test_constant_dsm_is_visible_inside_the_footprint(tm7, tilted):
@@ -71,13 +62,6 @@ def test_block_hides_the_ground_behind_it(tm7, tilted):
     off = oo.ortho(z, grid, -999.0, tm7, tilted, shape=(H, W), occlusion=False)
     assert not (off["state"] == oo.OCCLUDED).any()
     assert np.array_equal(off["state"] == oo.VISIBLE, (o["state"] == oo.VISIBLE) | occ)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from satmvs_amd import _lib, build
-    build.build()
-    return _lib.load()
 
 
 def test_ortho_entry_rejects_bad_arguments_without_a_gpu(lib, tm7):

@@ -7,28 +7,12 @@ import torch
 
 import dsm_render_oracle as ro
 import ortho_oracle as oo
+from dsm_testkit import dev, proj, scene, views_fixture  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 H, W = 128, 160
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("the GPU suite needs an MI355X")
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def proj():
-    from satmvs_amd.transverse_mercator import whu_tlc_projection
-    return whu_tlc_projection()
-
-
-@pytest.fixture(scope="module")
-def views():
-    return {s: ro.view_rpc(H, W, s, seed=11) for s in (0.0, 0.4, -0.4)}
+views = views_fixture(H, W, seed=11)
 
 
 def _image(shape, C, seed):
@@ -36,15 +20,7 @@ def _image(shape, C, seed):
 
 
 def _scene(grid):
-    """Terrain, two blocks, a NaN hole and a nodata hole (render tests' scene)."""
-    E, N = ro.cell_centres(grid)
-    z = (130.0 + 20.0 * np.sin(E / 53.0) * np.cos(N / 71.0)).astype(np.float32)
-    r0, c0 = grid.height // 2 - 3, grid.width // 2 - 3
-    z[r0:r0 + 6, c0:c0 + 6] += 40.0
-    z[r0 - 12:r0 - 8, c0 + 10:c0 + 14] += 25.0
-    z[r0:r0 + 3, c0 + 6:c0 + 8] = np.nan
-    z[r0 + 6:r0 + 8, c0:c0 + 4] = -999.0
-    return z
+    return scene(*ro.cell_centres(grid))
 
 
 def _agree_states(got, o, shape):

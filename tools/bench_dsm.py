@@ -19,26 +19,10 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from dsm_bench_common import stats, synth_heights  # noqa: E402
 from satmvs_amd import dsm, rpc_synth  # noqa: E402
 from satmvs_amd.transverse_mercator import whu_tlc_projection  # noqa: E402
-
-
-def synth_heights(n_views, size, dev, seed=0):
-    g = torch.Generator(device=dev).manual_seed(seed)
-    y = torch.arange(size, device=dev, dtype=torch.float32)[:, None]
-    x = torch.arange(size, device=dev, dtype=torch.float32)[None, :]
-    base = 150.0 + 60.0 * torch.sin(x / 97.0) * torch.cos(y / 131.0)
-    out = []
-    for _ in range(n_views):
-        h = base + 2.0 * torch.randn((size, size), device=dev, generator=g)
-        h[torch.rand((size, size), device=dev, generator=g) < 0.01] = float("nan")    # holes, as after filtering
-        out.append(h.contiguous())
-    return out
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return {"min": ts[0], "median": ts[len(ts) // 2], "max": ts[-1], "reps": len(ts)}
 
 
 def numpy_oracle_one_map(h, rpc, tm7, grid, chunk=1 << 20):

@@ -17,8 +17,6 @@ device result compared with it bit for bit.
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 import time
 
@@ -30,8 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_dsm import stats, synth_heights  # noqa: E402
-from bench_dsm_post import timed  # noqa: E402
+from dsm_bench_common import scratch_sizes, stats, synth_heights, timed  # noqa: E402
 from satmvs_amd import _lib, dsm, rpc_synth  # noqa: E402
 from satmvs_amd.transverse_mercator import whu_tlc_projection  # noqa: E402
 
@@ -83,18 +80,6 @@ def pool_ground(z, radii, thresholds):
     return torch.where(cls >= 2, torch.full_like(z, NODATA), z), cls
 
 
-def scratch_sizes():
-    """{kernel: private segment bytes} of the morphology kernels, from the code objects inside the built library."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), _lib.LIB_PATH, "morph"],
-                         capture_output=True, text=True).stdout
-    sizes = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 8 and re.search(r"dsm_morph", f[0]):
-            sizes[f[0]] = int(f[-3])
-    return sizes
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=5120)
@@ -121,7 +106,7 @@ def main():
     res = {"command": " ".join([os.path.basename(sys.executable)] + sys.argv),
            "workload": "bench_dsm_post's grid (%d x %dx%d maps, %.1f m cells, %dx%d) after despike radius 2, void share %.4f"
                        % (a.views, a.size, a.size, a.res, gw, gh, float((~ok).double().mean())),
-           "cells": gw * gh, "workspace_bytes": nbytes, "scratch_bytes": scratch_sizes(), "open": [], "ground": []}
+           "cells": gw * gh, "workspace_bytes": nbytes, "scratch_bytes": scratch_sizes(r"dsm_morph"), "open": [], "ground": []}
 
     def native_open(r):
         _lib.call("smvs_dsm_morph", _lib.ptr(z), gw, gh, NODATA, r, 2, _lib.ptr(out), _lib.ptr(ws), nbytes, stream)

@@ -15,8 +15,6 @@ oracle (tests/dsm_post_oracle.py) on the same grid and whether the device result
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 import time
 
@@ -27,42 +25,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_dsm import stats, synth_heights  # noqa: E402
+from dsm_bench_common import scratch_sizes, stats, synth_heights, timed  # noqa: E402
 from satmvs_amd import _lib, dsm, rpc_synth  # noqa: E402
 from satmvs_amd.transverse_mercator import whu_tlc_projection  # noqa: E402
 
 NODATA = -999.0
 
 
-def timed(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return stats(ts)
-
-
 def void_share(z):
     return float((~(torch.isfinite(z) & (z != NODATA))).double().mean())
-
-
-def scratch_sizes():
-    """{kernel: private segment bytes} of the clean-up kernels, from the code objects inside the built library."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), _lib.LIB_PATH, "dsm_"],
-                         capture_output=True, text=True).stdout
-    sizes = {}
-    for line in out.splitlines()[1:]:
-        f = line.split()
-        if len(f) >= 8 and re.match(r"dsm_(despike|fill)", f[0]):
-            sizes[f[0]] = int(f[-3])
-    return sizes
 
 
 def main():
@@ -101,7 +72,7 @@ def main():
     res = {"command": " ".join([os.path.basename(sys.executable)] + sys.argv),
            "workload": "%d x %dx%d height maps (GSD 2.1 m) fused into a %.1f m grid %dx%d (median); %.3g of the valid cells moved by "
                        "+-30..80 m, %.3g voided" % (a.views, a.size, a.size, a.res, gw, gh, a.speckle, a.drop),
-           "cells": gw * gh, "void_share_fused": void_fused, "void_share_input": void_share(z), "scratch_bytes": scratch_sizes(),
+           "cells": gw * gh, "void_share_fused": void_fused, "void_share_input": void_share(z), "scratch_bytes": scratch_sizes(r"^dsm_(despike|fill)"),
            "despike": [], "fill": []}
 
     def despike(radius):

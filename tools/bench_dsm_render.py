@@ -22,31 +22,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from dsm_bench_common import SHIFTS, scene_dsm, stats  # noqa: E402
 from satmvs_amd import dsm, rpc_synth  # noqa: E402
 from satmvs_amd.transverse_mercator import whu_tlc_projection  # noqa: E402
-
-SHIFTS = (0.0, 0.4, -0.4)
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return {"min": ts[0], "median": ts[len(ts) // 2], "max": ts[-1], "reps": len(ts)}
-
-
-def scene_dsm(grid, seed=0):
-    """Terrain (+-30 m over kilometres) plus rectangular blocks 20 - 60 m high, float32 (gh, gw)."""
-    rng = np.random.default_rng(seed)
-    r, c = np.mgrid[0:grid.height, 0:grid.width].astype(np.float64)
-    E, N = grid.e0 + c * grid.xres, grid.n0 - r * grid.yres
-    z = 150.0 + 30.0 * np.sin(E / 900.0) * np.cos(N / 1300.0) + 5.0 * np.sin(E / 170.0 + N / 230.0)
-    nb = grid.width * grid.height // 400                    # about one block per 400 cells
-    rr, cc = rng.integers(0, grid.height - 12, nb), rng.integers(0, grid.width - 12, nb)
-    hh, ww = rng.integers(3, 12, nb), rng.integers(3, 12, nb)
-    up = rng.uniform(20.0, 60.0, nb)
-    for i in range(nb):
-        z[rr[i]:rr[i] + hh[i], cc[i]:cc[i] + ww[i]] += up[i]
-    return z.astype(np.float32)
-
 
 def evals_per_pixel(heights, rpc, tm7, grid, h_lo, h_hi, tol, stride):
     """Mean K + 1 + B over a strided sample of the pixels (the kernel's formulas; invalid pixels: K + 1)."""

@@ -23,26 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_dsm_render import SHIFTS, scene_dsm, stats  # noqa: E402
+from dsm_bench_common import SHIFTS, scene_dsm, stats, timed  # noqa: E402
 from satmvs_amd import dsm  # noqa: E402
 from satmvs_amd.transverse_mercator import whu_tlc_projection  # noqa: E402
-
-
-def timed(fn, reset, reps, warmup):
-    for _ in range(warmup):
-        reset()
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        reset()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return stats(ts)
 
 
 def march_samples(z, grid, tm7, rpc, h_hi, S, stride):
@@ -74,7 +57,7 @@ def main():
     grid = ro.grid_over([(r, (S, S)) for r in rpcs], tm7, 100.0, 250.0, a.res, margin=50.0)
     z = scene_dsm(grid)
     zd = torch.from_numpy(z).to(dev)
-    h_hi = dsm._h_hi(zd, -999.0)
+    _, h_hi = dsm._valid_range(zd, -999.0, lower=False)
     rds = [torch.from_numpy(r).to(dev) for r in rpcs]
     g = torch.Generator(device=dev)
     g.manual_seed(0)
@@ -103,11 +86,11 @@ def main():
         st = dsm.visibility(zd, grid, rds[v], proj, (S, S), occ_tol=a.occ_tol)
         share = (torch.bincount(st.reshape(-1).long(), minlength=4).double() / st.numel()).tolist()
         K, Kmax = march_samples(z, grid, tm7, rpcs[v], h_hi, S, stride=max(1, min(gh, gw) // 64))
-        res["views"].append({"shift_m_per_m": shift, "ms_occlusion": timed(one(v, True), reset, a.reps, a.warmup),
+        res["views"].append({"shift_m_per_m": shift, "ms_occlusion": timed(one(v, True), a.reps, a.warmup, reset=reset),
                              "state_share": dict(zip(dsm.ORTHO_STATES, share)), "mean_K": K, "max_K": Kmax})
-    res["views"][0]["ms_no_occlusion"] = timed(one(0, False), reset, a.reps, a.warmup)
-    res["views"][1]["ms_no_occlusion"] = timed(one(1, False), reset, a.reps, a.warmup)
-    res["mosaic_3_views_ms"] = timed(mosaic, reset, a.reps, a.warmup)
+    res["views"][0]["ms_no_occlusion"] = timed(one(0, False), a.reps, a.warmup, reset=reset)
+    res["views"][1]["ms_no_occlusion"] = timed(one(1, False), a.reps, a.warmup, reset=reset)
+    res["mosaic_3_views_ms"] = timed(mosaic, a.reps, a.warmup, reset=reset)
     src = source.cpu().numpy()
     res["mosaic_source_share"] = {str(k): float((src == k).mean()) for k in (-1, 0, 1, 2)}
     ts = []
