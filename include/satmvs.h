@@ -310,6 +310,21 @@ size_t smvs_conv3d_packed_floats(int cin, int cout);
 int smvs_conv3d_pack(const float* w, float* packed, int cin, int cout, int layout, void* stream);
 int smvs_conv3d_fwd(int kind, const float* in, const float* packed, const float* skip, float* out, int B, int Cin, int Cout,
                     int Di, int Hi, int Wi, int relu, void* stream);
+/* Which kernel smvs_conv3d_fwd runs for these arguments (Di, Hi, Wi: the INPUT volume) -- the function the launcher itself asks.  Host code
+ * only: no HIP call, usable without a GPU.  Negative: smvs_conv3d_fwd rejects the arguments (SMVS_ERR_ARG).
+ *   SMVS_CONV3D_S1_COT2     stride-1 row kernel on 62-column tiles, 2 output channels per lane (Cout <= 2)
+ *   SMVS_CONV3D_S1_COT8     the same, 8 output channels per lane
+ *   SMVS_CONV3D_S2          stride-2 direct gathers
+ *   SMVS_CONV3D_T_SPLIT     transposed, linear voxels, input channels split over 4 waves (below 512 workgroups)
+ *   SMVS_CONV3D_T_UNSPLIT   transposed, 64 x 4 input rows per workgroup
+ *   SMVS_CONV3D_MFMA_S1 / SMVS_CONV3D_MFMA_S2 + SMVS_MFMA_*   the MFMA kernel (Cout 32 / 64 / 128, Cin a multiple of 8), stride 1 / 2 */
+enum { SMVS_CONV3D_S1_COT2 = 0, SMVS_CONV3D_S1_COT8 = 1, SMVS_CONV3D_S2 = 2, SMVS_CONV3D_T_SPLIT = 3, SMVS_CONV3D_T_UNSPLIT = 4,
+       SMVS_CONV3D_MFMA_S1 = 10, SMVS_CONV3D_MFMA_S2 = 20 };
+/* form of an MFMA launch, added to SMVS_CONV3D_MFMA_S* / SMVS_CONV3X3_MFMA_S*.  Below 1024 tiles of 32 output positions: one tile of 32 output
+ * channels per workgroup, input channels split over 8 waves (K8; (Cin / 2) % 8 == 0) or 4 (K4).  From 1024 tiles: 4 waves, every cout tile in
+ * one workgroup: NT1 / NT2 / NT4 for Cout 32 / 64 / 128. */
+enum { SMVS_MFMA_K8 = 0, SMVS_MFMA_K4 = 1, SMVS_MFMA_NT1 = 2, SMVS_MFMA_NT2 = 3, SMVS_MFMA_NT4 = 4 };
+int smvs_conv3d_variant(int kind, int B, int Cin, int Cout, int Di, int Hi, int Wi);
 
 /* nn.BatchNorm3d in TRAINING form (batch statistics over (B, N = D*H*W) per channel) with the block's ReLU -- the normalisation of every
  * Conv3d / Deconv3d block of CostRegNet under autograd (modules/module.py:324-410):
@@ -348,6 +363,18 @@ int smvs_conv3x3_fwd(int kind, const float* xA, int CA, const float* xB, int CB,
                      float* out, int B, int Cout, int H, int W, int relu, void* stream);
 /* init (kinds 0 / 1; same shape as out, or NULL; may be out itself): added to the sums before bias / ReLU -- an input gradient that continues
  * the contributions already collected for that tensor (whole-cell ConvGRU backward). */
+/* Which kernel smvs_conv3x3_fwd runs for these arguments (H, W: the INPUT plane; bias_aligned: no bias, or a 16-byte aligned one) -- the
+ * function the launchers themselves ask.  Host code only: no HIP call, usable without a GPU.  Negative: smvs_conv3x3_fwd rejects the
+ * dimensions (SMVS_ERR_ARG).  Workgroups are counted as 64 x 4 output pixels (transposed: input pixels) x groups of 8 output channels:
+ *   SMVS_CONV3X3_SPLIT_S1 / _S2      direct, stride 1 / 2, 4 waves split the input channels (below 512 workgroups in the batch)
+ *   SMVS_CONV3X3_UNSPLIT_S1 / _S2    direct, stride 1 / 2, 64 x 4 output pixels per workgroup
+ *   SMVS_CONV3X3_ROWS4               direct, stride 1, four output rows per lane (from 1024 workgroups in ONE sample)
+ *   SMVS_CONV3X3_T_SPLIT / _T_UNSPLIT    transposed, below / from 512 workgroups
+ *   SMVS_CONV3X3_MFMA_S1 / SMVS_CONV3X3_MFMA_S2 + SMVS_MFMA_*   the MFMA kernel (Cout 32 / 64 / 128, CA + CB a multiple of 8, CA even, bias
+ *                                    aligned), stride 1 / 2, forms as above */
+enum { SMVS_CONV3X3_SPLIT_S1 = 0, SMVS_CONV3X3_SPLIT_S2 = 1, SMVS_CONV3X3_UNSPLIT_S1 = 2, SMVS_CONV3X3_UNSPLIT_S2 = 3, SMVS_CONV3X3_ROWS4 = 4,
+       SMVS_CONV3X3_T_SPLIT = 5, SMVS_CONV3X3_T_UNSPLIT = 6, SMVS_CONV3X3_MFMA_S1 = 10, SMVS_CONV3X3_MFMA_S2 = 20 };
+int smvs_conv3x3_variant(int kind, int B, int CA, int CB, int Cout, int H, int W, int bias_aligned);
 
 /* Both gate norms of a ConvGRU cell in one call (modules/module.py:15-16, :37-40): x (B, 2C, HW) contiguous = the gate
  * convolution's output; channels [0, C) are normalised with (gamma, beta), channels [C, 2C) with (gamma2, beta2), each half

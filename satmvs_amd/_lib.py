@@ -92,7 +92,9 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_conv3d_packed_floats": [_i] * 2, "smvs_conv3d_wgrad_workspace_floats": [_i] * 6,
                "smvs_dsm_workspace_bytes": [_sz, _i, _i], "smvs_dsm_fill_workspace_bytes": [_i] * 3,
                "smvs_dsm_morph_workspace_bytes": [_i] * 3}
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",
+# host-side queries that return a code, not a status: called on load() directly, never through call()
+_QUERY_FUNCS = {"smvs_conv3x3_variant": [_i] * 8, "smvs_conv3d_variant": [_i] * 7}
+EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + list(_QUERY_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",
                                                                     "smvs_set_arith", "smvs_get_arith"])
 ARITH_MODES = {"exact": 0, "fused": 1}      # SMVS_ARITH_EXACT / SMVS_ARITH_FUSED of include/satmvs.h
 
@@ -121,6 +123,10 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_size_t
+    for name, argtypes in _QUERY_FUNCS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = C.c_int
     lib.smvs_version.restype = C.c_char_p
     lib.smvs_last_error.restype = C.c_char_p
     lib.smvs_red_set_streams.argtypes = [_i]

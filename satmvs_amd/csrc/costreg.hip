@@ -439,6 +439,20 @@ void convT3d_split_kernel(const Conv3Args a)
     }
 }
 
+// The kernel a layer runs, chosen from the geometry alone (codes: SMVS_CONV3D_* of include/satmvs.h); di = input dimensions, dout = output
+// dimensions, mfma = the layer has MFMA-order weights.  cr_launch_layer and smvs_conv3d_variant both ask here.
+constexpr int CR_SPLIT_BELOW = 512;          // workgroups (of the 64-position split form) below which the channel-split transposed kernel runs
+static int cr_variant(const CrLayer& l, bool mfma, int B, const int (&di)[3], const int (&dout)[3])
+{
+    if (mfma)
+        return (l.stride == 1 ? SMVS_CONV3D_MFMA_S1 : SMVS_CONV3D_MFMA_S2) + (int)mfma_conv_form(mfma_conv_tiles(dout[2], dout[1], dout[0], B), l.cout / 32, l.cin / 2);
+    const int ncog = (l.cout + CR_COT - 1) / CR_COT;
+    if (l.transposed)
+        return (((long long)di[0] * di[1] * di[2] + 63) / 64) * B * ncog < CR_SPLIT_BELOW ? SMVS_CONV3D_T_SPLIT : SMVS_CONV3D_T_UNSPLIT;
+    if (l.stride == 1) return l.cout <= 2 ? SMVS_CONV3D_S1_COT2 : SMVS_CONV3D_S1_COT8;
+    return SMVS_CONV3D_S2;
+}
+
 // One layer on the kernels above: wm = MFMA-order weights (null: direct kernels)
 static void cr_launch_layer(const CrLayer& l, const float* in, const float* w, const float* scale, const float* shift, const float* wm,
                             const float* skip, float* out, int B, const int (&di)[3], const int (&dout)[3], hipStream_t st)
@@ -449,26 +463,26 @@ static void cr_launch_layer(const CrLayer& l, const float* in, const float* w, c
     a.Di = di[0]; a.Hi = di[1]; a.Wi = di[2];
     a.Do = dout[0]; a.Ho = dout[1]; a.Wo = dout[2];
     const int ncog = (l.cout + CR_COT - 1) / CR_COT;
-    if (wm) {
+    const int variant = cr_variant(l, wm != nullptr, B, di, dout);
+    const dim3 grd1((a.Wo + CR_S1_TILE - 1) / CR_S1_TILE, (a.Ho * a.Do + 3) / 4, B * ncog);
+    if (variant >= SMVS_CONV3D_MFMA_S1) {
         MfmaConvArgs m{};
         m.inA = in; m.CA = l.cin; m.scaleA = 1.0f; m.w = wm;
         m.scale = a.scale; m.shift = a.shift; m.skip = skip; m.out = out;
         m.Cout = l.cout; m.relu = l.relu; m.stride = l.stride;
         m.Di = a.Di; m.Hi = a.Hi; m.Wi = a.Wi; m.Do = a.Do; m.Ho = a.Ho; m.Wo = a.Wo;
         mfma_conv_launch<27>(m, B, st);
-    } else if (l.transposed) {
-        dim3 grd((a.Wi + 63) / 64, (a.Hi * a.Di + 3) / 4, B * ncog);
-        constexpr int SPLIT_BELOW = 512;         // workgroups (of the 64-position split form) below which the channel-split kernel runs
-        if ((long long)((a.Di * a.Hi * a.Wi + 63) / 64) * B * ncog < SPLIT_BELOW)
-            hipLaunchKernelGGL(convT3d_split_kernel, dim3((a.Di * a.Hi * a.Wi + 63) / 64, 1, B * ncog), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL(convT3d_kernel, grd, dim3(256), 0, st, a);
-    } else {
-        dim3 grd((a.Wo + 63) / 64, (a.Ho * a.Do + 3) / 4, B * ncog);
-        const dim3 grd1((a.Wo + CR_S1_TILE - 1) / CR_S1_TILE, (a.Ho * a.Do + 3) / 4, B * ncog);
-        if (l.stride == 1 && l.cout <= 2) hipLaunchKernelGGL(conv3d_s1_kernel<2>, grd1, dim3(256), 0, st, a);
-        else if (l.stride == 1)           hipLaunchKernelGGL(conv3d_s1_kernel<CR_COT>, grd1, dim3(256), 0, st, a);
-        else                              hipLaunchKernelGGL(conv3d_kernel<2>, grd, dim3(256), 0, st, a);
+        return;
+    }
+    switch (variant) {
+    case SMVS_CONV3D_T_SPLIT:
+        hipLaunchKernelGGL(convT3d_split_kernel, dim3((a.Di * a.Hi * a.Wi + 63) / 64, 1, B * ncog), dim3(256), 0, st, a); break;
+    case SMVS_CONV3D_T_UNSPLIT:
+        hipLaunchKernelGGL(convT3d_kernel, dim3((a.Wi + 63) / 64, (a.Hi * a.Di + 3) / 4, B * ncog), dim3(256), 0, st, a); break;
+    case SMVS_CONV3D_S1_COT2: hipLaunchKernelGGL(conv3d_s1_kernel<2>, grd1, dim3(256), 0, st, a); break;
+    case SMVS_CONV3D_S1_COT8: hipLaunchKernelGGL(conv3d_s1_kernel<CR_COT>, grd1, dim3(256), 0, st, a); break;
+    default:
+        hipLaunchKernelGGL(conv3d_kernel<2>, dim3((a.Wo + 63) / 64, (a.Ho * a.Do + 3) / 4, B * ncog), dim3(256), 0, st, a); break;
     }
 }
 
@@ -593,27 +607,48 @@ SMVS_EXPORT int smvs_conv3d_pack(const float* w, float* packed, int cin, int cou
     return check_launch("conv3d_pack");
 }
 
+// the dimension checks of smvs_conv3d_fwd (null: accepted), shared with smvs_conv3d_variant
+static const char* conv3d_reject(int kind, int B, int Cin, int Cout, int Di, int Hi, int Wi)
+{
+    if (kind < 0 || kind > 2) return "kind must be 0 (stride 1), 1 (stride 2) or 2 (transposed, stride 2)";
+    if (B < 1 || Cin < 1 || Cout < 1 || Di < 1 || Hi < 1 || Wi < 1) return "non-positive dimension";
+    if (kind == 1 && ((Di | Hi | Wi) & 1)) return "stride-2 layer needs even D, H, W";
+    const long long vi = (long long)Di * Hi * Wi, vo = kind == 1 ? vi / 8 : kind == 2 ? vi * 8 : vi;
+    if (Cin * vi * 4 >= (1ll << 32) || Cout * vo * 4 >= (1ll << 32)) return "layer input or output larger than 4 GiB per batch item";
+    const int ncog = (Cout + smvs::CR_COT - 1) / smvs::CR_COT;
+    const long long rows = kind == 2 ? (long long)Di * Hi : kind == 1 ? (long long)Di * Hi / 4 : (long long)Di * Hi;
+    if ((rows + 3) / 4 > 65535 || (long long)B * ncog > 65535 || vo / 32 * B >= (1ll << 31)) return "volume too large for one launch grid";
+    return nullptr;
+}
+
+// layer and dimensions of a single-layer call, for smvs_conv3d_variant and smvs_conv3d_fwd alike
+struct Conv3dCall { smvs::CrLayer l; int di[3], dout[3]; bool mfma; };
+static Conv3dCall conv3d_call(int kind, int Cin, int Cout, int Di, int Hi, int Wi, int relu)
+{
+    Conv3dCall c{{Cin, Cout, kind == 0 ? 1 : 2, kind == 2, 0, relu ? 1 : 0}, {Di, Hi, Wi}, {}, false};
+    for (int i = 0; i < 3; ++i) c.dout[i] = kind == 1 ? c.di[i] / 2 : kind == 2 ? c.di[i] * 2 : c.di[i];
+    c.mfma = smvs::cr_use_mfma(c.l);
+    return c;
+}
+
+SMVS_EXPORT int smvs_conv3d_variant(int kind, int B, int Cin, int Cout, int Di, int Hi, int Wi)
+{
+    using namespace smvs;
+    if (conv3d_reject(kind, B, Cin, Cout, Di, Hi, Wi)) return -1;
+    const Conv3dCall c = conv3d_call(kind, Cin, Cout, Di, Hi, Wi, 0);
+    return cr_variant(c.l, c.mfma, B, c.di, c.dout);
+}
+
 SMVS_EXPORT int smvs_conv3d_fwd(int kind, const float* in, const float* packed, const float* skip, float* out, int B, int Cin, int Cout,
                                 int Di, int Hi, int Wi, int relu, void* stream)
 {
     using namespace smvs;
     if (!in || !packed || !out) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if (kind < 0 || kind > 2) return fail(SMVS_ERR_ARG, "kind must be 0 (stride 1), 1 (stride 2) or 2 (transposed, stride 2)");
-    if (B < 1 || Cin < 1 || Cout < 1 || Di < 1 || Hi < 1 || Wi < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if (kind == 1 && ((Di | Hi | Wi) & 1)) return fail(SMVS_ERR_ARG, "stride-2 layer needs even D, H, W (got %dx%dx%d)", Di, Hi, Wi);
-    const int di[3] = {Di, Hi, Wi};
-    const int dout[3] = {kind == 1 ? Di / 2 : kind == 2 ? Di * 2 : Di, kind == 1 ? Hi / 2 : kind == 2 ? Hi * 2 : Hi,
-                         kind == 1 ? Wi / 2 : kind == 2 ? Wi * 2 : Wi};
-    const long long vi = (long long)Di * Hi * Wi, vo = (long long)dout[0] * dout[1] * dout[2];
-    if (Cin * vi * 4 >= (1ll << 32) || Cout * vo * 4 >= (1ll << 32)) return fail(SMVS_ERR_ARG, "layer input or output larger than 4 GiB per batch item");
-    const int ncog = (Cout + CR_COT - 1) / CR_COT;
-    const long long rows = kind == 2 ? (long long)Di * Hi : (long long)dout[0] * dout[1];
-    if ((rows + 3) / 4 > 65535 || (long long)B * ncog > 65535 || vo / 32 * B >= (1ll << 31)) return fail(SMVS_ERR_ARG, "volume too large for one launch grid");
-    const CrLayer l{Cin, Cout, kind == 0 ? 1 : 2, kind == 2, 0, relu ? 1 : 0};
+    if (const char* why = conv3d_reject(kind, B, Cin, Cout, Di, Hi, Wi)) return fail(SMVS_ERR_ARG, "%s (got %dx%dx%d)", why, Di, Hi, Wi);
+    const Conv3dCall c = conv3d_call(kind, Cin, Cout, Di, Hi, Wi, relu);
     const size_t n = cr_packed_conv(Cin, Cout);
-    const int cp = ncog * CR_COT;
-    const bool mf = kind != 2 && mfma_conv_ok(Cin, 0, Cout);
-    cr_launch_layer(l, in, packed, packed + n, packed + n + cp, mf ? packed + n + 2 * cp : nullptr, skip, out, B, di, dout, (hipStream_t)stream);
+    const int cp = (Cout + CR_COT - 1) / CR_COT * CR_COT;
+    cr_launch_layer(c.l, in, packed, packed + n, packed + n + cp, c.mfma ? packed + n + 2 * cp : nullptr, skip, out, B, c.di, c.dout, (hipStream_t)stream);
     return check_launch("conv3d_fwd");
 }
 

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "smvs_device.h"
+#include "../../include/satmvs.h"
 
 namespace smvs {
 
@@ -376,23 +377,34 @@ inline bool mfma_conv_ok(int CA, int CB, int Cout)
 
 inline size_t mfma_packed_floats(int cin, int cout, int taps) { return (size_t)(cin / 2) * (taps == 9 ? MFMA9_WSLOT : taps) * ((cout + 31) / 32) * 64; }
 
+// Which instantiation serves a layer the MFMA kernel takes (mfma_conv_ok), from the geometry alone: `tiles_h` = tiles of 32 output positions
+// of the batch the variant is chosen for, nt = Cout / 32, ncip = input channel pairs.  The values are the low digit of the MFMA codes of
+// smvs_conv3x3_variant / smvs_conv3d_variant (include/satmvs.h).
+// Few tiles (the coarse levels): latency, not throughput, sets the time -- one cout tile per workgroup
+// and as many K-splitting waves as the channel count divides into.  Many tiles: one workgroup carries
+// every cout tile so the X operand is loaded once.
+// (at most 8 waves per workgroup)
+enum MfmaForm { MFMA_FORM_K8 = SMVS_MFMA_K8, MFMA_FORM_K4 = SMVS_MFMA_K4, MFMA_FORM_NT1 = SMVS_MFMA_NT1, MFMA_FORM_NT2 = SMVS_MFMA_NT2, MFMA_FORM_NT4 = SMVS_MFMA_NT4 };
+constexpr int MFMA_SMALL = 1024;             // tiles below which one cout tile per workgroup runs
+inline long long mfma_conv_tiles(int Wo, int Ho, int Do, int B) { return (long long)((Wo + 31) / 32) * Ho * Do * B; }
+inline MfmaForm mfma_conv_form(long long tiles_h, int nt, int ncip)
+{
+    if (tiles_h < MFMA_SMALL) return ncip % 8 == 0 ? MFMA_FORM_K8 : MFMA_FORM_K4;
+    return nt == 1 ? MFMA_FORM_NT1 : nt == 2 ? MFMA_FORM_NT2 : MFMA_FORM_NT4;
+}
+
 template <int TAPS>
 inline void mfma_conv_launch(const MfmaConvArgs& a, int B, hipStream_t st, int Bh = 0)   // Bh: batch the variant is chosen for (0 = B)
 {
-    const int tiles = ((a.Wo + 31) / 32) * a.Ho * a.Do * B;
-    const int tiles_h = ((a.Wo + 31) / 32) * a.Ho * a.Do * (Bh > 0 ? Bh : B);
+    const int tiles = (int)mfma_conv_tiles(a.Wo, a.Ho, a.Do, B);
     const int nt = a.Cout / 32, ncip = (a.CA + a.CB) / 2;
-    // Few tiles (the coarse levels): latency, not throughput, sets the time -- one cout tile per workgroup
-    // and as many K-splitting waves as the channel count divides into.  Many tiles: one workgroup carries
-    // every cout tile so the X operand is loaded once.
-    // (at most 8 waves per workgroup)
-    constexpr int SMALL = 1024;
-    if (tiles_h < SMALL) {
-        if (ncip % 8 == 0) hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 8>), dim3(tiles, nt), dim3(512), 0, st, a);
-        else               hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 4>), dim3(tiles, nt), dim3(256), 0, st, a);
-    } else if (nt == 1) hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 4>), dim3(tiles), dim3(256), 0, st, a);
-    else if (nt == 2)   hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 2, 4>), dim3(tiles), dim3(256), 0, st, a);
-    else                hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 4, 4>), dim3(tiles), dim3(256), 0, st, a);
+    switch (mfma_conv_form(mfma_conv_tiles(a.Wo, a.Ho, a.Do, Bh > 0 ? Bh : B), nt, ncip)) {
+    case MFMA_FORM_K8:  hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 8>), dim3(tiles, nt), dim3(512), 0, st, a); break;
+    case MFMA_FORM_K4:  hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 4>), dim3(tiles, nt), dim3(256), 0, st, a); break;
+    case MFMA_FORM_NT1: hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 1, 4>), dim3(tiles), dim3(256), 0, st, a); break;
+    case MFMA_FORM_NT2: hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 2, 4>), dim3(tiles), dim3(256), 0, st, a); break;
+    case MFMA_FORM_NT4: hipLaunchKernelGGL((mfma_conv_kernel<TAPS, 4, 4>), dim3(tiles), dim3(256), 0, st, a); break;
+    }
 }
 
 }  // namespace smvs

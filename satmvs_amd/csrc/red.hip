@@ -878,29 +878,49 @@ static MfmaConvArgs mfma_args(int stride, const ConvArgs& a, const float* wm)
     return m;
 }
 
+// The kernel a correlation runs, chosen from the geometry alone (codes: SMVS_CONV3X3_* of include/satmvs.h).  `mfma`: the layer has MFMA-order
+// weights and dense inputs.  Bh = the batch size the variant is chosen for.  launch_conv and smvs_conv3x3_variant both ask here.
+static int conv_variant(int stride, bool mfma, int CA, int CB, int Cout, int Ho, int Wo, int Bh)
+{
+    if (mfma && mfma_conv_ok(CA, CB, Cout))
+        return (stride == 1 ? SMVS_CONV3X3_MFMA_S1 : SMVS_CONV3X3_MFMA_S2) + (int)mfma_conv_form(mfma_conv_tiles(Wo, Ho, 1, Bh), Cout / 32, (CA + CB) / 2);
+    const int ncog = (Cout + COT - 1) / COT;
+    const int wx = (Wo + 63) / 64;
+    if ((long long)wx * ((Ho + 3) / 4) * Bh * ncog < SPLIT_BELOW)              // coarse plane: latency regime
+        return stride == 1 ? SMVS_CONV3X3_SPLIT_S1 : SMVS_CONV3X3_SPLIT_S2;
+    if (stride == 1 && (long long)wx * ((Ho + 3) / 4) * ncog >= ROWS4_FROM)    // throughput regime (one sample's geometry): 4 output rows per lane
+        return SMVS_CONV3X3_ROWS4;
+    return stride == 1 ? SMVS_CONV3X3_UNSPLIT_S1 : SMVS_CONV3X3_UNSPLIT_S2;
+}
+
+// ... and a stride-2 transposed convolution (workgroups counted over the INPUT plane)
+static int convT_variant(int Cout, int Hi, int Wi, int Bh)
+{
+    const int ncog = (Cout + COT - 1) / COT;
+    return (long long)((Wi + 63) / 64) * ((Hi + 3) / 4) * Bh * ncog < SPLIT_BELOW ? SMVS_CONV3X3_T_SPLIT : SMVS_CONV3X3_T_UNSPLIT;
+}
+
 // `wm` = MFMA-order weights of the same layer (used when the layer qualifies; the MFMA kernel reads dense inputs)
 // Bh = the batch size the kernel VARIANT is chosen for (0 = B): the last chunk of a plane range may be short, and a
 // plane's bits must not depend on how the range was chunked or sharded.
 static void launch_conv(int stride, const ConvArgs& a, int B, hipStream_t st, const float* wm = nullptr, int Bh = 0)
 {
     if (Bh <= 0) Bh = B;
-    if (wm && !a.inA_cs && mfma_conv_ok(a.CA, a.CB, a.Cout)) {
+    const int variant = conv_variant(stride, wm && !a.inA_cs, a.CA, a.CB, a.Cout, a.Ho, a.Wo, Bh);
+    if (variant >= SMVS_CONV3X3_MFMA_S1) {
         mfma_conv_launch<9>(mfma_args(stride, a, wm), B, st, Bh);
         return;
     }
     const int ncog = (a.Cout + COT - 1) / COT;
     const int wx = (a.Wo + 63) / 64;
-    if (wx * ((a.Ho + 3) / 4) * Bh * ncog < SPLIT_BELOW) {         // coarse plane: latency regime
-        dim3 grd(wx, a.Ho, B * ncog), blk(256);
-        if (stride == 1) hipLaunchKernelGGL((conv3x3_kernel<1, true>), grd, blk, 0, st, a);
-        else             hipLaunchKernelGGL((conv3x3_kernel<2, true>), grd, blk, 0, st, a);
-        return;
+    const dim3 blk(256), grd_split(wx, a.Ho, B * ncog), grd(wx, (a.Ho + 3) / 4, B * ncog);
+    switch (variant) {
+    case SMVS_CONV3X3_SPLIT_S1:   hipLaunchKernelGGL((conv3x3_kernel<1, true>), grd_split, blk, 0, st, a); break;
+    case SMVS_CONV3X3_SPLIT_S2:   hipLaunchKernelGGL((conv3x3_kernel<2, true>), grd_split, blk, 0, st, a); break;
+    case SMVS_CONV3X3_ROWS4:      hipLaunchKernelGGL((conv3x3_rows_kernel<4>), dim3(wx, (a.Ho + 15) / 16, B * ncog), blk, 0, st, a); break;
+    case SMVS_CONV3X3_UNSPLIT_S1: hipLaunchKernelGGL((conv3x3_kernel<1, false>), grd, blk, 0, st, a); break;
+    default:                      hipLaunchKernelGGL((conv3x3_kernel<2, false>), grd, blk, 0, st, a); break;
     }
-    dim3 grd(wx, (a.Ho + 3) / 4, B * ncog), blk(256);
-    if (stride == 1 && wx * ((a.Ho + 3) / 4) * ncog >= ROWS4_FROM)          // throughput regime (one sample's geometry): 4 output rows per lane
-        hipLaunchKernelGGL((conv3x3_rows_kernel<4>), dim3(wx, (a.Ho + 15) / 16, B * ncog), blk, 0, st, a);
-    else if (stride == 1) hipLaunchKernelGGL((conv3x3_kernel<1, false>), grd, blk, 0, st, a);
-    else             hipLaunchKernelGGL((conv3x3_kernel<2, false>), grd, blk, 0, st, a);
 }
 
 // one stride-1 convolution as a job of a level-batched launch; returns its workgroup count
@@ -938,11 +958,10 @@ static void launch_convT(const ConvArgs& a, int B, hipStream_t st, int Bh = 0)
     if (Bh <= 0) Bh = B;
     const int ncog = (a.Cout + COT - 1) / COT;
     const int wx = (a.Wi + 63) / 64;
-    if (wx * ((a.Hi + 3) / 4) * Bh * ncog < SPLIT_BELOW) {
+    if (convT_variant(a.Cout, a.Hi, a.Wi, Bh) == SMVS_CONV3X3_T_SPLIT)
         hipLaunchKernelGGL(convT3x3s2_kernel<true>, dim3(wx, a.Hi, B * ncog), dim3(256), 0, st, a);
-        return;
-    }
-    hipLaunchKernelGGL(convT3x3s2_kernel<false>, dim3(wx, (a.Hi + 3) / 4, B * ncog), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(convT3x3s2_kernel<false>, dim3(wx, (a.Hi + 3) / 4, B * ncog), dim3(256), 0, st, a);
 }
 
 // ---- plane pipeline ------------------------------------------------------------------------------------------
@@ -1340,26 +1359,48 @@ SMVS_EXPORT int smvs_conv3x3_pack(const float* w, float* packed, int cin, int co
     return check_launch("conv3x3_pack");
 }
 
+// the dimension checks of smvs_conv3x3_fwd (null: accepted), shared with smvs_conv3x3_variant
+static const char* conv3x3_reject(int kind, int B, int CA, int CB, int Cout, int H, int W)
+{
+    if (kind < 0 || kind > 2) return "kind must be 0, 1 or 2";
+    if (B < 1 || CA < 1 || CB < 0 || Cout < 1 || H < 1 || W < 1) return "non-positive dimension";
+    if (kind == 1 && ((H | W) & 1)) return "stride 2: H and W must be even";
+    if (kind == 2 && CB > 0) return "transposed layer: one operand, no bias, no initial sums";
+    const long long Ho = kind == 1 ? H / 2 : kind == 2 ? 2ll * H : H, Wo = kind == 1 ? W / 2 : kind == 2 ? 2ll * W : W;
+    if ((long long)(CA > CB ? CA : CB) * H * W * 4 >= (1ll << 31) || (long long)Cout * Ho * Wo * 4 >= (1ll << 31)) return "plane too large";
+    if ((long long)B * ((Cout + smvs::COT - 1) / smvs::COT) > 65535) return "batch too large";
+    return nullptr;
+}
+
+// the MFMA kernel reads its per-channel vectors as aligned float4 and pairs input channels: both operands even, bias 16-byte aligned
+static bool conv3x3_takes_mfma(int CA, int CB, int Cout, bool bias_aligned)
+{
+    return smvs::mfma_conv_ok(CA + CB, 0, Cout) && CA % 2 == 0 && bias_aligned;
+}
+
+SMVS_EXPORT int smvs_conv3x3_variant(int kind, int B, int CA, int CB, int Cout, int H, int W, int bias_aligned)
+{
+    using namespace smvs;
+    if (conv3x3_reject(kind, B, CA, CB, Cout, H, W)) return -1;
+    if (kind == 2) return convT_variant(Cout, H, W, B);
+    return conv_variant(kind == 1 ? 2 : 1, conv3x3_takes_mfma(CA, CB, Cout, bias_aligned != 0), CA, CB, Cout, kind == 1 ? H / 2 : H, kind == 1 ? W / 2 : W, B);
+}
+
 SMVS_EXPORT int smvs_conv3x3_fwd(int kind, const float* xA, int CA, const float* xB, int CB, const float* packed, const float* bias, const float* init,
                                  float* out, int B, int Cout, int H, int W, int relu, void* stream)
 {
     using namespace smvs;
     if (!xA || !packed || !out || (CB > 0 && !xB)) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if (kind < 0 || kind > 2) return fail(SMVS_ERR_ARG, "kind must be 0, 1 or 2");
-    if (B < 1 || CA < 1 || CB < 0 || Cout < 1 || H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if (kind == 1 && ((H | W) & 1)) return fail(SMVS_ERR_ARG, "stride 2: H and W must be even");
-    if (kind == 2 && (CB > 0 || bias || init)) return fail(SMVS_ERR_ARG, "transposed layer: one operand, no bias, no initial sums");
+    if (const char* why = conv3x3_reject(kind, B, CA, CB, Cout, H, W)) return fail(SMVS_ERR_ARG, "%s", why);
+    if (kind == 2 && (bias || init)) return fail(SMVS_ERR_ARG, "transposed layer: one operand, no bias, no initial sums");
     const int Ho = kind == 1 ? H / 2 : kind == 2 ? 2 * H : H, Wo = kind == 1 ? W / 2 : kind == 2 ? 2 * W : W;
-    if ((long long)(CA > CB ? CA : CB) * H * W * 4 >= (1ll << 31) || (long long)Cout * Ho * Wo * 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "plane too large");
-    if ((long long)B * ((Cout + COT - 1) / COT) > 65535) return fail(SMVS_ERR_ARG, "batch too large");
     const int Cin = CA + CB;
     ConvArgs a{};
     a.inA = xA; a.CA = CA; a.scaleA = 1.0f; a.inB = CB > 0 ? xB : nullptr; a.CB = CB;
     a.w = packed; a.bias = bias; a.init = init; a.out = out; a.Cout = Cout; a.Hi = H; a.Wi = W; a.Ho = Ho; a.Wo = Wo; a.relu = relu ? 1 : 0;
     if (kind == 2) launch_convT(a, B, (hipStream_t)stream);
     else {
-        // the MFMA kernel reads its per-channel vectors as aligned float4 and pairs input channels: both operands even, bias 16-byte aligned
-        const bool mf = mfma_conv_ok(Cin, 0, Cout) && CA % 2 == 0 && (!bias || ((uintptr_t)bias & 15) == 0);
+        const bool mf = conv3x3_takes_mfma(CA, CB, Cout, !bias || ((uintptr_t)bias & 15) == 0);
         launch_conv(kind == 1 ? 2 : 1, a, B, (hipStream_t)stream, mf ? packed + packed_conv_floats(Cin, Cout) : nullptr);
     }
     return check_launch("conv3x3_fwd");
