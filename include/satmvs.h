@@ -631,7 +631,28 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  * Limits (SMVS_ERR_ARG, checked before any HIP call): 1 <= radius, radii[k] <= 256, radii strictly increasing,
  *   1 <= n_levels <= 16, thresholds finite and >= 0, gw * gh < 2^31; out / dtm / cls / workspace distinct from dsm and from
  *   each other; workspace: smvs_dsm_morph_workspace_bytes(gw, gh, the largest radius) bytes (0 = unsupported arguments).
- *   No atomics, every value a selection: bit-identical from run to run and to the numpy statement of these rules. */
+ *   No atomics, every value a selection: bit-identical from run to run and to the numpy statement of these rules.
+ *
+ * Objects (csrc/dsm_label.hip).  mask (gh, gw) uint8 (device), read only: non-zero cells are foreground.  Two foreground cells
+ *   are adjacent iff they differ by one step E, N, W or S (connectivity 4) or by one of those or a diagonal step
+ *   (connectivity 8); a component is a class of the transitive closure of adjacency.  Components are ordered by the linear
+ *   index row * gw + col of their first cell in raster order.
+ * smvs_dsm_label: labels (gh, gw) int32 gets 1 .. n in that order (the numbering of scipy.ndimage.label), 0 at background
+ *   cells; n_out (device, one int) gets n, or -1 if a union-find loop gave up at its bound (a damaged parent array: never on
+ *   a sound device; labels are undefined then).  The result depends on the mask alone: equal bits from run to run.  The
+ *   labels buffer holds the parent array while the entry runs.  No host synchronisation.
+ * smvs_dsm_label_stats: per label k + 1, k = 0 .. n - 1, over the cells of `labels` that carry it (cells with a label outside
+ *   1 .. n contribute to nothing): area[k] int32 the number of cells; bbox[4 k ..] int32 r0, c0, r1, c1, inclusive
+ *   (INT_MAX, INT_MAX, -1, -1 if the label has no cell); rc_sum[2 k ..] int64 the sums of the rows and of the columns.  With
+ *   values (gh, gw) float32, a cell valid iff finite and != (float)nodata: nvalid[k] int32 the valid cells; vmin[k], vmax[k]
+ *   float32 the lowest and highest valid value by the order of the keys above (-0.0 below +0.0), nodata where nvalid is 0;
+ *   qsum[k] int64 the sum over the valid cells of q(v) = llrint(min(max((double)v, -2^21), 2^21) * 1024), halves to even:
+ *   heights in units of 2^-10 m (0.98 mm), summed exactly, |qsum| < 2^62.  mean = qsum / 1024 / nvalid and volume =
+ *   qsum / 1024 * xres * yres are the caller's, in float64.  Integer atomics only, so the bits do not depend on their order.
+ *   The entry initialises its outputs; n == 0 returns SMVS_OK without a launch.  values null <=> nvalid, vmin, vmax, qsum null.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers, gw, gh >= 1, gw * gh < 2^31, connectivity 4 or 8,
+ *   n >= 0; labels, n_out and workspace distinct from mask and from each other; every statistics output distinct from labels,
+ *   values and the other outputs; workspace: smvs_dsm_label_workspace_bytes(gw, gh) bytes (0 = unsupported arguments). */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -656,6 +677,12 @@ int smvs_dsm_morph(const float* dsm, int gw, int gh, float nodata, int radius, i
                    void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_ground(const float* dsm, int gw, int gh, float nodata, const int* radii, const double* thresholds, int n_levels,
                     float* dtm, unsigned char* cls, void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_label_workspace_bytes(int gw, int gh);
+int smvs_dsm_label(const unsigned char* mask, int gw, int gh, int connectivity, int* labels, int* n_out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_label_stats(const int* labels, const float* values, int gw, int gh, float nodata, int n,
+                         int* area, int* bbox, long long* rc_sum,
+                         int* nvalid, float* vmin, float* vmax, long long* qsum, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,12 @@ and the split into terrain and what stands on it (progressive morphological filt
     above = ndsm(dsm, dtm)                                     # heights above ground, >= 0; nodata where either has none
     opened = morph(dsm, radius=8, op="open")                   # the building block: erode / dilate / open / close
 
+and the objects that stand on the ground (connected components in scipy.ndimage.label's numbering, exact statistics):
+
+    labels, stats = extract_objects(above, grid)               # > 2.5 m, >= 50 m^2: area, bbox, centroid, mean, max, volume
+    labels, n = label(above > 10.0, connectivity=4)            # the building block; label_stats(), sieve_labels()
+    voids, n_voids = label(~(np.isfinite(dsm) & (dsm != -999.0)))   # the void regions fill_voids could not reach
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -35,6 +41,8 @@ smvs_dsm_despike takes the median of every cell's window with a sorting network 
 smvs_dsm_fill finds the eight directional hits of every void cell as states carried along columns, diagonals and rows.
 smvs_dsm_morph / smvs_dsm_ground take window minima and maxima as row and column passes over order-preserving keys, each a
 doubling in LDS whose cost does not grow with the radius but with its logarithm.
+smvs_dsm_label is a union-find over cell indices (tiles in LDS, tile borders with integer min atomics, a three-level scan
+for the numbering); smvs_dsm_label_stats reduces along rows and columns on chip before its integer atomics.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -521,6 +529,167 @@ def ndsm(dsm, dtm, nodata=-999.0, clamp=True):
     if clamp:
         d = torch.where(d > 0.0, d, torch.zeros_like(d))                  # every zero leaves as +0.0
     return _back(as_numpy, torch.where(both, d, torch.full_like(d, nd)))
+
+
+# ---- objects: connected components of a mask and their statistics ---------------------------------------------------------------
+def _mask_checked(mask):
+    if not isinstance(mask, torch.Tensor):
+        mask = np.asarray(mask)
+        integral = mask.dtype == np.bool_ or np.issubdtype(mask.dtype, np.integer)
+    else:
+        integral = mask.dtype == torch.bool or not (mask.is_floating_point() or mask.is_complex())
+    if mask.ndim != 2:
+        raise ValueError("a mask is (gh, gw), got shape %s" % (tuple(mask.shape),))
+    if not integral:
+        raise ValueError("a mask is bool or an integer type (non-zero = foreground), got %s" % (mask.dtype,))
+    gh, gw = int(mask.shape[0]), int(mask.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("a mask has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    return mask
+
+
+def _connectivity_checked(connectivity):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
+    return int(connectivity)
+
+
+def _labels_checked(labels):
+    if not isinstance(labels, torch.Tensor):
+        labels = np.asarray(labels)
+    if labels.ndim != 2:
+        raise ValueError("labels are (gh, gw), got shape %s" % (tuple(labels.shape),))
+    if labels.dtype not in (np.int32, torch.int32):
+        raise ValueError("labels are int32, got %s" % (labels.dtype,))
+    gh, gw = int(labels.shape[0]), int(labels.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("labels have positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    return labels
+
+
+def label(mask, connectivity=8):
+    """Connected components of a mask (include/satmvs.h smvs_dsm_label, DESIGN.md section 9, "Objects"): mask (gh, gw), bool or
+    any integer dtype, non-zero = foreground (a float mask is rejected: threshold it yourself); connectivity 4 (E, N, W, S) or 8
+    (plus the diagonals).  Labels are 1 .. n in raster order of every component's first cell, the numbering of
+    scipy.ndimage.label, 0 = background; they depend on the mask alone, bit for bit.
+    -> (labels (gh, gw) int32, n int); labels numpy if the mask came as numpy, a device tensor otherwise.  Reading n is the one
+    synchronisation."""
+    mask = _mask_checked(mask)
+    connectivity = _connectivity_checked(connectivity)
+    if not isinstance(mask, torch.Tensor):
+        mask = np.not_equal(mask, 0).view(np.uint8)          # every integer dtype numpy has, torch's or not
+    m, as_numpy = _to_device(mask)
+    m = (m != 0).to(torch.uint8).contiguous()
+    gh, gw = m.shape
+    nbytes = _lib.load().smvs_dsm_label_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported labelling: %d x %d cells" % (gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+    labels = torch.empty((gh, gw), dtype=torch.int32, device=m.device)
+    n_dev = torch.empty(1, dtype=torch.int32, device=m.device)
+    _call(m.device, "smvs_dsm_label", m, gw, gh, connectivity, labels, n_dev, ws, nbytes)
+    n = int(n_dev.item())
+    if n < 0:
+        raise _lib.SatMVSNativeError("smvs_dsm_label gave up: a union-find loop reached its bound (n = %d)" % n)
+    return _back(as_numpy, labels), n
+
+
+def label_stats(labels, n, values=None, grid=None, nodata=-999.0):
+    """Statistics of the labels 1 .. n of a label map (include/satmvs.h smvs_dsm_label_stats): labels (gh, gw) int32 from
+    label(); cells with a label outside 1 .. n count for nothing.  -> dict of arrays of length n, entry k for label k + 1:
+      area int32 [cells]; bbox int32 (n, 4) r0, c0, r1, c1 inclusive; rc_sum int64 (n, 2); centroid float64 (n, 2) row, col
+      with grid (a DSMGrid of the labels' shape): area_m2, and centroid_en float64 (n, 2) east, north (cell centres)
+      with values ((gh, gw) float32, never converted; valid = finite and != nodata): n_valid int32; min, max float32 (by the
+        keys' order: -0.0 below +0.0; nodata where n_valid is 0); qsum int64 = the exact sum of the valid values rounded to
+        units of 2^-10 m (0.98 mm, far below any DSM's accuracy) and clamped to +-2^21 m; mean float64 = qsum / 1024 / n_valid
+        (NaN where n_valid is 0)
+      with both: volume float64 = qsum / 1024 * xres * yres [m^3].
+    Every sum is an integer sum: equal bits from run to run.  numpy if the labels came as numpy, device tensors otherwise."""
+    labels = _labels_checked(labels)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31:
+        raise ValueError("n must be an integer in 0 .. 2^31 - 1, got %r" % (n,))
+    n = int(n)
+    if values is not None:
+        values = _dsm_bits(values)
+        if tuple(values.shape) != tuple(labels.shape):
+            raise ValueError("values shape %s differs from the labels' %s" % (tuple(values.shape), tuple(labels.shape)))
+    if grid is not None:
+        _on_grid(labels, grid)
+    lab, as_numpy = _to_device(labels)
+    dev = lab.device
+    gh, gw = lab.shape
+    area = torch.empty(n, dtype=torch.int32, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    rc = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    v = nvalid = vmin = vmax = qsum = None
+    if values is not None:
+        v, _ = _to_device(values, dev=dev)
+        nvalid = torch.empty(n, dtype=torch.int32, device=dev)
+        vmin = torch.empty(n, dtype=torch.float32, device=dev)
+        vmax = torch.empty_like(vmin)
+        qsum = torch.empty(n, dtype=torch.int64, device=dev)
+    if n:
+        _call(dev, "smvs_dsm_label_stats", lab, v, gw, gh, float(nodata), n, area, bbox, rc, nvalid, vmin, vmax, qsum)
+    out = {"area": area, "bbox": bbox, "rc_sum": rc, "centroid": rc.double() / area.double()[:, None]}
+    if grid is not None:
+        out["area_m2"] = area.double() * float(grid.xres) * float(grid.yres)
+        out["centroid_en"] = torch.stack([float(grid.e0) + out["centroid"][:, 1] * float(grid.xres),
+                                          float(grid.n0) - out["centroid"][:, 0] * float(grid.yres)], dim=1)
+    if values is not None:
+        some = nvalid > 0
+        out.update({"n_valid": nvalid, "min": vmin, "max": vmax, "qsum": qsum,
+                    "mean": torch.where(some, qsum.double() / 1024.0 / nvalid.double().clamp(min=1.0), torch.full_like(qsum, float("nan"), dtype=torch.float64))})
+        if grid is not None:
+            out["volume"] = qsum.double() / 1024.0 * float(grid.xres) * float(grid.yres)
+    return {k: _back(as_numpy, t) for k, t in out.items()}
+
+
+def sieve_labels(labels, area, min_area=1, max_area=None):
+    """Drop the components whose area [cells] is outside min_area .. max_area (None: no upper limit): their cells become 0, the
+    others are renumbered 1 .. n' in their old order, so still in raster order of their first cells.  labels (gh, gw) int32
+    with values 0 .. n, area (n) from label_stats.  Torch operators on whatever device the labels are on.
+    -> (labels', n', kept): kept int64 (n') = the old indices (label - 1) of the components that stay."""
+    labels = _labels_checked(labels)
+    min_area = _int_checked(min_area, "min_area", 0, 2 ** 31 - 1)
+    if max_area is not None:
+        max_area = _int_checked(max_area, "max_area", min_area, 2 ** 31 - 1)
+    as_numpy = not isinstance(labels, torch.Tensor)
+    lab = torch.as_tensor(labels)
+    a = torch.as_tensor(np.asarray(area) if not isinstance(area, torch.Tensor) else area).to(lab.device)
+    if a.ndim != 1 or a.is_floating_point():
+        raise ValueError("area is a 1-D integer array, one entry per label, got %s %s" % (a.dtype, tuple(a.shape)))
+    keep = a >= min_area
+    if max_area is not None:
+        keep &= a <= max_area
+    new_id = torch.cumsum(keep, 0, dtype=torch.int32) * keep                 # the new label of an old one, 0 if dropped
+    lut = torch.cat([torch.zeros(1, dtype=torch.int32, device=lab.device), new_id])
+    out = lut[lab.long()]
+    kept = torch.nonzero(keep)[:, 0]
+    out, kept_out = _back(as_numpy, out, kept)
+    return out, int(kept.numel()), kept_out
+
+
+def extract_objects(above, grid, min_height=2.5, min_area_m2=50.0, connectivity=8, nodata=-999.0):
+    """The objects of an nDSM: foreground = the valid cells of `above` ((gh, gw) float32 heights above ground, from ndsm()) with
+    above > float32(min_height); label(); label_stats(values=above, grid=grid); sieve_labels() at ceil(min_area_m2 / (xres
+    yres)) cells.  The defaults (2.5 m, 50 m^2 = two cells of a 5 m grid) are a choice for 5 m grids, not tuned on
+    real data.  -> (labels (gh, gw) int32 with 1 .. n' on the objects that stay, stats: the dict of label_stats restricted to
+    them); numpy if `above` came as numpy, device tensors otherwise."""
+    above = _on_grid(_dsm_bits(above), grid)
+    connectivity = _connectivity_checked(connectivity)
+    min_height, min_area_m2 = float(min_height), float(min_area_m2)
+    if not math.isfinite(min_height):
+        raise ValueError("min_height must be finite, got %r" % min_height)
+    if not (math.isfinite(min_area_m2) and min_area_m2 >= 0.0):
+        raise ValueError("min_area_m2 must be finite and >= 0, got %r" % min_area_m2)
+    min_cells = _int_checked(int(math.ceil(min_area_m2 / (float(grid.xres) * float(grid.yres)))), "min_area_m2 in cells", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(above)
+    fg = torch.isfinite(z) & (z != float(np.float32(nodata))) & (z > float(np.float32(min_height)))
+    labels, n = label(fg, connectivity)
+    stats = label_stats(labels, n, values=z, grid=grid, nodata=nodata)
+    labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
+    stats = {k: t[kept] for k, t in stats.items()}
+    return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
