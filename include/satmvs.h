@@ -652,7 +652,36 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   The entry initialises its outputs; n == 0 returns SMVS_OK without a launch.  values null <=> nvalid, vmin, vmax, qsum null.
  * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers, gw, gh >= 1, gw * gh < 2^31, connectivity 4 or 8,
  *   n >= 0; labels, n_out and workspace distinct from mask and from each other; every statistics output distinct from labels,
- *   values and the other outputs; workspace: smvs_dsm_label_workspace_bytes(gw, gh) bytes (0 = unsupported arguments). */
+ *   values and the other outputs; workspace: smvs_dsm_label_workspace_bytes(gw, gh) bytes (0 = unsupported arguments).
+ *
+ * Registration (csrc/dsm_coreg.hip).  A cell is valid iff it is finite and != (float)nodata, as above.
+ * smvs_dsm_shift_stats: a (gha, gwa), the moving grid, and b (ghb, gwb), the fixed one, float32 (device), read only, of equal
+ *   cell sizes (the caller's business).  For every shift (sx, sy) in [-radius, radius]^2, cell (r, c) of b is paired with cell
+ *   (r + oy + sy, c + ox + sx) of a; a partner off a's grid is no pair.  d = ((double)a - (double)b) - dz0, two IEEE float64
+ *   subtractions in this order, not contracted.  The pair counts iff both cells are valid and |d| <= trim (inclusive).
+ *   q = llrint(d * 256), halves to even: the difference in units of 2^-8 m (3.9 mm).  stats (device, int64, (2 radius + 1)^2
+ *   x 3): stats[((sy + radius) (2 radius + 1) + (sx + radius)) 3 + {0, 1, 2}] = n, the sum of q, the sum of q^2 over the
+ *   counted pairs.  trim <= 256 gives |q| <= 2^16, so the sum of q^2 stays below 2^63 for any grid accepted.  Integer sums:
+ *   the bits do not depend on the order of the additions, are equal from run to run and equal the numpy statement of these
+ *   rules.  The entry writes every element of stats (no atomics: per-workgroup partial sums in the workspace, folded by a
+ *   second kernel in a fixed order).  No host synchronisation.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; sizes >= 1, gwa * gha and gwb * ghb < 2^31;
+ *   0 <= radius <= 32; |ox|, |oy| < 2^30; dz0 finite; 0 < trim <= 256; stats and workspace distinct from a, b and each
+ *   other; workspace: smvs_dsm_shift_workspace_bytes(gwa, gha, gwb, ghb, radius) bytes (0 = unsupported arguments).
+ * smvs_dsm_regrid: src (ghs, gws) float32 (device) on the grid grid4_src = (e0, n0, xres, yres) (HOST doubles, the centre of
+ *   cell (0, 0) and the cell sizes, as in smvs_rpc_dsm_render) resampled onto the (ghd, gwd) grid grid4_dst.  For the
+ *   destination cell (r, c): E = e0d + c xresd, N = n0d - r yresd, u = (E - e0s) / xress, v = (n0s - N) / yress, IEEE
+ *   float64, not contracted (the cell rule of smvs_rpc_dsm_bin).  A tap is a source cell; a tap off the grid or invalid
+ *   makes the cell nodata.
+ *   mode 0 (nearest): the one tap (floor(v + 0.5), floor(u + 0.5)).
+ *   mode 1 (bilinear): i = floor(u), j = floor(v), fx = u - i, fy = v - j; column i has the weight 1 - fx, column i + 1 fx,
+ *   row j 1 - fy, row j + 1 fy; a tap whose column or row weight is exactly 0 is NOT read (so a regrid onto an
+ *   integer-aligned grid is a crop) and stands as 0.0 in the value (float)((1 - fy) ((1 - fx) z00 + fx z01) + fy ((1 - fx) z10
+ *   + fx z11) + dz), float64 operations in this order, z00 = (j, i), z01 = (j, i + 1), z10 = (j + 1, i), z11 = (j + 1, i + 1).
+ *   A cell that takes one tap with the weight 1 (always in mode 0) gets (float)((double)z + dz), and with dz == 0 the tap's
+ *   bits.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; sizes >= 1, gws * ghs and gwd * ghd < 2^31;
+ *   finite origins, finite resolutions > 0; mode 0 or 1; dz finite; out distinct from src. */
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -683,6 +712,12 @@ int smvs_dsm_label(const unsigned char* mask, int gw, int gh, int connectivity, 
 int smvs_dsm_label_stats(const int* labels, const float* values, int gw, int gh, float nodata, int n,
                          int* area, int* bbox, long long* rc_sum,
                          int* nvalid, float* vmin, float* vmax, long long* qsum, void* stream);
+size_t smvs_dsm_shift_workspace_bytes(int gwa, int gha, int gwb, int ghb, int radius);
+int smvs_dsm_shift_stats(const float* a, int gwa, int gha, const float* b, int gwb, int ghb, float nodata,
+                         int ox, int oy, int radius, double dz0, double trim,
+                         long long* stats, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_regrid(const float* src, int gws, int ghs, const double* grid4_src, float nodata,
+                    const double* grid4_dst, int gwd, int ghd, int mode, double dz, float* out, void* stream);
 
 #ifdef __cplusplus
 }

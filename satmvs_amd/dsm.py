@@ -21,6 +21,13 @@ and the objects that stand on the ground (connected components in scipy.ndimage.
     labels, n = label(above > 10.0, connectivity=4)            # the building block; label_stats(), sieve_labels()
     voids, n_voids = label(~(np.isfinite(dsm) & (dsm != -999.0)))   # the void regions fill_voids could not reach
 
+and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
+
+    reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
+    on_gt = regrid(dsm, reg["grid"], gt_grid, dz=-reg["dz"])   # onto the other grid, bilinear or nearest
+    scores = compare_dsms(dsm, grid, gt, gt_grid)              # {"shift", "before", "after"}: dsm_metrics around the registration
+    diff, labels, stats = changes(new, new_grid, old, old_grid)   # rises and falls above 2.5 m and 50 m^2 as objects
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -43,6 +50,8 @@ smvs_dsm_morph / smvs_dsm_ground take window minima and maxima as row and column
 doubling in LDS whose cost does not grow with the radius but with its logarithm.
 smvs_dsm_label is a union-find over cell indices (tiles in LDS, tile borders with integer min atomics, a three-level scan
 for the numbering); smvs_dsm_label_stats reduces along rows and columns on chip before its integer atomics.
+smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
+shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -690,6 +699,239 @@ def extract_objects(above, grid, min_height=2.5, min_area_m2=50.0, connectivity=
     labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
     stats = {k: t[kept] for k, t in stats.items()}
     return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}
+
+
+# ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
+REGRID_MODES = {"nearest": 0, "bilinear": 1}
+MAX_SHIFT_RADIUS = 32
+MAX_TRIM = 256.0
+
+
+def _grid_checked(grid, name):
+    vals = (grid.e0, grid.n0, grid.xres, grid.yres)
+    if not all(math.isfinite(float(v)) for v in vals) or not (float(grid.xres) > 0.0 and float(grid.yres) > 0.0):
+        raise ValueError("%s needs finite origins and positive finite resolutions, got %r" % (name, grid))
+    gw, gh = int(grid.width), int(grid.height)
+    if gw < 1 or gh < 1 or gw * gh >= 2 ** 31:
+        raise ValueError("%s has positive sizes and fewer than 2^31 cells, got %d x %d" % (name, gw, gh))
+    return grid
+
+
+def _finite(v, name):
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError("%s must be finite, got %r" % (name, v))
+    return v
+
+
+def _trim_checked(trim):
+    trim = float(trim)
+    if not (0.0 < trim <= MAX_TRIM):
+        raise ValueError("trim must be in (0, %g] m, got %r" % (MAX_TRIM, trim))
+    return trim
+
+
+def regrid(dsm, grid, to_grid, mode="bilinear", dz=0.0, nodata=-999.0):
+    """A DSM on `grid` resampled onto `to_grid` (include/satmvs.h smvs_dsm_regrid, DESIGN.md section 9, "Registration"): every
+    cell of to_grid takes the source cell its centre falls in ("nearest") or the bilinear mean of the four around it
+    ("bilinear", float64), plus dz [m]; a tap that is off the grid or invalid makes the cell nodata, and a tap with the
+    weight 0 is not read, so onto a grid whose centres coincide with the source's the result is a crop, bit for bit with
+    dz = 0.  dsm (grid.height, grid.width) of any real dtype (taken as float32), numpy or a device tensor.
+    -> (to_grid.height, to_grid.width) float32; numpy if the DSM came as numpy, a device tensor otherwise."""
+    if mode not in REGRID_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(REGRID_MODES), mode))
+    _grid_checked(grid, "grid")
+    _grid_checked(to_grid, "to_grid")
+    dz = _finite(dz, "dz")
+    dsm = _dsm_converted(dsm, grid)
+    z, as_numpy = _to_device(dsm, torch.float32)
+    out = torch.empty((int(to_grid.height), int(to_grid.width)), dtype=torch.float32, device=z.device)
+    _call(z.device, "smvs_dsm_regrid", z, int(grid.width), int(grid.height), grid.grid4(), float(nodata), to_grid.grid4(),
+          int(to_grid.width), int(to_grid.height), REGRID_MODES[mode], dz, out)
+    return _back(as_numpy, out)
+
+
+def shift_stats(a, b, offset=(0, 0), radius=8, dz0=0.0, trim=256.0, nodata=-999.0):
+    """The statistics of a - b under every integer shift (include/satmvs.h smvs_dsm_shift_stats): for (sx, sy) in [-radius,
+    radius]^2 cell (r, c) of b meets cell (r + oy + sy, c + ox + sx) of a, offset = (ox, oy); d = a - b - dz0 in float64; the
+    pair counts iff both cells are valid and |d| <= trim [m]; q = d in units of 2^-8 m, rounded half to even.
+    a, b: (gh, gw) float32 grids of equal cell size, numpy or device tensors, never converted; 0 <= radius <= 32; 0 < trim <= 256.
+    -> (2 radius + 1, 2 radius + 1, 3) int64, [sy + radius, sx + radius] = (n, sum q, sum q^2), exact integer sums with
+    equal bits from run to run; numpy if `a` came as numpy, a device tensor otherwise."""
+    a, b = _dsm_bits(a), _dsm_bits(b)
+    ox, oy = _int_pair(offset, "offset")
+    if abs(ox) >= 2 ** 30 or abs(oy) >= 2 ** 30:
+        raise ValueError("offset must be below 2^30 in size, got %r" % ((ox, oy),))
+    radius = _int_checked(radius, "radius", 0, MAX_SHIFT_RADIUS)
+    dz0 = _finite(dz0, "dz0")
+    trim = _trim_checked(trim)
+    za, as_numpy = _to_device(a)
+    zb, _ = _to_device(b, dev=za.device)
+    (gha, gwa), (ghb, gwb) = za.shape, zb.shape
+    nbytes = _lib.load().smvs_dsm_shift_workspace_bytes(gwa, gha, gwb, ghb, radius)
+    if nbytes == 0:
+        raise ValueError("unsupported shift search: %d x %d against %d x %d cells, radius %d" % (gwa, gha, gwb, ghb, radius))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=za.device)
+    side = 2 * radius + 1
+    stats = torch.empty((side, side, 3), dtype=torch.int64, device=za.device)
+    _call(za.device, "smvs_dsm_shift_stats", za, gwa, gha, zb, gwb, ghb, float(nodata), ox, oy, radius, dz0, trim, stats, ws, nbytes)
+    return _back(as_numpy, stats)
+
+
+def best_shift(stats, min_overlap=0.5):
+    """The selection rule of coregister on one (2R + 1, 2R + 1, 3) array of shift_stats, on the host in exact Python integers:
+    a shift is eligible iff n >= max(2, ceil(min_overlap max n)); the best is the eligible one with the lowest variance
+    (n sum q^2 - (sum q)^2) / n^2, compared by cross-multiplication; ties go to the smaller sx^2 + sy^2, then the lower sy,
+    then the lower sx.  The sub-cell step per axis is the vertex of the parabola through the variances at the best shift and
+    its two neighbours, d = (c- - c+) / (2 (c- - 2 c0 + c+)) in float64 clamped to +-1/2, 0 where a neighbour is missing or not
+    eligible or the denominator is <= 0.
+    -> None if no shift is eligible, else dict: shift (sx, sy), subcell (dx, dy), n, sum_q, variance_q (float64, in q^2)."""
+    st = np.asarray(stats.detach().cpu() if isinstance(stats, torch.Tensor) else stats)
+    if st.ndim != 3 or st.shape[0] != st.shape[1] or st.shape[0] % 2 != 1 or st.shape[2] != 3:
+        raise ValueError("stats is (2R + 1, 2R + 1, 3), got %s" % (tuple(st.shape),))
+    min_overlap = float(min_overlap)
+    if not 0.0 <= min_overlap <= 1.0:
+        raise ValueError("min_overlap must be in 0 .. 1, got %r" % min_overlap)
+    R = st.shape[0] // 2
+    rows = st.tolist()                                        # Python integers from here on
+    need = max(2, int(math.ceil(min_overlap * max(max(v[0] for v in row) for row in rows))))
+
+    def cost(sx, sy):
+        """(numerator, denominator) of the variance of an eligible shift on the grid, else None."""
+        if abs(sx) > R or abs(sy) > R:
+            return None
+        n, s1, s2 = rows[sy + R][sx + R]
+        return (n * s2 - s1 * s1, n * n) if n >= need else None
+
+    best = None
+    for sy in range(-R, R + 1):
+        for sx in range(-R, R + 1):
+            c = cost(sx, sy)
+            if c is None:
+                continue
+            key = (sx * sx + sy * sy, sy, sx)
+            if best is None:
+                lower = True
+            else:
+                lhs, rhs = c[0] * best[0][1], best[0][0] * c[1]
+                lower = lhs < rhs or (lhs == rhs and key < best[1])
+            if lower:
+                best = (c, key)
+    if best is None:
+        return None
+    (num, den), (_, sy, sx) = best
+
+    def vertex(lo, hi):
+        if lo is None or hi is None:
+            return 0.0
+        c0, cl, ch = num / den, lo[0] / lo[1], hi[0] / hi[1]
+        bend = cl - 2.0 * c0 + ch
+        return min(0.5, max(-0.5, 0.5 * (cl - ch) / bend)) if bend > 0.0 else 0.0
+
+    n, s1, _ = rows[sy + R][sx + R]
+    return {"shift": (sx, sy), "subcell": (vertex(cost(sx - 1, sy), cost(sx + 1, sy)), vertex(cost(sx, sy - 1), cost(sx, sy + 1))),
+            "n": n, "sum_q": s1, "variance_q": num / den}
+
+
+def coregister(a, grid_a, b, grid_b, radius=8, trim=10.0, min_overlap=0.5, rounds=2, nodata=-999.0):
+    """The offset between two DSMs of equal cell size: the planimetric shift, in whole cells within +-radius of where the
+    georeferences put them, that minimises the variance of a - b, refined to a fraction of a cell by a parabola per axis,
+    and the vertical offset from the mean (best_shift for the rule).  Round 1 runs shift_stats with dz0 = 0 and trim = 256 m;
+    every later round with dz0 = the last dz and the caller's trim [m], which keeps changes and blunders out of the sums.
+    The defaults (radius 8, trim 10 m, two rounds) are a choice for 5 m grids on a synthetic scene, not tuned
+    on real data.  a is the moving DSM, b the fixed one; both (gh, gw) float32, never converted.
+    -> dict: shift_cells (sx, sy): b's cell (r, c) meets a's cell (r + oy + sy, c + ox + sx); subcell (dx, dy) in cells;
+    de, dn [m]: what to add to a's georeference; grid: grid_a moved by (de, dn) -- nothing is resampled, registration changes
+    the world file; dz [m] = dz0 + sum q / (256 n): the mean of a - b over the counted pairs, so a - dz meets b
+    (regrid(a, grid, grid_b, dz=-dz)); n; std [m] of a - b at the best shift; offset (ox, oy); stats: the last round's
+    shift_stats.  Raises ValueError("no overlap") when no shift has two pairs."""
+    a, b = _on_grid(_dsm_bits(a), grid_a), _on_grid(_dsm_bits(b), grid_b)
+    _grid_checked(grid_a, "grid_a")
+    _grid_checked(grid_b, "grid_b")
+    if float(grid_a.xres) != float(grid_b.xres) or float(grid_a.yres) != float(grid_b.yres):
+        raise ValueError("coregister needs grids of equal xres and equal yres (%r, %r against %r, %r): regrid() one DSM onto "
+                         "the other's resolution first" % (grid_a.xres, grid_a.yres, grid_b.xres, grid_b.yres))
+    radius = _int_checked(radius, "radius", 0, MAX_SHIFT_RADIUS)
+    rounds = _int_checked(rounds, "rounds", 1, 16)
+    trim = _trim_checked(trim)
+    min_overlap = float(min_overlap)
+    if not 0.0 <= min_overlap <= 1.0:
+        raise ValueError("min_overlap must be in 0 .. 1, got %r" % min_overlap)
+    xres, yres = float(grid_a.xres), float(grid_a.yres)
+    u0, v0 = (float(grid_b.e0) - float(grid_a.e0)) / xres, (float(grid_a.n0) - float(grid_b.n0)) / yres
+    ox, oy = math.floor(u0 + 0.5), math.floor(v0 + 0.5)      # b's cell (0, 0) in a's index space, to the nearest cell
+    if abs(ox) >= 2 ** 30 or abs(oy) >= 2 ** 30:
+        raise ValueError("no overlap")
+    fx, fy = u0 - ox, v0 - oy                                # what the rounding left, carried into de and dn
+    dz, pick, stats = 0.0, None, None
+    for k in range(rounds):
+        stats = shift_stats(a, b, (ox, oy), radius, dz, 256.0 if k == 0 else trim, nodata)
+        pick = best_shift(stats, min_overlap)
+        if pick is None:
+            raise ValueError("no overlap")
+        dz = dz + pick["sum_q"] / (256.0 * pick["n"])
+    (sx, sy), (dx, dy) = pick["shift"], pick["subcell"]
+    de, dn = (fx - sx - dx) * xres, (sy + dy - fy) * yres
+    moved = DSMGrid(float(grid_a.e0) + de, float(grid_a.n0) + dn, grid_a.xres, grid_a.yres, grid_a.width, grid_a.height)
+    return {"shift_cells": (sx, sy), "subcell": (dx, dy), "de": de, "dn": dn, "dz": dz, "n": pick["n"],
+            "std": math.sqrt(max(pick["variance_q"], 0.0)) / 256.0, "grid": moved, "offset": (ox, oy), "stats": stats}
+
+
+def _same_resolution(g, h):
+    return float(g.xres) == float(h.xres) and float(g.yres) == float(h.yres)
+
+
+def _registered(a, grid_a, b, grid_b, register, nodata, **coregister_kw):
+    """(a on grid_b as the georeferences say, a on grid_b after registration, the coregister dict or None)."""
+    plain = regrid(a, grid_a, grid_b, nodata=nodata)
+    if not register:
+        return plain, plain, None
+    if _same_resolution(grid_a, grid_b):
+        a32 = a.to(torch.float32) if isinstance(a, torch.Tensor) else np.asarray(a, np.float32)
+        shift = coregister(a32, grid_a, b, grid_b, nodata=nodata, **coregister_kw)
+    else:                                                    # the nearest grid of b's resolution is b's own
+        shift = coregister(plain, grid_b, b, grid_b, nodata=nodata, **coregister_kw)
+    moved = DSMGrid(float(grid_a.e0) + shift["de"], float(grid_a.n0) + shift["dn"], grid_a.xres, grid_a.yres, grid_a.width, grid_a.height)
+    shift = dict(shift, grid=moved)
+    return plain, regrid(a, moved, grid_b, dz=-shift["dz"], nodata=nodata), shift
+
+
+def compare_dsms(est, grid_est, gt, grid_gt, register=True, nodata=-999.0, thresholds=(2.5, 7.5), **coregister_kw):
+    """Score a DSM against a reference DSM on another grid: est is regridded (bilinear) onto grid_gt and scored with dsm_metrics
+    ("before"); with `register` the offset between the two is found with coregister (on est itself where the resolutions are
+    equal, else on est regridded onto grid_gt), est is regridded again from the corrected grid with -dz, and scored ("after").
+    gt (grid_gt's shape) float32.  -> {"shift": the coregister dict (None without register), "before": ..., "after": ...}."""
+    _on_grid(gt, grid_gt)
+    plain, moved, shift = _registered(est, grid_est, gt, grid_gt, register, nodata, **coregister_kw)
+    g = torch.as_tensor(gt).to(plain.device) if isinstance(plain, torch.Tensor) else torch.as_tensor(np.asarray(gt))
+    before = dsm_metrics(torch.as_tensor(plain), g, float(np.float32(nodata)), thresholds)
+    after = dsm_metrics(torch.as_tensor(moved), g, float(np.float32(nodata)), thresholds) if register else before
+    return {"shift": shift, "before": before, "after": after}
+
+
+def changes(a, grid_a, b, grid_b, min_dh=2.5, min_area_m2=50.0, register=True, connectivity=8, nodata=-999.0, **coregister_kw):
+    """What changed between two epochs: a is registered to b (coregister, unless register=False) and regridded onto grid_b;
+    diff = a - b in float32 where both are valid, nodata elsewhere; the rises (diff > min_dh) and the falls (-diff > min_dh)
+    each go through extract_objects with min_area_m2, and the falls' labels are numbered after the rises'.
+    -> (diff (grid_b's shape) float32, labels int32, stats: extract_objects' dict over rises then falls, heights as |diff|,
+    plus sign int8 (+1 rise, -1 fall)); numpy if `a` came as numpy, device tensors otherwise."""
+    _on_grid(b, grid_b)
+    _, moved, _ = _registered(a, grid_a, b, grid_b, register, nodata, **coregister_kw)
+    as_numpy = not isinstance(moved, torch.Tensor)
+    za, _ = _to_device(moved)
+    zb, _ = _to_device(b if isinstance(b, torch.Tensor) else np.asarray(b, np.float32), torch.float32, za.device)
+    nd = float(np.float32(nodata))
+    both = torch.isfinite(za) & (za != nd) & torch.isfinite(zb) & (zb != nd)
+    d = za - zb
+    diff = torch.where(both, d, torch.full_like(d, nd))
+    up_labels, up = extract_objects(diff, grid_b, min_dh, min_area_m2, connectivity, nodata)
+    down_labels, down = extract_objects(torch.where(both, -d, torch.full_like(d, nd)), grid_b, min_dh, min_area_m2, connectivity, nodata)
+    n_up = int(up["area"].numel())
+    labels = up_labels + torch.where(down_labels > 0, down_labels + n_up, torch.zeros_like(down_labels))
+    stats = {k: torch.cat([up[k], down[k]]) for k in up}
+    stats["sign"] = torch.cat([torch.ones(n_up, dtype=torch.int8, device=za.device),
+                               -torch.ones(int(down["area"].numel()), dtype=torch.int8, device=za.device)])
+    return _back(as_numpy, diff), _back(as_numpy, labels), {k: _back(as_numpy, v) for k, v in stats.items()}
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
