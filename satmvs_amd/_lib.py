@@ -3,6 +3,11 @@
 There is no CPU fallback: if the library is missing, or a tensor is not on a HIP device, the
 call raises.  PyTorch is used only for device memory and streams; every pointer handed to the
 library is `tensor.data_ptr()` and the stream is torch's current HIP stream.
+
+The package makes every native call through `launch(dev, name, *args)`: the arguments in the order of the
+entry's declaration in include/satmvs.h, tensors and numpy arrays as they are (marshal() turns them into
+device / host pointers, None is NULL), without the trailing stream -- launch() selects `dev` and appends its
+current stream.  `call` is the raw form underneath, for a caller that brings its own pointers and stream.
 """
 from __future__ import annotations
 
@@ -10,6 +15,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -240,6 +246,35 @@ def call(name, *args):
 
 def current_stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _raw_stream(index):
+    """Handle of device `index`'s current stream without the torch.cuda.Stream object around it (the one private torch call of
+    the package; current_stream()'s way where a torch build does not have it)."""
+    try:
+        return torch._C._cuda_getCurrentRawStream(index)
+    except AttributeError:
+        return torch.cuda.current_stream(index).cuda_stream
+
+
+def marshal(args):
+    """The arguments of a native call as ctypes takes them: a tensor becomes its data pointer, a numpy array its host
+    pointer, and anything else (None = NULL, numbers, pointers, ptr_array results) stays what it is.  Pure: needs no GPU."""
+    return [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a
+            for a in args]
+
+
+def launch(dev, name, *args):
+    """One native call on dev's current stream: call(name, *marshal(args), stream) with `dev` selected.  Passing the
+    tensors themselves keeps them alive until the call has been enqueued."""
+    if dev.index == torch.cuda.current_device():
+        # `dev` is selected already (every call of a one-GPU process; autograd selects a node's device for its backward): no guard
+        # to enter and leave, and the stream handle without the torch.cuda.Stream object around it -- the eager training step is
+        # host-bound and makes ~10^4 of these calls (profiles/launch_marshal_train_step.txt)
+        call(name, *marshal(args), C.c_void_p(_raw_stream(dev.index)))
+        return
+    with torch.cuda.device(dev):
+        call(name, *marshal(args), current_stream(dev))
 
 
 def require_device(*tensors):

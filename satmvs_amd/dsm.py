@@ -58,7 +58,6 @@ the image bilinearly.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -204,12 +203,7 @@ def _maps(heights, rpcs, masks, dev):
     return out
 
 
-def _call(dev, name, *args):
-    """One native call on dev's current stream: tensors go as device pointers, numpy arrays as host pointers, None as NULL."""
-    args = [_lib.ptr(a) if isinstance(a, torch.Tensor) else a.ctypes.data_as(ctypes.c_void_p) if isinstance(a, np.ndarray) else a
-            for a in args]
-    with torch.cuda.device(dev):
-        _lib.call(name, *args, _lib.current_stream(dev))
+_call = _lib.launch     # one native call on dev's current stream: tensors as device pointers, numpy arrays as host pointers, None as NULL
 
 
 def _bin(h, r, m, tm7, grid4, gw, gh, cell, count, east=None, north=None):

@@ -87,9 +87,7 @@ class GeneratedHeights:
             from .. import _lib
             out = torch.empty(tuple(self.shape), dtype=torch.float32, device=self.prev.device)
             gs = self.c_struct()
-            with torch.cuda.device(self.prev.device):
-                _lib.call("smvs_height_hypotheses", ctypes.addressof(gs), _lib.ptr(out), out.shape[0], self.H, self.W,
-                          _lib.current_stream(self.prev.device))
+            _lib.launch(self.prev.device, "smvs_height_hypotheses", ctypes.addressof(gs), out, out.shape[0], self.H, self.W)
             return out
         if self.var is not None:
             cur = F.interpolate(self.prev.unsqueeze(1), [self.H, self.W], mode="bilinear", align_corners=False)

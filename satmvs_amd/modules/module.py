@@ -18,6 +18,7 @@ torch.manual_seed yields the same initial parameters.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import threading
 
@@ -74,6 +75,17 @@ def _packed(kind, device, tensors, build):
                 del _PACK_CACHE[mine[0]]                   # oldest entry of this device (dicts keep insertion order)
             hit = _PACK_CACHE.setdefault(key, (packed, refs))
     return hit[0]
+
+
+def _packed_weights(kind, device, tensors, size_query, pack_entry):
+    """_packed() for a whole module: `tensors` as float32 on `device`, packed by the native entry `pack_entry` = (name, *ints) into
+    a buffer of `size_query` = (name, *ints) floats."""
+    def build():
+        packed = torch.empty(getattr(_lib.load(), size_query[0])(*size_query[1:]), dtype=torch.float32, device=device)
+        src = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in tensors]
+        _lib.launch(device, pack_entry[0], _lib.ptr_array(src), *pack_entry[1:], packed)
+        return packed
+    return _packed(kind, device, tensors, build)
 
 
 def _workspace(module, attr, nbytes, dev):
@@ -293,15 +305,8 @@ class _REDCore(nn.Module):
         """Device buffer in the kernel's layout; rebuilt when any parameter changed (optimizer step, load)."""
         tensors = _tensors_by_path(self, self._PARAM_ORDER)
         in_ch = tensors[self._PARAM_ORDER.index("conv1.conv.weight")].shape[1]
-
-        def build():
-            lib = _lib.load()
-            packed = torch.empty(lib.smvs_red_packed_floats(in_ch), dtype=torch.float32, device=device)
-            src = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in tensors]
-            with torch.cuda.device(device):
-                _lib.call("smvs_red_pack_weights", _lib.ptr_array(src), in_ch, _lib.ptr(packed), _lib.current_stream(device))
-            return packed
-        return _packed("red", device, tensors, build), in_ch
+        packed = _packed_weights("red", device, tensors, ("smvs_red_packed_floats", in_ch), ("smvs_red_pack_weights", in_ch))
+        return packed, in_ch
 
     def native_step(self, cost, s1, s2, s3, s4):
         """One plane through smvs_red_step_fwd (HIP).  States are updated in place and returned."""
@@ -318,9 +323,7 @@ class _REDCore(nn.Module):
             raise ValueError("plane %dx%d is not a positive multiple of 8" % (h, w))
         ws = _workspace(self, "_ws_step", nbytes, dev)
         out = torch.empty((b, 1, h, w), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_red_step_fwd", _lib.ptr(packed), _lib.ptr(cost), *[_lib.ptr(s) for s in states],
-                      _lib.ptr(out), _lib.ptr(ws), nbytes, b, c, h, w, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_red_step_fwd", packed, cost, *states, out, ws, nbytes, b, c, h, w)
         return (out, *states)
 
     def native_pred_planes(self, features, proj_matrices, depth_values, geo_model, use_qc, states, acc_state,
@@ -355,19 +358,13 @@ class _REDCore(nn.Module):
                 raise ValueError("states must be contiguous float32")
         target = acc_state if reg_volume is None else reg_volume
         name = "smvs_red_pred_planes" if reg_volume is None else "smvs_red_volume_planes"
-        with torch.cuda.device(dev):
-            if gen is not None:
-                import ctypes
-                gs = gen.c_struct()
-                _lib.call(name + "_gen", kind, _lib.ptr(feats[0]), _lib.ptr_array(feats[1:]), len(feats) - 1,
-                          _lib.ptr(geo), ctypes.addressof(gs), _lib.ptr(packed), *[_lib.ptr(s) for s in states],
-                          _lib.ptr(target), _lib.ptr(ws), nbytes, b, c, D, h, w, d_begin, d_end,
-                          _lib.current_stream(dev))
-            else:
-                _lib.call(name, kind, _lib.ptr(feats[0]), _lib.ptr_array(feats[1:]), len(feats) - 1,
-                          _lib.ptr(geo), _lib.ptr(depth), is4d | _lib.call_arith_bits(), _lib.ptr(packed), *[_lib.ptr(s) for s in states],
-                          _lib.ptr(target), _lib.ptr(ws), nbytes, b, c, D, h, w, d_begin, d_end,
-                          _lib.current_stream(dev))
+        if gen is not None:
+            gs = gen.c_struct()                                  # (alive until the call below has been enqueued)
+            name, heights = name + "_gen", (ctypes.addressof(gs),)
+        else:
+            heights = (depth, is4d | _lib.call_arith_bits())
+        _lib.launch(dev, name, kind, feats[0], _lib.ptr_array(feats[1:]), len(feats) - 1, geo, *heights, packed, *states, target, ws,
+                    nbytes, b, c, D, h, w, d_begin, d_end)
 
     def native_volume(self, features, proj_matrices, depth_values, geo_model, use_qc):
         """(B,D,H,W) regularised cost of the whole sweep without materialising the variance volume
@@ -619,16 +616,8 @@ class CostRegNet(nn.Module):
     def _packed_weights(self, device):
         tensors = _tensors_by_path(self, self._names())
         in_ch = tensors[0].shape[1]
-
-        def build():
-            lib = _lib.load()
-            packed = torch.empty(lib.smvs_costreg_packed_floats(in_ch), dtype=torch.float32, device=device)
-            src = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in tensors]
-            with torch.cuda.device(device):
-                _lib.call("smvs_costreg_pack_weights", _lib.ptr_array(src), in_ch, _lib.ptr(packed),
-                          _lib.current_stream(device))
-            return packed
-        return _packed("costreg", device, tensors, build), in_ch
+        packed = _packed_weights("costreg", device, tensors, ("smvs_costreg_packed_floats", in_ch), ("smvs_costreg_pack_weights", in_ch))
+        return packed, in_ch
 
     def _use_native(self, x):
         """Native kernels: GPU, eval mode (BatchNorm3d folded from its running statistics), no gradient wanted,
@@ -656,9 +645,7 @@ class CostRegNet(nn.Module):
             raise ValueError("volume %s is not a positive multiple of 8 in D, H, W" % (tuple(x.shape),))
         ws = _workspace(self, "_ws", nbytes, dev)
         out = torch.empty((b, 1, d, h, w), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_costreg_fwd", _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(ws), nbytes,
-                      b, c, d, h, w, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_costreg_fwd", packed, x, out, ws, nbytes, b, c, d, h, w)
         return out
 
     def forward(self, x):
@@ -742,17 +729,9 @@ class FeatureNet(nn.Module):
         """Parameters + BatchNorm running statistics repacked for the HIP kernels; cached until any of them
         changes (load_state_dict / an optimiser step / a training-mode forward bump the tensor versions)."""
         tensors = _tensors_by_path(self, self._names())
-
-        def build():
-            lib = _lib.load()
-            packed = torch.empty(lib.smvs_featnet_packed_floats(self.base_channels, self._arch()), dtype=torch.float32,
-                                 device=device)
-            src = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in tensors]
-            with torch.cuda.device(device):
-                _lib.call("smvs_featnet_pack_weights", _lib.ptr_array(src), self.base_channels, self._arch(),
-                          _lib.ptr(packed), _lib.current_stream(device))
-            return packed
-        return _packed("featnet%d" % self._arch(), device, tensors, build)
+        ints = (self.base_channels, self._arch())
+        return _packed_weights("featnet%d" % self._arch(), device, tensors, ("smvs_featnet_packed_floats", *ints),
+                               ("smvs_featnet_pack_weights", *ints))
 
     def _use_native(self, x):
         """Native kernels: GPU, eval mode (BatchNorm folded from running statistics), no gradient wanted, and
@@ -786,9 +765,7 @@ class FeatureNet(nn.Module):
         s1 = torch.empty((n, 4 * c, h // 4, w // 4), dtype=torch.float32, device=dev)
         s2 = torch.empty((n, 2 * c, h // 2, w // 2), dtype=torch.float32, device=dev)
         s3 = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_featnet_fwd", _lib.ptr(packed), _lib.ptr(x), _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(s3),
-                      _lib.ptr(ws), nbytes, n, h, w, c, self._arch(), _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_featnet_fwd", packed, x, s1, s2, s3, ws, nbytes, n, h, w, c, self._arch())
         return {"stage1": s1, "stage2": s2, "stage3": s3}
 
     def forward_views(self, imgs):
@@ -847,31 +824,27 @@ def softmax_depth_regression(reg, depth_values):
     if torch.is_grad_enabled() and reg.requires_grad:
         p = F.softmax(reg, dim=1)
         return depth_regression(p, gen.materialize() if gen is not None else depth_values), p.max(1)[0]
-    if gen is not None:
-        import ctypes
-        dev = _lib.require_device(reg, gen.prev)
-        r = reg.detach().to(torch.float32).contiguous()
-        B, D, H, W = r.shape
-        depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        conf = torch.empty_like(depth)
-        gs = gen.c_struct()
-        with torch.cuda.device(dev):
-            _lib.call("smvs_softmax_regress_fwd_gen", _lib.ptr(r), ctypes.addressof(gs), _lib.ptr(depth), _lib.ptr(conf),
-                      B, D, H, W, _lib.current_stream(dev))
-        return depth, conf
-    dev = _lib.require_device(reg, depth_values)
-    r = reg.detach().to(torch.float32).contiguous()
+    gs = gen.c_struct() if gen is not None else None            # the kernel's argument struct: alive until the launch below returns
+    dev, r, suffix, heights = _regress_operands(reg, depth_values, gen, gs)
     B, D, H, W = r.shape
-    dv = depth_values.detach().to(torch.float32).contiguous()
-    is4d = 1 if dv.dim() == 4 else 0
-    if is4d and tuple(dv.shape) != (B, D, H, W):
-        dv = F.interpolate(dv, [H, W], mode="bilinear", align_corners=False).contiguous()
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     conf = torch.empty_like(depth)
-    with torch.cuda.device(dev):
-        _lib.call("smvs_softmax_regress_fwd", _lib.ptr(r), _lib.ptr(dv), is4d, _lib.ptr(depth), _lib.ptr(conf),
-                  B, D, H, W, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_softmax_regress_fwd" + suffix, r, *heights, depth, conf, B, D, H, W)
     return depth, conf
+
+
+def _regress_operands(reg, depth_values, gen, gs):
+    """(device, reg as contiguous float32, entry-name suffix, height arguments) of a native regression.  Generated heights take the
+    `_gen` entry and the address of `gs`, gen's struct, which the caller owns; a tensor of heights goes as (depth_values, is4d)."""
+    dev = _lib.require_device(reg, gen.prev if gen is not None else depth_values)
+    r = reg.detach().to(torch.float32).contiguous()
+    if gen is not None:
+        return dev, r, "_gen", (ctypes.addressof(gs),)
+    dv = depth_values.detach().to(torch.float32).contiguous()
+    is4d = 1 if dv.dim() == 4 else 0
+    if is4d and tuple(dv.shape) != tuple(r.shape):
+        dv = F.interpolate(dv, [r.shape[2], r.shape[3]], mode="bilinear", align_corners=False).contiguous()
+    return dev, r, "", (dv, is4d)
 
 
 def window_depth_regression(reg, depth_values, lamb=None):
@@ -897,32 +870,13 @@ def window_depth_regression(reg, depth_values, lamb=None):
         if dv.dim() == 2:
             dv = dv.view(*dv.shape, 1, 1)
         return depth, conf, lamb * torch.sum((dv - depth.unsqueeze(1)) ** 2 * p, dim=1) ** 0.5
-    if gen is not None:
-        import ctypes
-        dev = _lib.require_device(reg, gen.prev)
-        r = reg.detach().to(torch.float32).contiguous()
-        B, D, H, W = r.shape
-        depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        conf = torch.empty_like(depth)
-        var = torch.empty_like(depth) if lamb is not None else None
-        gs = gen.c_struct()
-        with torch.cuda.device(dev):
-            _lib.call("smvs_window_regress_fwd_gen", _lib.ptr(r), ctypes.addressof(gs), _lib.ptr(depth), _lib.ptr(conf),
-                      _lib.ptr(var) if var is not None else None, float(lamb or 0.0), B, D, H, W, _lib.current_stream(dev))
-        return (depth, conf) if lamb is None else (depth, conf, var)
-    dev = _lib.require_device(reg, depth_values)
-    r = reg.detach().to(torch.float32).contiguous()
+    gs = gen.c_struct() if gen is not None else None            # the kernel's argument struct: alive until the launch below returns
+    dev, r, suffix, heights = _regress_operands(reg, depth_values, gen, gs)
     B, D, H, W = r.shape
-    dv = depth_values.detach().to(torch.float32).contiguous()
-    is4d = 1 if dv.dim() == 4 else 0
-    if is4d and tuple(dv.shape) != (B, D, H, W):
-        dv = F.interpolate(dv, [H, W], mode="bilinear", align_corners=False).contiguous()
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     conf = torch.empty_like(depth)
     var = torch.empty_like(depth) if lamb is not None else None
-    with torch.cuda.device(dev):
-        _lib.call("smvs_window_regress_fwd", _lib.ptr(r), _lib.ptr(dv), is4d, _lib.ptr(depth), _lib.ptr(conf),
-                  _lib.ptr(var) if var is not None else None, float(lamb or 0.0), B, D, H, W, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_window_regress_fwd" + suffix, r, *heights, depth, conf, var, float(lamb or 0.0), B, D, H, W)
     return (depth, conf) if lamb is None else (depth, conf, var)
 
 
@@ -944,17 +898,11 @@ class StreamingRegression:
         dv = depth_values.detach().to(torch.float32).contiguous()
         is4d = 1 if dv.dim() == 4 else 0
         D = dv.shape[1]
-        with torch.cuda.device(dev):
-            _lib.call("smvs_stream_regress_step", _lib.ptr(r), _lib.ptr(dv), is4d, _lib.ptr(self.state[0]),
-                      _lib.ptr(self.state[1]), _lib.ptr(self.state[2]), self.B, D, self.H, self.W, d,
-                      _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_stream_regress_step", r, dv, is4d, *self.state, self.B, D, self.H, self.W, d)
 
     def result(self):
         dev = self.state.device
         depth = torch.empty((self.B, self.H, self.W), dtype=torch.float32, device=dev)
         conf = torch.empty_like(depth)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_stream_regress_final", _lib.ptr(self.state[0]), _lib.ptr(self.state[1]),
-                      _lib.ptr(self.state[2]), _lib.ptr(depth), _lib.ptr(conf), self.B * self.H * self.W,
-                      _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_stream_regress_final", *self.state, depth, conf, self.B * self.H * self.W)
         return depth, conf

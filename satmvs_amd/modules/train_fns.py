@@ -68,9 +68,7 @@ class _GroupNorm1Fn(torch.autograd.Function):
         y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
         stats = torch.empty((B, 2), dtype=torch.float32, device=dev)
         ws = _gn_scratch(dev, 2 * B * ((C * H * W + 4095) // 4096))
-        with torch.cuda.device(dev):
-            _lib.call("smvs_groupnorm1_fwd", _lib.ptr(x), xbs, _lib.ptr(w), _lib.ptr(b), float(eps), int(act), _lib.ptr(y),
-                      _lib.ptr(stats), _lib.ptr(ws), B, C, H * W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_groupnorm1_fwd", x, xbs, w, b, float(eps), int(act), y, stats, ws, B, C, H * W)
         ctx.save_for_backward(x, w, y, stats)
         ctx.meta = (xbs, int(act))
         return y
@@ -87,9 +85,7 @@ class _GroupNorm1Fn(torch.autograd.Function):
         dg = torch.empty((C,), dtype=torch.float32, device=dev)
         db = torch.empty((C,), dtype=torch.float32, device=dev)
         ws = _gn_scratch(dev, 2 * B * C * ((H * W + 4095) // 4096))
-        with torch.cuda.device(dev):
-            _lib.call("smvs_groupnorm1_bwd", _lib.ptr(dy), _lib.ptr(x), xbs, _lib.ptr(y), _lib.ptr(w), _lib.ptr(stats), act,
-                      _lib.ptr(dx), C * H * W, _lib.ptr(dg), _lib.ptr(db), _lib.ptr(ws), B, C, H * W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_groupnorm1_bwd", dy, x, xbs, y, w, stats, act, dx, C * H * W, dg, db, ws, B, C, H * W)
         return dx, dg, db, None, None
 
 
@@ -106,9 +102,8 @@ class _GroupNormPairFn(torch.autograd.Function):
         ws_ = [_f32c_fast(t.detach()) for t in (w1, b1, w2, b2)]
         y = torch.empty_like(x)
         stats = torch.empty((2 * B, 2), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_groupnorm1_pair_fwd", _lib.ptr(x), _lib.ptr(ws_[0]), _lib.ptr(ws_[1]), _lib.ptr(ws_[2]), _lib.ptr(ws_[3]), float(eps),
-                      int(act), _lib.ptr(y), _lib.ptr(stats), _lib.ptr(_gn_scratch(dev, 4 * B * ((C * H * W + 4095) // 4096))), B, C, H * W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_groupnorm1_pair_fwd", x, *ws_, float(eps), int(act), y, stats,
+                    _gn_scratch(dev, 4 * B * ((C * H * W + 4095) // 4096)), B, C, H * W)
         ctx.save_for_backward(x, ws_[0], ws_[2], y, stats)
         ctx.act = int(act)
         return y
@@ -123,10 +118,8 @@ class _GroupNormPairFn(torch.autograd.Function):
         dy = _f32c_fast(dy)
         dx = torch.empty_like(x)
         g = torch.empty((4, C), dtype=torch.float32, device=dev)              # dgamma, dbeta, dgamma2, dbeta2
-        with torch.cuda.device(dev):
-            _lib.call("smvs_groupnorm1_pair_bwd", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(stats), ctx.act,
-                      _lib.ptr(dx), _lib.ptr(g[0]), _lib.ptr(g[1]), _lib.ptr(g[2]), _lib.ptr(g[3]), _lib.ptr(_gn_scratch(dev, 4 * B * C * ((H * W + 4095) // 4096))),
-                      B, C, H * W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_groupnorm1_pair_bwd", dy, x, y, w1, w2, stats, ctx.act, dx, g[0], g[1], g[2], g[3],
+                    _gn_scratch(dev, 4 * B * C * ((H * W + 4095) // 4096)), B, C, H * W)
         return dx, g[0], g[1], g[2], g[3], None, None
 
 
@@ -140,8 +133,7 @@ class _GruMulCatFn(torch.autograd.Function):
         B, Cx, H, W = x.shape
         Ch = h.shape[1]
         out = torch.empty((B, Cx + Ch, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_gru_mul_cat_fwd", _lib.ptr(x), _lib.ptr(r), _lib.ptr(h), _lib.ptr(out), B, Cx, Ch, H * W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_gru_mul_cat_fwd", x, r, h, out, B, Cx, Ch, H * W)
         ctx.save_for_backward(r, h)
         ctx.cx = Cx
         return out
@@ -153,9 +145,7 @@ class _GruMulCatFn(torch.autograd.Function):
         B, Ch, H, W = h.shape
         dcat = _f32c_fast(dcat)
         dr, dh = torch.empty_like(r), torch.empty_like(h)
-        with torch.cuda.device(h.device):
-            _lib.call("smvs_gru_mul_cat_bwd", _lib.ptr(dcat), _lib.ptr(r), _lib.ptr(h), _lib.ptr(dr), _lib.ptr(dh), B, ctx.cx, Ch, H * W,
-                      _lib.current_stream(h.device))
+        _lib.launch(h.device, "smvs_gru_mul_cat_bwd", dcat, r, h, dr, dh, B, ctx.cx, Ch, H * W)
         return dcat[:, :ctx.cx], dr, dh
 
 
@@ -167,8 +157,7 @@ class _GruBlendFn(torch.autograd.Function):
         dev = _lib.require_device(u, h, y)
         u, h, y = _f32c_fast(u), _f32c_fast(h), _f32c_fast(y)
         out = torch.empty_like(h)
-        with torch.cuda.device(dev):
-            _lib.call("smvs_gru_blend_fwd", _lib.ptr(u), _lib.ptr(h), _lib.ptr(y), _lib.ptr(out), h.numel(), _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_gru_blend_fwd", u, h, y, out, h.numel())
         ctx.save_for_backward(u, h, y)
         return out
 
@@ -178,9 +167,7 @@ class _GruBlendFn(torch.autograd.Function):
         u, h, y = ctx.saved_tensors
         dy = _f32c_fast(dy)
         du, dh, dc = torch.empty_like(u), torch.empty_like(h), torch.empty_like(y)
-        with torch.cuda.device(h.device):
-            _lib.call("smvs_gru_blend_bwd", _lib.ptr(dy), _lib.ptr(u), _lib.ptr(h), _lib.ptr(y), _lib.ptr(du), _lib.ptr(dh), _lib.ptr(dc), h.numel(),
-                      _lib.current_stream(h.device))
+        _lib.launch(h.device, "smvs_gru_blend_bwd", dy, u, h, y, du, dh, dc, h.numel())
         return du, dh, dc
 
 
@@ -307,11 +294,9 @@ class _WgradSink:
                         for t in e_:
                             if t is not None:
                                 t.record_stream(here)
-            with torch.cuda.device(dev):
-                _lib.call("smvs_conv3x3_wgrad_list", _lib.ptr_array([e[0] for e in ent]),
-                          _lib.ptr_array([e[1] for e in ent]) if win20 is not None else None, _lib.ptr_array([e[2] for e in ent]), len(ent),
-                          _lib.ptr(dw), _lib.ptr(buf[nw:]) if lay["sums"] else None, Bper, CA, CB, Cg, H, W, lay["stride"],
-                          _lib.current_stream(dev))
+            _lib.launch(dev, "smvs_conv3x3_wgrad_list", _lib.ptr_array([e[0] for e in ent]),
+                        _lib.ptr_array([e[1] for e in ent]) if win20 is not None else None, _lib.ptr_array([e[2] for e in ent]), len(ent),
+                        dw, buf[nw:] if lay["sums"] else None, Bper, CA, CB, Cg, H, W, lay["stride"])
             res = self.results[key] = (dw, buf[nw:] if lay["sums"] else None)
         return res
 
@@ -386,9 +371,7 @@ class _Conv3x3WgradFn(torch.autograd.Function):
             if buf is None or buf.device != xc.device:
                 buf = torch.zeros((nw + (Cg if sums else 0),), dtype=torch.float32, device=xc.device)    # one fill for both gradients
             dw = buf[:nw].view(weight.shape)
-            with torch.cuda.device(xc.device):
-                _lib.call("smvs_conv3x3_wgrad_strided", _lib.ptr(window), _lib.ptr(grid), _lib.ptr(dw), _lib.ptr(buf[nw:]) if sums else None,
-                          B, Cw, Cg, H, W, stride, _lib.current_stream(xc.device))
+            _lib.launch(xc.device, "smvs_conv3x3_wgrad_strided", window, grid, dw, buf[nw:] if sums else None, B, Cw, Cg, H, W, stride)
             if has_bias:
                 db = buf[nw:] if sums else dy.sum((0, 2, 3))
         return dx, dw, db, None, None
@@ -403,9 +386,7 @@ def _conv3d_wgrad(window, grid, weight_shape, stride, zeroed=None):
     dw = zeroed.view(weight_shape) if zeroed is not None and zeroed.device == dev else torch.zeros(weight_shape, dtype=torch.float32, device=dev)
     nws = _lib.load().smvs_conv3d_wgrad_workspace_floats(B, Cw, Cg, D, H, W)
     ws = torch.empty((max(nws, 1),), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("smvs_conv3d_wgrad", _lib.ptr(window), _lib.ptr(grid), _lib.ptr(dw), _lib.ptr(ws), nws, B, Cw, Cg, D, H, W, stride,
-                  _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_conv3d_wgrad", window, grid, dw, ws, nws, B, Cw, Cg, D, H, W, stride)
     return dw
 
 
@@ -450,8 +431,7 @@ def _conv3d_packed(weight, layout, cin, cout):
     if hit is not None and hit[0] == weight._version and hit[1] == _PARAM_EPOCH[0] and not hit[2].expired():
         return hit[3]
     packed = torch.empty((_lib.load().smvs_conv3d_packed_floats(cin, cout),), dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.call("smvs_conv3d_pack", _lib.ptr(weight), _lib.ptr(packed), cin, cout, layout, _lib.current_stream(weight.device))
+    _lib.launch(weight.device, "smvs_conv3d_pack", weight, packed, cin, cout, layout)
     if sum(1 for k in _CONV_PACK if k[3] == key[3]) > 256:          # per device (nn.DataParallel: ~120 entries per replica device);
         for k in [k for k in _CONV_PACK if k[3] == key[3]][:128]:     # the oldest half of THIS device's entries goes (dicts keep insertion order)
             del _CONV_PACK[k]
@@ -493,9 +473,8 @@ class _Conv3dNativeFn(torch.autograd.Function):
         dims = tuple(x.shape[2:])
         Cout = weight.shape[1] if kind == "t2" else weight.shape[0]
         out = torch.empty((B, Cout) + _conv3d_out_dims(kind, dims), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("smvs_conv3d_fwd", fk, _lib.ptr(x), _lib.ptr(_conv3d_packed(weight, flay, Cin, Cout)), None, _lib.ptr(out), B, Cin, Cout,
-                      dims[0], dims[1], dims[2], 0, _lib.current_stream(x.device))
+        _lib.launch(x.device, "smvs_conv3d_fwd", fk, x, _conv3d_packed(weight, flay, Cin, Cout), None, out, B, Cin, Cout,
+                    dims[0], dims[1], dims[2], 0)
         ctx.save_for_backward(x, weight)
         ctx.kind = kind
         arena = getattr(_TLS, "arena", None)
@@ -513,15 +492,14 @@ class _Conv3dNativeFn(torch.autograd.Function):
         Cout = dy.shape[1]
         dev = x.device
         dx = dw = None
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _lib.call("smvs_conv3d_fwd", bk, _lib.ptr(dy), _lib.ptr(_conv3d_packed(weight, blay, Cout, Cin)), None, _lib.ptr(dx), B, Cout, Cin,
-                          dy.shape[2], dy.shape[3], dy.shape[4], 0, _lib.current_stream(dev))
-            if ctx.needs_input_grad[1]:
-                window, grid = (dy, x) if kind == "t2" else (x, dy)         # the tensor read through the taps / the one on the output grid
-                buf, ctx.zeroed = ctx.zeroed, None                          # (a second backward through the same graph gets fresh memory)
-                dw = _conv3d_wgrad(window, grid, weight.shape, stride, buf)
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _lib.launch(dev, "smvs_conv3d_fwd", bk, dy, _conv3d_packed(weight, blay, Cout, Cin), None, dx, B, Cout, Cin,
+                        dy.shape[2], dy.shape[3], dy.shape[4], 0)
+        if ctx.needs_input_grad[1]:
+            window, grid = (dy, x) if kind == "t2" else (x, dy)         # the tensor read through the taps / the one on the output grid
+            buf, ctx.zeroed = ctx.zeroed, None                          # (a second backward through the same graph gets fresh memory)
+            dw = _conv3d_wgrad(window, grid, weight.shape, stride, buf)
         return dx, dw, None
 
 
@@ -570,12 +548,9 @@ class _BatchNormReluFn(torch.autograd.Function):
         zb = arena.take(4 * C) if zf is not None else None                                          # ... and the backward's
         ws = zf.view(torch.float64) if zf is not None else torch.empty((2 * C,), dtype=torch.float64, device=x.device)
         track = bn.track_running_stats and bn.running_mean is not None
-        with torch.cuda.device(x.device):
-            _lib.call("smvs_batchnorm_train_fwd", _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(bn.running_mean) if track else None,
-                      _lib.ptr(bn.running_var) if track else None,
-                      _lib.ptr(bn.num_batches_tracked) if track and bn.num_batches_tracked is not None and bn.num_batches_tracked.is_cuda else None,
-                      float(bn.momentum), float(bn.eps), (1 if relu else 0) | (2 if zf is not None else 0),
-                      _lib.ptr(y), _lib.ptr(saved), _lib.ptr(ws), B, C, N, _lib.current_stream(x.device))
+        _lib.launch(x.device, "smvs_batchnorm_train_fwd", x, gamma, beta, bn.running_mean if track else None, bn.running_var if track else None,
+                    bn.num_batches_tracked if track and bn.num_batches_tracked is not None and bn.num_batches_tracked.is_cuda else None,
+                    float(bn.momentum), float(bn.eps), (1 if relu else 0) | (2 if zf is not None else 0), y, saved, ws, B, C, N)
         ctx.save_for_backward(x, gamma, beta, saved)
         ctx.relu = bool(relu)
         ctx.zeroed = zb
@@ -592,10 +567,8 @@ class _BatchNormReluFn(torch.autograd.Function):
         dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
         zb, ctx.zeroed = ctx.zeroed, None                                   # (a second backward through the same graph clears its own)
         ws = zb.view(torch.float64) if zb is not None else torch.empty((2 * C,), dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("smvs_batchnorm_train_bwd", _lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(saved),
-                      (1 if ctx.relu else 0) | (2 if zb is not None else 0),
-                      _lib.ptr(dx), _lib.ptr(dgb[0]), _lib.ptr(dgb[1]), _lib.ptr(ws), B, C, N, _lib.current_stream(x.device))
+        _lib.launch(x.device, "smvs_batchnorm_train_bwd", dy, x, gamma, beta, saved, (1 if ctx.relu else 0) | (2 if zb is not None else 0),
+                    dx, dgb[0], dgb[1], ws, B, C, N)
         return dx, dgb[0], dgb[1], None, None
 
 
@@ -622,8 +595,7 @@ def _conv_packed(weight, layout, cin, cout):
     if hit is not None and hit[0] == weight._version and hit[1] == _PARAM_EPOCH[0] and not hit[2].expired():
         return hit[3]
     packed = torch.empty((_lib.load().smvs_conv3x3_packed_floats(cin, cout),), dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _lib.call("smvs_conv3x3_pack", _lib.ptr(weight), _lib.ptr(packed), cin, cout, layout, _lib.current_stream(weight.device))
+    _lib.launch(weight.device, "smvs_conv3x3_pack", weight, packed, cin, cout, layout)
     if sum(1 for k in _CONV_PACK if k[3] == key[3]) > 256:          # per device (nn.DataParallel: ~120 entries per replica device);
         for k in [k for k in _CONV_PACK if k[3] == key[3]][:128]:     # the oldest half of THIS device's entries goes (dicts keep insertion order)
             del _CONV_PACK[k]
@@ -657,10 +629,7 @@ class _Conv3x3NativeFn(torch.autograd.Function):
         out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=xa.device)
         packed = _conv_packed(weight, flay, CA + CB, Cout)
         fused_bias = bias if kind != "t2" else None              # (the stride-2 transposed layers of the regulariser have no bias)
-        with torch.cuda.device(xa.device):
-            _lib.call("smvs_conv3x3_fwd", fk, _lib.ptr(xa), CA, _lib.ptr(xb) if xb is not None else None, CB, _lib.ptr(packed),
-                      _lib.ptr(fused_bias) if fused_bias is not None else None, None, _lib.ptr(out), B, Cout, H, W, 1 if relu else 0,
-                      _lib.current_stream(xa.device))
+        _lib.launch(xa.device, "smvs_conv3x3_fwd", fk, xa, CA, xb, CB, packed, fused_bias, None, out, B, Cout, H, W, 1 if relu else 0)
         ctx.save_for_backward(xa, xb, weight, out if relu else None)
         ctx.kind, ctx.relu, ctx.has_bias = kind, bool(relu), bias is not None
         ctx.sink = getattr(_TLS, "sink", None)
@@ -685,33 +654,31 @@ class _Conv3x3NativeFn(torch.autograd.Function):
         Cout = dy.shape[1]
         dev = xa.device
         dxa = dxb = dw = db = None
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0] or (xb is not None and ctx.needs_input_grad[1]):
-                dx = torch.empty((B, CA + CB, H, W), dtype=torch.float32, device=dev)
-                _lib.call("smvs_conv3x3_fwd", bk, _lib.ptr(dy), Cout, None, 0, _lib.ptr(_conv_packed(weight, blay, Cout, CA + CB)), None, None,
-                          _lib.ptr(dx), B, CA + CB, dy.shape[2], dy.shape[3], 0, _lib.current_stream(dev))
-                dxa = dx[:, :CA] if ctx.needs_input_grad[0] else None
-                dxb = dx[:, CA:] if xb is not None and ctx.needs_input_grad[1] else None
-            if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-                sums = ctx.has_bias and not transposed
-                # the tensor read through the taps / the one on the output grid (they swap for the transposed layers)
-                window, win2, grid = (dy, None, xa) if transposed else (xa, xb, dy)
-                if ctx.sink is not None:                         # deferred: one launch per layer after the last plane
-                    ctx.sink.add(weight, ctx.bias, window, win2, grid, stride)
-                    dw = _placeholder(weight)
-                    db = (_placeholder(ctx.bias) if sums else dy.sum((0, 2, 3))) if ctx.has_bias else None
-                else:
-                    nw = weight.numel()
-                    buf, ctx.zeroed = ctx.zeroed, None           # (a second backward through the same graph gets fresh memory)
-                    if buf is None or buf.device != dev:
-                        buf = torch.zeros((nw + (Cout if sums else 0),), dtype=torch.float32, device=dev)
-                    dw = buf[:nw].view(weight.shape)
-                    _lib.call("smvs_conv3x3_wgrad_list", _lib.ptr_array([window]), _lib.ptr_array([win2]) if win2 is not None else None,
-                              _lib.ptr_array([grid]), 1, _lib.ptr(dw), _lib.ptr(buf[nw:]) if sums else None, B, window.shape[1],
-                              win2.shape[1] if win2 is not None else 0, grid.shape[1], grid.shape[2], grid.shape[3], stride,
-                              _lib.current_stream(dev))
-                    if ctx.has_bias:
-                        db = buf[nw:] if sums else dy.sum((0, 2, 3))
+        if ctx.needs_input_grad[0] or (xb is not None and ctx.needs_input_grad[1]):
+            dx = torch.empty((B, CA + CB, H, W), dtype=torch.float32, device=dev)
+            _lib.launch(dev, "smvs_conv3x3_fwd", bk, dy, Cout, None, 0, _conv_packed(weight, blay, Cout, CA + CB), None, None, dx,
+                        B, CA + CB, dy.shape[2], dy.shape[3], 0)
+            dxa = dx[:, :CA] if ctx.needs_input_grad[0] else None
+            dxb = dx[:, CA:] if xb is not None and ctx.needs_input_grad[1] else None
+        if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
+            sums = ctx.has_bias and not transposed
+            # the tensor read through the taps / the one on the output grid (they swap for the transposed layers)
+            window, win2, grid = (dy, None, xa) if transposed else (xa, xb, dy)
+            if ctx.sink is not None:                         # deferred: one launch per layer after the last plane
+                ctx.sink.add(weight, ctx.bias, window, win2, grid, stride)
+                dw = _placeholder(weight)
+                db = (_placeholder(ctx.bias) if sums else dy.sum((0, 2, 3))) if ctx.has_bias else None
+            else:
+                nw = weight.numel()
+                buf, ctx.zeroed = ctx.zeroed, None           # (a second backward through the same graph gets fresh memory)
+                if buf is None or buf.device != dev:
+                    buf = torch.zeros((nw + (Cout if sums else 0),), dtype=torch.float32, device=dev)
+                dw = buf[:nw].view(weight.shape)
+                _lib.launch(dev, "smvs_conv3x3_wgrad_list", _lib.ptr_array([window]), _lib.ptr_array([win2]) if win2 is not None else None,
+                            _lib.ptr_array([grid]), 1, dw, buf[nw:] if sums else None, B, window.shape[1],
+                            win2.shape[1] if win2 is not None else 0, grid.shape[1], grid.shape[2], grid.shape[3], stride)
+                if ctx.has_bias:
+                    db = buf[nw:] if sums else dy.sum((0, 2, 3))
         return dxa, dxb, dw, db, None, None
 
 
@@ -769,9 +736,9 @@ def _wgrad_now_or_later(sink, weight, bias, window, win2, grid, stride):
     Cg = grid.shape[1]
     buf = torch.zeros((nw + (Cg if bias is not None else 0),), dtype=torch.float32, device=dev)
     dw = buf[:nw].view(weight.shape)
-    _lib.call("smvs_conv3x3_wgrad_list", _lib.ptr_array([window]), _lib.ptr_array([win2]) if win2 is not None else None, _lib.ptr_array([grid]), 1,
-              _lib.ptr(dw), _lib.ptr(buf[nw:]) if bias is not None else None, window.shape[0], window.shape[1],
-              win2.shape[1] if win2 is not None else 0, Cg, grid.shape[2], grid.shape[3], stride, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_conv3x3_wgrad_list", _lib.ptr_array([window]), _lib.ptr_array([win2]) if win2 is not None else None,
+                _lib.ptr_array([grid]), 1, dw, buf[nw:] if bias is not None else None, window.shape[0], window.shape[1],
+                win2.shape[1] if win2 is not None else 0, Cg, grid.shape[2], grid.shape[3], stride)
     return dw, (buf[nw:] if bias is not None else None)
 
 
@@ -790,23 +757,19 @@ class _ConvGRUCellFn(torch.autograd.Function):
         B, Cx, H, W = x.shape
         C = h.shape[1]
         HW = H * W
-        st = _lib.current_stream(dev)
         rw, rb, uw, ub, nw_, nb_ = [_f32c_fast(t.detach()) for t in (rw, rb, uw, ub, nw_, nb_)]
         e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         gates, ru, rh, craw, cand, out = e(B, 2 * C, H, W), e(B, 2 * C, H, W), e(B, C, H, W), e(B, C, H, W), e(B, C, H, W), e(B, C, H, W)
         stats_g, stats_o = e(2 * B, 2), e(B, 2)
         nblk = (C * HW + 4095) // 4096
-        with torch.cuda.device(dev):
-            _lib.call("smvs_conv3x3_fwd", 0, _lib.ptr(x), Cx, _lib.ptr(h), C, _lib.ptr(_conv_packed(gw, 0, Cx + C, 2 * C)), _lib.ptr(gb), None,
-                      _lib.ptr(gates), B, 2 * C, H, W, 0, st)
-            # (round 6: r * h leaves the gate norms' apply pass and the candidate convolution reads (x, r*h) as two tensors -- no cat launch;
-            # the blend leaves the output norm's apply pass -- no blend launch)
-            _lib.call("smvs_groupnorm1_pair_fwd_mul", _lib.ptr(gates), _lib.ptr(rw), _lib.ptr(rb), _lib.ptr(uw), _lib.ptr(ub), float(eps), 1, _lib.ptr(ru),
-                      _lib.ptr(stats_g), _lib.ptr(_gn_scratch(dev, 4 * B * nblk)), _lib.ptr(h), _lib.ptr(rh), B, C, HW, st)
-            _lib.call("smvs_conv3x3_fwd", 0, _lib.ptr(x), Cx, _lib.ptr(rh), C, _lib.ptr(_conv_packed(ow, 0, Cx + C, C)), _lib.ptr(ob), None,
-                      _lib.ptr(craw), B, C, H, W, 0, st)
-            _lib.call("smvs_groupnorm1_fwd_blend", _lib.ptr(craw), C * HW, _lib.ptr(nw_), _lib.ptr(nb_), float(eps), 2, _lib.ptr(cand), _lib.ptr(stats_o),
-                      _lib.ptr(_gn_scratch(dev, 2 * B * nblk)), _lib.ptr(ru[:, C:]), 2 * C * HW, _lib.ptr(h), _lib.ptr(out), B, C, HW, st)
+        _lib.launch(dev, "smvs_conv3x3_fwd", 0, x, Cx, h, C, _conv_packed(gw, 0, Cx + C, 2 * C), gb, None, gates, B, 2 * C, H, W, 0)
+        # (round 6: r * h leaves the gate norms' apply pass and the candidate convolution reads (x, r*h) as two tensors -- no cat launch;
+        # the blend leaves the output norm's apply pass -- no blend launch)
+        _lib.launch(dev, "smvs_groupnorm1_pair_fwd_mul", gates, rw, rb, uw, ub, float(eps), 1, ru, stats_g, _gn_scratch(dev, 4 * B * nblk),
+                    h, rh, B, C, HW)
+        _lib.launch(dev, "smvs_conv3x3_fwd", 0, x, Cx, rh, C, _conv_packed(ow, 0, Cx + C, C), ob, None, craw, B, C, H, W, 0)
+        _lib.launch(dev, "smvs_groupnorm1_fwd_blend", craw, C * HW, nw_, nb_, float(eps), 2, cand, stats_o, _gn_scratch(dev, 2 * B * nblk),
+                    ru[:, C:], 2 * C * HW, h, out, B, C, HW)
         ctx.save_for_backward(x, h, gw, gb, ow, ob, rw, uw, nw_, gates, ru, rh, craw, cand, stats_g, stats_o)
         ctx.sink = getattr(_TLS, "sink", None)
         return out
@@ -819,26 +782,20 @@ class _ConvGRUCellFn(torch.autograd.Function):
         B, Cx, H, W = x.shape
         C = h.shape[1]
         HW = H * W
-        st = _lib.current_stream(dev)
         dnew = _f32c_fast(dnew)
         e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         dru, dh_b, dcand, dcraw, dxc, dgates = e(B, 2 * C, H, W), e(B, C, H, W), e(B, C, H, W), e(B, C, H, W), e(B, Cx + C, H, W), e(B, 2 * C, H, W)
         g4, dn = e(4, C), e(2, C)
         r, u = ru[:, :C], ru[:, C:]
         nseg = (HW + 4095) // 4096
-        with torch.cuda.device(dev):
-            _lib.call("smvs_gru_blend_bwd", _lib.ptr(dnew), _lib.ptr(u), _lib.ptr(h), _lib.ptr(cand), _lib.ptr(dru[:, C:]), _lib.ptr(dh_b), _lib.ptr(dcand),
-                      h.numel(), st)
-            _lib.call("smvs_groupnorm1_bwd", _lib.ptr(dcand), _lib.ptr(craw), C * HW, _lib.ptr(cand), _lib.ptr(nw_), _lib.ptr(stats_o), 2, _lib.ptr(dcraw),
-                      C * HW, _lib.ptr(dn[0]), _lib.ptr(dn[1]), _lib.ptr(_gn_scratch(dev, 2 * B * C * nseg)), B, C, HW, st)
-            _lib.call("smvs_conv3x3_fwd", 0, _lib.ptr(dcraw), C, None, 0, _lib.ptr(_conv_packed(ow, 2, C, Cx + C)), None, None, _lib.ptr(dxc),
-                      B, Cx + C, H, W, 0, st)
-            dow, dob = _wgrad_now_or_later(ctx.sink, ow, ob, x, rh, dcraw, 1)
-            _lib.call("smvs_gru_mul_cat_bwd_acc", _lib.ptr(dxc), _lib.ptr(r), _lib.ptr(h), _lib.ptr(dh_b), _lib.ptr(dru), B, Cx, C, HW, st)
-            _lib.call("smvs_groupnorm1_pair_bwd", _lib.ptr(dru), _lib.ptr(gates), _lib.ptr(ru), _lib.ptr(rw), _lib.ptr(uw), _lib.ptr(stats_g), 1,
-                      _lib.ptr(dgates), _lib.ptr(g4[0]), _lib.ptr(g4[1]), _lib.ptr(g4[2]), _lib.ptr(g4[3]), _lib.ptr(_gn_scratch(dev, 4 * B * C * nseg)),
-                      B, C, HW, st)
-            _lib.call("smvs_conv3x3_fwd", 0, _lib.ptr(dgates), 2 * C, None, 0, _lib.ptr(_conv_packed(gw, 2, 2 * C, Cx + C)), None, _lib.ptr(dxc),
-                      _lib.ptr(dxc), B, Cx + C, H, W, 0, st)
-            dgw, dgb = _wgrad_now_or_later(ctx.sink, gw, gb, x, h, dgates, 1)
+        _lib.launch(dev, "smvs_gru_blend_bwd", dnew, u, h, cand, dru[:, C:], dh_b, dcand, h.numel())
+        _lib.launch(dev, "smvs_groupnorm1_bwd", dcand, craw, C * HW, cand, nw_, stats_o, 2, dcraw, C * HW, dn[0], dn[1],
+                    _gn_scratch(dev, 2 * B * C * nseg), B, C, HW)
+        _lib.launch(dev, "smvs_conv3x3_fwd", 0, dcraw, C, None, 0, _conv_packed(ow, 2, C, Cx + C), None, None, dxc, B, Cx + C, H, W, 0)
+        dow, dob = _wgrad_now_or_later(ctx.sink, ow, ob, x, rh, dcraw, 1)
+        _lib.launch(dev, "smvs_gru_mul_cat_bwd_acc", dxc, r, h, dh_b, dru, B, Cx, C, HW)
+        _lib.launch(dev, "smvs_groupnorm1_pair_bwd", dru, gates, ru, rw, uw, stats_g, 1, dgates, g4[0], g4[1], g4[2], g4[3],
+                    _gn_scratch(dev, 4 * B * C * nseg), B, C, HW)
+        _lib.launch(dev, "smvs_conv3x3_fwd", 0, dgates, 2 * C, None, 0, _conv_packed(gw, 2, 2 * C, Cx + C), None, dxc, dxc, B, Cx + C, H, W, 0)
+        dgw, dgb = _wgrad_now_or_later(ctx.sink, gw, gb, x, h, dgates, 1)
         return dxc[:, :Cx], dxc[:, Cx:], dgw, dgb, g4[0], g4[1], g4[2], g4[3], dow, dob, dn[0], dn[1], None

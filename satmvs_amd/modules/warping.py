@@ -18,6 +18,8 @@ reference too (warping.py:322).
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -92,14 +94,8 @@ class _WarpFn(torch.autograd.Function):
         B, C, H, W = fea.shape
         D = depth.shape[1]
         out = torch.empty((B, C, D, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            if geo == 0:
-                _lib.call("smvs_rpc_warp_fwd", _lib.ptr(fea), _lib.ptr(src_geo), _lib.ptr(ref_geo), _lib.ptr(depth),
-                          is4d, _lib.ptr(out), B, C, D, H, W, st)
-            else:
-                _lib.call("smvs_homo_warp_fwd", _lib.ptr(fea), _lib.ptr(src_geo), _lib.ptr(depth), is4d,
-                          _lib.ptr(out), B, C, D, H, W, st)
+        name, geo_args = ("smvs_rpc_warp_fwd", (src_geo, ref_geo)) if geo == 0 else ("smvs_homo_warp_fwd", (src_geo,))
+        _lib.launch(dev, name, fea, *geo_args, depth, is4d, out, B, C, D, H, W)
         ctx.save_for_backward(src_geo, ref_geo if ref_geo is not None else src_geo, depth)
         ctx.meta = (is4d, geo, (B, C, D, H, W))
         return out
@@ -111,14 +107,8 @@ class _WarpFn(torch.autograd.Function):
         g = _f32c(grad_out)
         dev = g.device
         grad_src = torch.zeros((B, C, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            if geo == 0:
-                _lib.call("smvs_rpc_warp_bwd", _lib.ptr(g), _lib.ptr(src_geo), _lib.ptr(ref_geo), _lib.ptr(depth),
-                          is4d, _lib.ptr(grad_src), B, C, D, H, W, st)
-            else:
-                _lib.call("smvs_homo_warp_bwd", _lib.ptr(g), _lib.ptr(src_geo), _lib.ptr(depth), is4d,
-                          _lib.ptr(grad_src), B, C, D, H, W, st)
+        name, geo_args = ("smvs_rpc_warp_bwd", (src_geo, ref_geo)) if geo == 0 else ("smvs_homo_warp_bwd", (src_geo,))
+        _lib.launch(dev, name, g, *geo_args, depth, is4d, grad_src, B, C, D, H, W)
         return grad_src, None, None, None, None, None
 
 
@@ -128,8 +118,7 @@ def _compose_homography(src_proj, ref_proj):
     s, r = _f64c(src_proj), _f64c(ref_proj)
     n = s.numel() // 16
     out = torch.empty_like(s)
-    with torch.cuda.device(dev):
-        _lib.call("smvs_homo_compose", _lib.ptr(s), _lib.ptr(r), _lib.ptr(out), n, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_homo_compose", s, r, out, n)
     return out
 
 
@@ -162,11 +151,8 @@ def _project(a, b, h, rpc, direction):
     a2, b2, h2 = (_f64c(t).reshape(B, -1) for t in (a, b, h))
     o0, o1 = torch.empty_like(a2), torch.empty_like(a2)
     n = a2.shape[1]
-    with torch.cuda.device(dev):
-        st = _lib.current_stream(dev)
-        for i in range(B):
-            _lib.call("smvs_rpc_project", _lib.ptr(rpc[i]), _lib.ptr(a2[i]), _lib.ptr(b2[i]), _lib.ptr(h2[i]),
-                      _lib.ptr(o0[i]), _lib.ptr(o1[i]), n, direction, st)
+    for i in range(B):
+        _lib.launch(dev, "smvs_rpc_project", rpc[i], a2[i], b2[i], h2[i], o0[i], o1[i], n, direction)
     return o0.reshape(shape), o1.reshape(shape)
 
 
@@ -197,9 +183,7 @@ def plane_coefficients(geo, depth, is4d, n_src, H, W, d_begin=0, d_end=None):
     d_end = D if d_end is None else d_end
     nbytes = _lib.load().smvs_rpc_plane_coef_bytes(B, n_src, D)
     pc = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_plane_coef", _lib.ptr(geo), _lib.ptr(depth), is4d, _lib.ptr(pc), B, n_src, D, H, W,
-                  d_begin, d_end, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_rpc_plane_coef", geo, depth, is4d, pc, B, n_src, D, H, W, d_begin, d_end)
     return pc
 
 
@@ -221,20 +205,16 @@ class _CostVolFn(torch.autograd.Function):
                 raise ValueError("source feature %s != reference feature %s" % (tuple(s.shape), tuple(ref.shape)))
         nd = d_end - d_begin
         out = torch.empty((B, C, nd, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = _lib.current_stream(dev)
-            if geo_kind == 0 and plane_constant and B * nd * H * W >= _FOLD_MIN_VOXELS:
-                # plane-constant heights (stage 1 of every cascade) collapse the source cubics to bivariate ones: fold them for
-                # the planes of this launch.  The kernel runs its geometry from the folded records and checks its own heights
-                # against them afterwards, wave by wave -- a wave whose heights differ redoes it with the trivariate chain,
-                # which is why heights that vary inside a plane (stages 2 / 3) are not sent this way
-                pc = plane_coefficients(geo, depth, is4d, len(srcs), H, W, d_begin, d_end)
-                _lib.call("smvs_rpc_costvol_fwd_pc", _lib.ptr(ref), _lib.ptr_array(srcs), len(srcs), _lib.ptr(geo), _lib.ptr(depth),
-                          is4d | _lib.call_arith_bits(), _lib.ptr(pc), _lib.ptr(out), B, C, D, H, W, d_begin, d_end, nd, 0, st)
-            else:
-                name = "smvs_rpc_costvol_fwd" if geo_kind == 0 else "smvs_homo_costvol_fwd"
-                _lib.call(name, _lib.ptr(ref), _lib.ptr_array(srcs), len(srcs), _lib.ptr(geo), _lib.ptr(depth), is4d | _lib.call_arith_bits(),
-                          _lib.ptr(out), B, C, D, H, W, d_begin, d_end, nd, 0, st)
+        if geo_kind == 0 and plane_constant and B * nd * H * W >= _FOLD_MIN_VOXELS:
+            # plane-constant heights (stage 1 of every cascade) collapse the source cubics to bivariate ones: fold them for
+            # the planes of this launch.  The kernel runs its geometry from the folded records and checks its own heights
+            # against them afterwards, wave by wave -- a wave whose heights differ redoes it with the trivariate chain,
+            # which is why heights that vary inside a plane (stages 2 / 3) are not sent this way
+            name, geo_args = "smvs_rpc_costvol_fwd_pc", (plane_coefficients(geo, depth, is4d, len(srcs), H, W, d_begin, d_end),)
+        else:
+            name, geo_args = ("smvs_rpc_costvol_fwd" if geo_kind == 0 else "smvs_homo_costvol_fwd"), ()
+        _lib.launch(dev, name, ref, _lib.ptr_array(srcs), len(srcs), geo, depth, is4d | _lib.call_arith_bits(), *geo_args, out,
+                    B, C, D, H, W, d_begin, d_end, nd, 0)
         ctx.save_for_backward(geo, depth, ref, *srcs)
         ctx.meta = (geo_kind, is4d, d_begin, d_end, (B, C, D, H, W))
         return out
@@ -249,10 +229,8 @@ class _CostVolFn(torch.autograd.Function):
         dev = g.device
         g_ref = torch.zeros_like(ref)
         g_srcs = [torch.zeros_like(s) for s in srcs]
-        with torch.cuda.device(dev):
-            _lib.call("smvs_costvol_bwd", geo_kind, _lib.ptr(g), _lib.ptr(ref), _lib.ptr_array(srcs), len(srcs),
-                      _lib.ptr(geo), _lib.ptr(depth), is4d, _lib.ptr(g_ref), _lib.ptr_array(g_srcs),
-                      B, C, D, H, W, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_costvol_bwd", geo_kind, g, ref, _lib.ptr_array(srcs), len(srcs), geo, depth, is4d, g_ref,
+                    _lib.ptr_array(g_srcs), B, C, D, H, W)
         return (None, None, None, None, None, None, None, g_ref, *g_srcs)
 
 
@@ -314,7 +292,6 @@ def variance_cost_volume(features, proj_matrices, depth_values, geo_model="rpc",
 
 def _costvol_generated(features, proj_matrices, gen, geo_model, use_qc, d_begin, d_end):
     """variance_cost_volume with the hypotheses evaluated inside the kernel (smvs_*_costvol_fwd_gen); no autograd."""
-    import ctypes
     ref = _f32c(features[0])
     srcs = [_f32c(s) for s in features[1:]]
     B, C, H, W = ref.shape
@@ -327,8 +304,6 @@ def _costvol_generated(features, proj_matrices, gen, geo_model, use_qc, d_begin,
     nd = d_end - d_begin
     out = torch.empty((B, C, nd, H, W), dtype=torch.float32, device=dev)
     gs = gen.c_struct()
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_costvol_fwd_gen" if kind == 0 else "smvs_homo_costvol_fwd_gen", _lib.ptr(ref),
-                  _lib.ptr_array(srcs), len(srcs), _lib.ptr(geo), ctypes.addressof(gs), _lib.ptr(out),
-                  B, C, D, H, W, d_begin, d_end, nd, 0, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_rpc_costvol_fwd_gen" if kind == 0 else "smvs_homo_costvol_fwd_gen", ref, _lib.ptr_array(srcs), len(srcs),
+                geo, ctypes.addressof(gs), out, B, C, D, H, W, d_begin, d_end, nd, 0)
     return out

@@ -34,10 +34,7 @@ def _pair(depth_ref, intrinsics_ref, extrinsics_ref, depth_src, intrinsics_src, 
     dep, xs, ys = (torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(3))
     xb = torch.empty_like(xs) if want_back else None
     yb = torch.empty_like(xs) if want_back else None
-    with torch.cuda.device(dev):
-        _lib.call("smvs_pinhole_geo_consistency", _lib.ptr(dr), _lib.ptr(ds), _lib.ptr(mats), H, W, Hs, Ws, float(p_thre), float(relative_d_thre),
-                  _lib.ptr(mask), _lib.ptr(dep), _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(xb) if want_back else None,
-                  _lib.ptr(yb) if want_back else None, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_pinhole_geo_consistency", dr, ds, mats, H, W, Hs, Ws, float(p_thre), float(relative_d_thre), mask, dep, xs, ys, xb, yb)
     return mask, dep, xs, ys, xb, yb
 
 

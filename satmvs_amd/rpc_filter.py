@@ -43,10 +43,7 @@ def _pair(depth_ref, rpc_ref, depth_src, rpc_src, p_ratio, d_ratio, want_back):
     ys = torch.empty_like(xs)
     xb = torch.empty_like(xs) if want_back else None
     yb = torch.empty_like(xs) if want_back else None
-    with torch.cuda.device(dev):
-        _lib.call("smvs_rpc_geo_consistency", _lib.ptr(dr), _lib.ptr(rr), _lib.ptr(ds), _lib.ptr(rs), H, W, Hs, Ws,
-                  float(p_ratio), float(d_ratio), _lib.ptr(mask), _lib.ptr(dep), _lib.ptr(xs), _lib.ptr(ys),
-                  _lib.ptr(xb) if want_back else None, _lib.ptr(yb) if want_back else None, _lib.current_stream(dev))
+    _lib.launch(dev, "smvs_rpc_geo_consistency", dr, rr, ds, rs, H, W, Hs, Ws, float(p_ratio), float(d_ratio), mask, dep, xs, ys, xb, yb)
     return mask, dep, xs, ys, xb, yb
 
 

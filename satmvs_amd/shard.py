@@ -62,8 +62,7 @@ def allreduce_regression_state(state, group=None, force=False):
     mine = flat[rank * chunk:(rank + 1) * chunk]
     if flat.is_cuda:
         from . import _lib
-        with torch.cuda.device(flat.device):
-            _lib.call("smvs_regress_fold", _lib.ptr(recv), _lib.ptr(mine), world, chunk, rank * chunk, row_len, _lib.current_stream(flat.device))
+        _lib.launch(flat.device, "smvs_regress_fold", recv, mine, world, chunk, rank * chunk, row_len)
     else:
         idx = torch.arange(rank * chunk, (rank + 1) * chunk)
         is_max = (idx // row_len) >= 2

@@ -7,7 +7,6 @@ Same classes, constructor arguments and methods as the reference's tools/Transve
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
@@ -67,10 +66,7 @@ class TransverseMercator:
         flat = t.to(device=dev, dtype=torch.float64).reshape(-1, 2)
         a, b = flat[:, 0].contiguous(), flat[:, 1].contiguous()
         o0, o1 = torch.empty_like(a), torch.empty_like(a)
-        tm7 = self.tm7()
-        with torch.cuda.device(dev):
-            _lib.call("smvs_tm_project", tm7.ctypes.data_as(ctypes.c_void_p), _lib.ptr(a), _lib.ptr(b),
-                      _lib.ptr(o0), _lib.ptr(o1), a.numel(), direction, _lib.current_stream(dev))
+        _lib.launch(dev, "smvs_tm_project", self.tm7(), a, b, o0, o1, a.numel(), direction)
         out = torch.stack((o0, o1), dim=-1).reshape(t.shape)
         return out.cpu().numpy() if is_numpy else out
 

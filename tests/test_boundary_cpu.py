@@ -445,3 +445,70 @@ def test_arith_scope_is_thread_local_and_matches_the_header():
     assert _lib.call_arith_bits() == 0 and seen["other"] == 0
     with pytest.raises(ValueError):
         _lib.arith_scope("fast")
+
+
+# ---- the launcher ----------------------------------------------------------------------------------------
+def test_marshal_maps_tensors_and_arrays_and_passes_the_rest_through():
+    """_lib.marshal: a tensor goes as its data pointer (a view's storage offset included), a numpy array as its host pointer,
+    and None, numbers, pointers, ptr_array results and addressof integers stay the very objects they were, in order."""
+    from satmvs_amd import _lib
+    from satmvs_amd.modules.depth_range import _HeightGenStruct
+    t = torch.arange(24, dtype=torch.float32).reshape(4, 6)
+    view = t[1:, 2:]
+    a = np.arange(7, dtype=np.float64)
+    vp = C.c_void_p(4096)
+    arr = _lib.ptr_array([t, view])
+    gs = _HeightGenStruct(16, 8, 16, 32, 64, 6, 5.0)
+    addr = C.addressof(gs)
+    f = 2.5
+    args = [t, view, a, None, 7, f, vp, arr, addr]
+    out = _lib.marshal(args)
+    assert isinstance(out, list) and len(out) == len(args)
+    assert view.storage_offset() == 8 and view.data_ptr() == t.data_ptr() + 8 * 4
+    for got, want in ((out[0], t.data_ptr()), (out[1], view.data_ptr()), (out[2], a.ctypes.data)):
+        assert type(got) is C.c_void_p and got.value == want
+    assert out[3] is None and out[4] is args[4] and out[5] is f and out[6] is vp and out[7] is arr and out[8] is addr
+    assert [arr[0], arr[1]] == [t.data_ptr(), view.data_ptr()]
+    # order: the reversed list gives the reversed result
+    back = _lib.marshal(args[::-1])
+    assert all(x is y for x, y in zip(back[:6], args[:2:-1])) and [x.value for x in back[6:]] == [x.value for x in out[2::-1]]
+    assert _lib.marshal(()) == [] and args[0] is t                          # pure: nothing to marshal, the input untouched
+
+
+def test_marshalled_arguments_satisfy_the_ctypes_signatures(lib):
+    """call(name, *marshal([...]), stream) with CPU tensors, a numpy array and plain numbers reaches the entry's own argument checks."""
+    from satmvs_amd import _lib
+    rpc = torch.zeros(170, dtype=torch.float64)
+    pts = [torch.zeros(4, dtype=torch.float64) for _ in range(4)]
+    out = np.zeros(4, dtype=np.float64)
+    with pytest.raises(_lib.SatMVSNativeError, match="dir must be"):
+        _lib.call("smvs_rpc_project", *_lib.marshal([rpc, *pts, out, 4, 7]), None)
+
+
+def test_the_package_makes_its_native_calls_through_launch():
+    """No `_lib.call(` under satmvs_amd/ outside _lib.py: every site goes through _lib.launch (device guard, marshalling and the
+    current stream in one place).  A site that must pass another stream would be listed here with its reason; there is none."""
+    import ast
+    allowed = {}                                                            # relative path -> number of deliberate _lib.call sites
+    pkg = os.path.join(ROOT, "satmvs_amd")
+    found = {}
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            path = os.path.join(dirpath, f)
+            rel = os.path.relpath(path, pkg)
+            if not f.endswith(".py") or rel == "_lib.py":
+                continue
+            n = 0
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                # `<anything>.call` (so `_lib.call(...)`, an alias of the module, a reference handed on) ...
+                if isinstance(node, ast.Attribute) and node.attr == "call":
+                    n += 1
+                # ... and `from ._lib import call [as x]` / `from . import _lib as x`, which would hide it from the line above
+                if isinstance(node, ast.ImportFrom):
+                    from_lib = (node.module or "").split(".")[-1] == "_lib"
+                    n += sum(1 for a in node.names if (from_lib and a.name in ("call", "*")) or (a.name == "_lib" and a.asname not in (None, "_lib")))
+                if isinstance(node, ast.Import):
+                    n += sum(1 for a in node.names if a.name.split(".")[-1] == "_lib" and a.asname not in (None, "_lib"))
+            if n:
+                found[rel] = n
+    assert found == allowed

@@ -767,3 +767,35 @@ def test_homo_compose_singular_reference_returns(dev):
     assert not np.isfinite(got[1]).all() and not np.isfinite(got[3]).all()
     for i in (0, 2, 4):
         assert np.abs(got[i] - src[i] @ np.linalg.inv(ref[i])).max() <= osn.compose_bound(src[i], ref[i])
+
+
+# ---- the launcher's stream rule --------------------------------------------------------------------------
+def test_launch_runs_on_the_current_stream(dev, monkeypatch):
+    """A native call goes to the stream that is current where it is made (_lib.launch).  Under `with torch.cuda.stream(side)` the
+    blend of the ConvGRU cell is handed `side`'s handle and not the handle of the stream that produced the operands -- read off the
+    call itself, on both of launch's paths (device already current / selected by the guard) -- and, with the copy back on `side`
+    too and only `side` synchronised, the result is bit for bit u * h + (1 - u) * y."""
+    from satmvs_amd import _lib
+    from satmvs_amd.modules.train_fns import _GruBlendFn
+    g = torch.Generator().manual_seed(11)
+    producer = torch.cuda.current_stream(dev)
+    u, h, y = (torch.rand(3, 1024, generator=g).to(dev) * s for s in (1.0, 3.0, -2.0))      # produced on `producer`
+    want = (u * h + (1 - u) * y).cpu()
+    side = torch.cuda.Stream(dev)
+    assert side.cuda_stream != producer.cuda_stream
+    seen = []
+    real_call = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *args: (seen.append((name, args[-1].value or 0)), real_call(name, *args))[1])
+    side.wait_stream(producer)
+    with torch.cuda.stream(side):
+        out = _GruBlendFn.apply(u, h, y)
+        got = torch.empty(out.shape, dtype=out.dtype).pin_memory()
+        got.copy_(out, non_blocking=True)
+        monkeypatch.setattr(torch.cuda, "current_device", lambda: -1)      # "another device is current": launch enters its guard
+        out2 = _GruBlendFn.apply(u, h, y)
+        monkeypatch.undo()
+        got2 = out2.cpu()
+    side.synchronize()
+    assert seen == [("smvs_gru_blend_fwd", side.cuda_stream)] * 2
+    assert got.shape == (3, 1024) and torch.equal(got, want) and torch.equal(got2, want)
+    torch.cuda.synchronize(dev)
