@@ -681,7 +681,50 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   A cell that takes one tap with the weight 1 (always in mode 0) gets (float)((double)z + dz), and with dz == 0 the tap's
  *   bits.
  *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; sizes >= 1, gws * ghs and gwd * ghd < 2^31;
- *   finite origins, finite resolutions > 0; mode 0 or 1; dz finite; out distinct from src. */
+ *   finite origins, finite resolutions > 0; mode 0 or 1; dz finite; out distinct from src.
+ *
+ * Mosaic (csrc/dsm_mosaic.hip).
+ * smvs_dsm_dist: the exact squared Euclidean distance transform.  mask (gh, gw) uint8 (device), read only: non-zero cells are
+ *   foreground, any non-zero byte.  The background set B holds the zero cells and, with border = 1, every cell off the grid
+ *   (the whole plane outside).  d2 (gh, gw) int32: d2[r][c] = min(cap^2, min over (r', c') in B of (r - r')^2 + (c - c')^2),
+ *   cap = max_dist; an empty B gives cap^2 everywhere; a value of cap^2 means "at least cap".  These are the squares of
+ *   scipy.ndimage.distance_transform_edt(mask), capped; with border = 1 the same on the mask padded by one ring of zeros,
+ *   cropped back.  Integers only, every value a minimum: equal bits from run to run and to the numpy statement of this rule.
+ *   The entry writes every element of d2 and of the part of the workspace it reads (a workspace full of anything will do);
+ *   no atomics, no host synchronisation.  The cap is part of the contract: it bounds every halo.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; gw, gh >= 1, gw * gh < 2^31; border 0 or 1;
+ *   1 <= max_dist <= 1024; d2 and workspace distinct from mask and from each other; workspace:
+ *   smvs_dsm_dist_workspace_bytes(gw, gh, max_dist) bytes (0 = unsupported arguments).
+ * smvs_dsm_mosaic: n_layers layers (a HOST array of smvs_dsm_layer; z (gh, gw) float32 and d2 (gh, gw) int32 on the device,
+ *   read only) combined into the (gh, gw) destination.  Layer k's cell (r, c) lies on destination cell (r + oy_k, c + ox_k);
+ *   what falls off the destination is ignored, and a layer that misses it altogether contributes nothing.  A layer cell is
+ *   valid iff it is finite and != (float)nodata, as above.  For a destination cell V is the list of the layers valid there, in
+ *   ascending k, m = |V|.  out (gh, gw) float32 gets (float)nodata where V is empty, else by mode:
+ *   0 first: the bits of the first of V.  1 last: the bits of the last of V.
+ *   2 min / 3 max: the bits of the lowest / highest of V by the order of the keys above (-0.0 below +0.0); ties keep the
+ *     earlier layer.
+ *   4 mean: (float)(S / m), S the float64 sum of (double)z over V in ascending k, STARTED FROM THE FIRST TERM (not from 0.0).
+ *   5 feather: (float)(S / W), S = sum of w_k (double)z_k, W = sum of w_k over V in ascending k, both started from their
+ *     first terms, w_k = sqrt((double)min(max(d2_k, 1), feather^2)): the weight ramps up over `feather` cells from the tile's
+ *     edge and voids when d2 is smvs_dsm_dist of the layer's validity mask with border = 1, and a wrong d2 can never give a
+ *     zero or NaN weight.
+ *   The float64 operations are IEEE, each product, sum, square root and quotient rounded by itself to nearest, nothing
+ *   contracted.  Starting from the first term makes a mosaic of one layer that layer's bits in every mode (-0.0 included:
+ *   w z / w is within a float64 rounding or two of z, far inside half a float32 ulp).
+ *   Optional outputs (each may be null; the entry writes every element): count (gh, gw) uint8 = m; source (gh, gw) uint8 =
+ *   the layer taken in modes 0 .. 3, the layer with the largest weight in modes 4 and 5 (ties to the earlier layer; in mode 4
+ *   the first of V), 255 where V is empty; spread (gh, gw) float32 = (float)((double)hi - (double)lo), hi and lo the highest
+ *   and lowest of V, 0 for one layer, (float)nodata where V is empty.
+ *   One launch, one lane per destination cell, the layer table in the kernel arguments; no workspace, atomics or state.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null layers, out and every z; 1 <= n_layers <= 64; every size
+ *   >= 1 and below 2^31 cells; |ox|, |oy| < 2^30; mode 0 .. 5; in mode 5 1 <= feather <= 1024 and every d2 non-null (feather
+ *   and d2 are ignored otherwise); out, count, source and spread distinct from each other and from every layer buffer. */
+typedef struct smvs_dsm_layer {
+    const float* z;              /* (gh, gw) float32, device */
+    const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
+    int gw, gh, ox, oy;
+} smvs_dsm_layer;
+
 int smvs_tm_project(const double* tm7, const double* a, const double* b, double* o0, double* o1, size_t n, int dir, void* stream);
 int smvs_rpc_dsm_bin(const float* height, const unsigned char* mask, const double* rpc170, int H, int W,
                      const double* tm7, const double* grid4, int gw, int gh,
@@ -718,6 +761,11 @@ int smvs_dsm_shift_stats(const float* a, int gwa, int gha, const float* b, int g
                          long long* stats, void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_regrid(const float* src, int gws, int ghs, const double* grid4_src, float nodata,
                     const double* grid4_dst, int gwd, int ghd, int mode, double dz, float* out, void* stream);
+size_t smvs_dsm_dist_workspace_bytes(int gw, int gh, int max_dist);
+int smvs_dsm_dist(const unsigned char* mask, int gw, int gh, int border, int max_dist,
+                  int* d2, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_mosaic(const smvs_dsm_layer* layers, int n_layers, float nodata, int mode, int feather,
+                    int gw, int gh, float* out, unsigned char* count, unsigned char* source, float* spread, void* stream);
 
 #ifdef __cplusplus
 }

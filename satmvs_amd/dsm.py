@@ -28,6 +28,13 @@ and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epo
     scores = compare_dsms(dsm, grid, gt, gt_grid)              # {"shift", "before", "after"}: dsm_metrics around the registration
     diff, labels, stats = changes(new, new_grid, old, old_grid)   # rises and falls above 2.5 m and 50 m^2 as objects
 
+and several DSMs (one per stereo triplet, strip, block or epoch) put together into one, feathered so that no seam shows:
+
+    reg = coregister(tile, g, ref, ref_grid)                   # the tile's offset against what is there already
+    whole = mosaic([ref, tile - reg["dz"]], [ref_grid, reg["grid"]], align="bilinear")   # on mosaic_grid(...) of the two
+    d = distance(valid, max_dist=64)                           # the building block: cells to the nearest void, exact
+    near = buffer_mask(~valid, 2.5)                            # everything within 2.5 cells of a void, for scoring
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -52,12 +59,16 @@ smvs_dsm_label is a union-find over cell indices (tiles in LDS, tile borders wit
 for the numbering); smvs_dsm_label_stats reduces along rows and columns on chip before its integer atomics.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
+smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
+carried along columns, then a lower envelope searched outwards along rows in LDS); smvs_dsm_mosaic is one lane per
+destination cell over a table of up to 64 layers, float64 sums in the list's order.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -926,6 +937,194 @@ def changes(a, grid_a, b, grid_b, min_dh=2.5, min_area_m2=50.0, register=True, c
     stats["sign"] = torch.cat([torch.ones(n_up, dtype=torch.int8, device=za.device),
                                -torch.ones(int(down["area"].numel()), dtype=torch.int8, device=za.device)])
     return _back(as_numpy, diff), _back(as_numpy, labels), {k: _back(as_numpy, v) for k, v in stats.items()}
+
+
+# ---- mosaic: the distance to the nearest void or edge, and tiles on one lattice blended into one DSM ----------------------------
+MAX_DIST = 1024
+MAX_MOSAIC_LAYERS = 64
+MOSAIC_MODES = {"first": 0, "last": 1, "min": 2, "max": 3, "mean": 4, "feather": 5}
+ALIGN_TOLERANCE = 1e-6                                            # cells; see mosaic()
+
+
+class _Layer(ctypes.Structure):                                   # smvs_dsm_layer of include/satmvs.h
+    _fields_ = [("z", ctypes.c_void_p), ("d2", ctypes.c_void_p), ("gw", ctypes.c_int), ("gh", ctypes.c_int),
+                ("ox", ctypes.c_int), ("oy", ctypes.c_int)]
+
+
+def _mask_u8(mask):
+    """A checked mask as a contiguous uint8 device tensor of 0 / 1 -> (tensor, whether the caller gave numpy)."""
+    mask = _mask_checked(mask)
+    if not isinstance(mask, torch.Tensor):
+        mask = np.not_equal(mask, 0).view(np.uint8)
+    m, as_numpy = _to_device(mask)
+    return (m != 0).to(torch.uint8).contiguous(), as_numpy
+
+
+def _dist(m, max_dist, border):
+    """smvs_dsm_dist of a uint8 device mask -> (gh, gw) int32 device tensor."""
+    gh, gw = m.shape
+    nbytes = _lib.load().smvs_dsm_dist_workspace_bytes(gw, gh, max_dist)
+    if nbytes == 0:
+        raise ValueError("unsupported distance transform: %d x %d cells, max_dist %d" % (gw, gh, max_dist))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+    d2 = torch.empty((gh, gw), dtype=torch.int32, device=m.device)
+    _call(m.device, "smvs_dsm_dist", m, gw, gh, 1 if border else 0, max_dist, d2, ws, nbytes)
+    return d2
+
+
+def _max_dist_checked(max_dist, shape):
+    if max_dist is None:
+        return min(MAX_DIST, int(math.ceil(math.hypot(int(shape[0]), int(shape[1])))))
+    return _int_checked(max_dist, "max_dist", 1, MAX_DIST)
+
+
+def distance(mask, max_dist=None, border=False, squared=False):
+    """The exact Euclidean distance of every cell to the nearest background cell (include/satmvs.h smvs_dsm_dist, DESIGN.md
+    section 9, "Mosaic"): mask (gh, gw), bool or an integer dtype, numpy or a device tensor, non-zero = foreground; the
+    background is the zero cells and, with `border`, everything off the grid.  Distances are capped at max_dist cells
+    (1 .. 1024; None = min(1024, ceil(hypot(gh, gw))), which no distance within the grid exceeds): a value equal to max_dist
+    means "at least max_dist", also where there is no background cell at all.
+    -> (gh, gw) int32 squared distances with `squared` (scipy.ndimage.distance_transform_edt(mask)^2, capped, bit for bit), else
+    their float32 square roots in cells; numpy if the mask came as numpy, a device tensor otherwise."""
+    mask = _mask_checked(mask)
+    max_dist = _max_dist_checked(max_dist, mask.shape)
+    m, as_numpy = _mask_u8(mask)
+    d2 = _dist(m, max_dist, border)
+    return _back(as_numpy, d2 if squared else d2.to(torch.float64).sqrt().to(torch.float32))
+
+
+def _radius_cap(radius):
+    """(floor(radius^2), the transform's cap) of a buffer radius, checked."""
+    radius = float(radius)
+    if not (0.0 < radius < float(MAX_DIST)):
+        raise ValueError("radius must be above 0 and below %d cells (at %d the transform's cap could not tell 'exactly' from "
+                         "'further'), got %r" % (MAX_DIST, MAX_DIST, radius))
+    return int(math.floor(radius * radius)), int(math.floor(radius)) + 1
+
+
+def buffer_mask(mask, radius, border=False):
+    """The Euclidean buffer of a mask: True where a set cell lies within `radius` cells, inclusive (the set cells themselves
+    are True), as the integer comparison d^2 <= floor(radius^2) on distance(~mask, floor(radius) + 1, border, squared=True).
+    With `border` everything off the grid counts as set.  0 < radius < 1024.
+    -> (gh, gw) bool; numpy if the mask came as numpy, a device tensor otherwise."""
+    mask = _mask_checked(mask)
+    limit, cap = _radius_cap(radius)
+    m, as_numpy = _mask_u8(mask)
+    return _back(as_numpy, _dist(1 - m, cap, border) <= limit)
+
+
+def _layer_offset(grid, to_grid):
+    """Where cell (0, 0) of `grid` lies on `to_grid`, from the world-file numbers in float64 -> (ox, oy, aligned)."""
+    u = (float(grid.e0) - float(to_grid.e0)) / float(to_grid.xres)
+    v = (float(to_grid.n0) - float(grid.n0)) / float(to_grid.yres)
+    ox, oy = math.floor(u + 0.5), math.floor(v + 0.5)
+    aligned = _same_resolution(grid, to_grid) and abs(u - ox) <= ALIGN_TOLERANCE and abs(v - oy) <= ALIGN_TOLERANCE
+    return int(ox), int(oy), aligned
+
+
+def _span_on(grid, to_grid):
+    """The first and last column and row of to_grid's lattice (unclipped) that the cell centres of `grid` reach."""
+    ox, oy, aligned = _layer_offset(grid, to_grid)
+    if aligned:
+        return ox, ox + int(grid.width) - 1, oy, oy + int(grid.height) - 1
+    u0 = (float(grid.e0) - float(to_grid.e0)) / float(to_grid.xres)
+    v0 = (float(to_grid.n0) - float(grid.n0)) / float(to_grid.yres)
+    u1 = u0 + (int(grid.width) - 1) * float(grid.xres) / float(to_grid.xres)
+    v1 = v0 + (int(grid.height) - 1) * float(grid.yres) / float(to_grid.yres)
+    return math.floor(u0), math.ceil(u1), math.floor(v0), math.ceil(v1)
+
+
+def _grids_checked(grids):
+    grids = list(grids)
+    if not grids:
+        raise ValueError("a mosaic needs at least one layer")
+    if len(grids) > MAX_MOSAIC_LAYERS:
+        raise ValueError("a mosaic takes at most %d layers, got %d: mosaic them in groups" % (MAX_MOSAIC_LAYERS, len(grids)))
+    return [_grid_checked(g, "grids[%d]" % k) for k, g in enumerate(grids)]
+
+
+def mosaic_grid(grids):
+    """The smallest DSMGrid on the lattice of grids[0] (its origin and cell sizes) that covers the cell centres of every grid."""
+    grids = _grids_checked(grids)
+    first = grids[0]
+    spans = [_span_on(g, first) for g in grids]
+    c0, c1 = min(s[0] for s in spans), max(s[1] for s in spans)
+    r0, r1 = min(s[2] for s in spans), max(s[3] for s in spans)
+    out = DSMGrid(float(first.e0) + c0 * float(first.xres), float(first.n0) - r0 * float(first.yres), first.xres, first.yres,
+                  int(c1 - c0 + 1), int(r1 - r0 + 1))
+    return _grid_checked(out, "the mosaic's grid")
+
+
+def mosaic(dsms, grids, to_grid=None, mode="feather", feather=16, align=None, nodata=-999.0,
+           return_count=False, return_source=False, return_spread=False):
+    """Several DSMs put together on one grid (include/satmvs.h smvs_dsm_mosaic, DESIGN.md section 9, "Mosaic").  dsms[k] is
+    (grids[k].height, grids[k].width) of any real dtype (taken as float32), numpy or a device tensor; at most 64 layers;
+    to_grid=None means mosaic_grid(grids).  Where several layers are valid a destination cell takes, by `mode`, the "first" or
+    "last" of them in the list's order, the "min" or "max" (ties to the earlier layer), their "mean" (float64, in the list's
+    order), or the "feather" blend: the mean with the weights min(max(d, 1), feather), d the distance [cells] of the layer's
+    cell to the layer's nearest void or edge (smvs_dsm_dist of its validity mask with the border as background), so a tile
+    fades out over `feather` cells towards its seams instead of leaving a step there.  Cells no layer covers get nodata; one
+    layer alone comes back bit for bit in every mode.
+    A layer is aligned iff its xres and yres equal to_grid's and its offsets ox = (e0_k - e0_d) / xres, oy = (n0_d - n0_k) /
+    yres (float64) are within 1e-6 cell of integers -- a stated choice: world-file doubles at UTM magnitudes resolve about
+    1e-10 cell of 5 m, and 1e-6 cell is 5 micrometres.  An unaligned layer raises ValueError unless align = "nearest" or
+    "bilinear", which regrid()s it first onto the part of to_grid's lattice it covers.  The defaults (feather 16, 1e-6 cell)
+    are a choice for 5 m grids on a synthetic scene, not tuned on real data.
+    -> (to_grid.height, to_grid.width) float32, then with return_count uint8 the number of valid layers per cell, with
+    return_source uint8 the layer taken (first .. max) or weighing most (mean: the first valid; feather; 255 = none), with
+    return_spread float32 highest - lowest valid layer (the overlap-agreement map; nodata where none), in that order; numpy
+    if dsms[0] came as numpy, device tensors otherwise."""
+    if mode not in MOSAIC_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
+    if align is not None and align not in REGRID_MODES:
+        raise ValueError("align must be None or one of %s, got %r" % (sorted(REGRID_MODES), align))
+    feather = _int_checked(feather, "feather", 1, MAX_DIST)
+    dsms = list(dsms)
+    grids = _grids_checked(grids)
+    if len(dsms) != len(grids):
+        raise ValueError("one grid per DSM: %d DSMs, %d grids" % (len(dsms), len(grids)))
+    to_grid = mosaic_grid(grids) if to_grid is None else _grid_checked(to_grid, "to_grid")
+    gw, gh = int(to_grid.width), int(to_grid.height)
+    dsms = [_dsm_converted(z, g) for z, g in zip(dsms, grids)]
+    plan = []                                                # per layer: (ox, oy, None) or (c0, r0, the sub-grid to regrid onto)
+    for k, g in enumerate(grids):
+        ox, oy, aligned = _layer_offset(g, to_grid)
+        if aligned:
+            if abs(ox) >= 2 ** 30 or abs(oy) >= 2 ** 30:
+                raise ValueError("grids[%d] lies %d, %d cells from to_grid: offsets must be below 2^30" % (k, ox, oy))
+            plan.append((ox, oy, None))
+            continue
+        if align is None:
+            raise ValueError("grids[%d] is not aligned with to_grid (equal cell sizes and an offset within %g cell of whole cells): "
+                             "pass align='nearest' or 'bilinear', or regrid() it yourself" % (k, ALIGN_TOLERANCE))
+        c0, c1, r0, r1 = _span_on(g, to_grid)
+        c0, c1, r0, r1 = max(c0, 0), min(c1, gw - 1), max(r0, 0), min(r1, gh - 1)
+        if c1 < c0 or r1 < r0:                               # misses the destination: one void cell stands for it
+            c0 = c1 = r0 = r1 = 0
+        sub = DSMGrid(float(to_grid.e0) + c0 * float(to_grid.xres), float(to_grid.n0) - r0 * float(to_grid.yres),
+                      to_grid.xres, to_grid.yres, c1 - c0 + 1, r1 - r0 + 1)
+        plan.append((c0, r0, sub))
+    as_numpy = not isinstance(dsms[0], torch.Tensor)
+    dev = _dev() if as_numpy or not dsms[0].is_cuda else dsms[0].device
+    nd = float(np.float32(nodata))
+    table = (_Layer * len(dsms))()
+    held = []                                                # every layer's tensors, alive until the call is enqueued
+    for k, (z, g, (ox, oy, sub)) in enumerate(zip(dsms, grids, plan)):
+        z, _ = _to_device(z, torch.float32, dev)
+        if sub is not None:
+            z = regrid(z, g, sub, mode=align, nodata=nodata)
+        d2 = None
+        if mode == "feather":
+            d2 = _dist((torch.isfinite(z) & (z != nd)).to(torch.uint8), feather, True)
+        held.append((z, d2))
+        table[k] = _Layer(z.data_ptr(), d2.data_ptr() if d2 is not None else None, int(z.shape[1]), int(z.shape[0]), ox, oy)
+    out = torch.empty((gh, gw), dtype=torch.float32, device=dev)
+    count = torch.empty((gh, gw), dtype=torch.uint8, device=dev) if return_count else None
+    source = torch.empty((gh, gw), dtype=torch.uint8, device=dev) if return_source else None
+    spread = torch.empty((gh, gw), dtype=torch.float32, device=dev) if return_spread else None
+    _call(dev, "smvs_dsm_mosaic", table, len(dsms), float(nodata), MOSAIC_MODES[mode], feather, gw, gh, out, count, source, spread)
+    del held
+    return _back(as_numpy, *([out] + [t for t in (count, source, spread) if t is not None]))
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
