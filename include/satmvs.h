@@ -718,7 +718,43 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   One launch, one lane per destination cell, the layer table in the kernel arguments; no workspace, atomics or state.
  *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null layers, out and every z; 1 <= n_layers <= 64; every size
  *   >= 1 and below 2^31 cells; |ox|, |oy| < 2^30; mode 0 .. 5; in mode 5 1 <= feather <= 1024 and every d2 non-null (feather
- *   and d2 are ignored otherwise); out, count, source and spread distinct from each other and from every layer buffer. */
+ *   and d2 are ignored otherwise); out, count, source and spread distinct from each other and from every layer buffer.
+ *
+ * Sun (csrc/dsm_sun.hip).
+ * smvs_dsm_shadow: cast shadows as an exclusive running maximum along lines of cells that run towards the sun.  dsm (gh, gw)
+ *   float32 (device), read only; a cell is valid iff it is finite and != (float)nodata, as above.  (ucol, urow) is the
+ *   horizontal direction TOWARDS the sun in cell-index units (columns run east, rows south), finite, not both 0.  There is
+ *   no trigonometry in the library: the caller derives ucol, urow, a and b (dsm.sun_terms: a = tan(elevation) xres sin(az),
+ *   b = -tan(elevation) yres cos(az), so that a c + b r is tan(elevation) times the distance along the sun's direction).
+ *   Lines.  If |urow| >= |ucol| (a tie included) the grid is row-major: m = ucol / urow (one IEEE division, |m| <= 1),
+ *   s(r) = floor(m (double)r + 0.5) (a product, then a sum, then a floor, not contracted), the line of cell (r, c) is
+ *   L = c - s(r), so a row holds at most one cell of a line, and sunward order is ascending r if urow < 0, descending r if
+ *   urow > 0.  Otherwise it is column-major: m = urow / ucol, s(c) = floor(m (double)c + 0.5), L = r - s(c), ascending c if
+ *   ucol < 0, descending c if ucol > 0.
+ *   Key.  g(r, c) = (double)z - (a (double)c + b (double)r): two products, their sum, then the difference, each rounded by
+ *   itself.
+ *   Result.  For a valid cell G is the maximum of g over the VALID cells of its line that come before it in sunward order
+ *   (an exclusive scan; -inf if there are none; of two zeros +0.0 is the greater, the keys' order above), and d = G - g,
+ *   one float64 subtraction.  shade (gh, gw) uint8: 0 at an invalid cell, 2 if d > tol, else 1.  depth, if non-null,
+ *   (gh, gw) float32: (float)d at valid cells (-inf where nothing lies sunward), (float)nodata at invalid cells.  Invalid
+ *   cells neither occlude nor receive.  A maximum does not depend on the order of its operands, so the bits are equal from
+ *   run to run, for any decomposition of the scan, and equal to the numpy statement of this rule.
+ *   A line follows the true ray to within less than one cell across it (s(i) - m i lies in (-1/2, 1/2] at both cells);
+ *   the distance along the ray is exact.
+ *   The entry writes every element of its outputs and of the part of the workspace it reads; no atomics, no host
+ *   synchronisation.  The workspace size depends on (gw, gh) alone and covers every direction.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null dsm, shade and workspace; gw, gh >= 1, gw * gh < 2^31;
+ *   finite ucol, urow, not both 0; a, b finite and at most 2^900 in size (so that every g is finite); tol finite and >= 0;
+ *   shade, depth and workspace distinct from dsm and from each other; workspace: smvs_dsm_shadow_workspace_bytes(gw, gh)
+ *   bytes (0 = unsupported sizes).
+ * smvs_dsm_gradient: Horn's 3 x 3 gradient.  A neighbour that is off the grid or invalid takes the centre's value.  For a
+ *   valid cell, with z as doubles:
+ *   dzde = (float)((((z[r-1,c+1] + 2 z[r,c+1]) + z[r+1,c+1]) - ((z[r-1,c-1] + 2 z[r,c-1]) + z[r+1,c-1])) / (8 xres))
+ *   dzdn = (float)((((z[r-1,c-1] + 2 z[r-1,c]) + z[r-1,c+1]) - ((z[r+1,c-1] + 2 z[r+1,c]) + z[r+1,c+1])) / (8 yres))
+ *   in this order, every operation rounded by itself (8 xres and 8 yres are one product each); invalid cells get
+ *   (float)nodata in both outputs.  One lane per cell; bit-identical to its numpy statement.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; gw, gh >= 1, gw * gh < 2^31; finite
+ *   resolutions > 0; dzde and dzdn distinct from dsm and from each other. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -766,6 +802,12 @@ int smvs_dsm_dist(const unsigned char* mask, int gw, int gh, int border, int max
                   int* d2, void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_mosaic(const smvs_dsm_layer* layers, int n_layers, float nodata, int mode, int feather,
                     int gw, int gh, float* out, unsigned char* count, unsigned char* source, float* spread, void* stream);
+size_t smvs_dsm_shadow_workspace_bytes(int gw, int gh);
+int smvs_dsm_shadow(const float* dsm, int gw, int gh, float nodata,
+                    double ucol, double urow, double a, double b, double tol,
+                    unsigned char* shade, float* depth, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_gradient(const float* dsm, int gw, int gh, float nodata, double xres, double yres,
+                      float* dzde, float* dzdn, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,13 @@ and several DSMs (one per stereo triplet, strip, block or epoch) put together in
     d = distance(valid, max_dist=64)                           # the building block: cells to the nearest void, exact
     near = buffer_mask(~valid, 2.5)                            # everything within 2.5 cells of a void, for scoring
 
+and the sun over a DSM: cast shadows for a given sun, shaded relief, and exposure over a list of suns:
+
+    shade = cast_shadows(dsm, grid, azimuth=135.0, elevation=30.0)      # uint8: 0 no height, 1 lit, 2 in cast shadow
+    relief = hillshade(dsm, grid, azimuth=315.0, elevation=45.0, shadows=True)   # float32 in [0, 1]; slope(), aspect(), gradient()
+    exposure = sun_exposure(dsm, grid, suns, weights)          # sum of w cos(incidence) over the suns that reach a cell
+    per_roof = label_stats(labels, n, values=exposure)         # "how much sun does this roof get"
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -62,6 +69,9 @@ shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination c
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
 carried along columns, then a lower envelope searched outwards along rows in LDS); smvs_dsm_mosaic is one lane per
 destination cell over a table of up to 64 layers, float64 sums in the list's order.
+smvs_dsm_shadow is an exclusive running maximum of z - tan(elevation) (distance towards the sun) along sheared lines of
+the grid, a lane per line, cut into bands with an exact carry, the east-west directions between tile transposes through LDS;
+smvs_dsm_gradient is Horn's 3 x 3 gradient, one lane per cell.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -1344,3 +1354,175 @@ def dsm_metrics(est, gt, nodata, thresholds=(2.5, 7.5)):
         for t in thresholds:
             out["<%g" % t] = float("nan")
     return out
+
+
+# ---- the sun: cast shadows, gradient, shaded relief, exposure -------------------------------------------------------------------
+def _sun_checked(azimuth, elevation):
+    azimuth, elevation = float(azimuth), float(elevation)
+    if not math.isfinite(azimuth):
+        raise ValueError("azimuth must be finite [degrees clockwise from north], got %r" % azimuth)
+    if not 0.0 < elevation < 90.0:
+        raise ValueError("elevation must be above 0 and below 90 degrees, got %r" % elevation)
+    return azimuth, elevation
+
+
+def _shadow_tol_checked(tol):
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol must be finite and >= 0, got %r" % tol)
+    return tol
+
+
+def sun_terms(grid, azimuth, elevation):
+    """The four doubles smvs_dsm_shadow takes for a sun at `azimuth` [degrees clockwise from north, TOWARDS the sun, any finite
+    value] and `elevation` [degrees, above 0 and below 90] over `grid`: with sA, cA = sin, cos(radians(azimuth)) and k =
+    tan(radians(elevation)), ucol = sA / xres, urow = -cA / yres (the direction towards the sun in cells; rows run south),
+    a = k xres sA, b = -k yres cA (k times the distance towards the sun, per column and per row).  -> (ucol, urow, a, b)."""
+    azimuth, elevation = _sun_checked(azimuth, elevation)
+    _grid_checked(grid, "grid")
+    xres, yres = float(grid.xres), float(grid.yres)
+    sA, cA = math.sin(math.radians(azimuth)), math.cos(math.radians(azimuth))
+    k = math.tan(math.radians(elevation))
+    return sA / xres, -cA / yres, k * xres * sA, -k * yres * cA
+
+
+def _shadow_workspace(z):
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_shadow_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported shadow casting: %d x %d cells" % (gw, gh))
+    return torch.empty(nbytes, dtype=torch.uint8, device=z.device), nbytes
+
+
+def _shadow(z, terms, nodata, tol, ws, nbytes, want_depth=False):
+    """smvs_dsm_shadow on a device grid with a workspace the caller keeps -> (shade, depth or None)."""
+    gh, gw = z.shape
+    shade = torch.empty((gh, gw), dtype=torch.uint8, device=z.device)
+    depth = torch.empty((gh, gw), dtype=torch.float32, device=z.device) if want_depth else None
+    _call(z.device, "smvs_dsm_shadow", z, gw, gh, float(nodata), *terms, tol, shade, depth, ws, nbytes)
+    return shade, depth
+
+
+def cast_shadows(dsm, grid, azimuth, elevation, nodata=-999.0, tol=0.1, return_depth=False):
+    """The cells of a DSM in cast shadow for one sun (include/satmvs.h smvs_dsm_shadow, DESIGN.md section 9, "Sun").  azimuth:
+    degrees clockwise from north TOWARDS the sun, any finite value; 0 < elevation < 90 degrees.  Along a line of cells that
+    runs towards the sun, a cell is shadowed iff the highest g = z - tan(elevation) (distance towards the sun) among the valid
+    cells sunward of it exceeds its own g by more than tol [m]; the lines are the grid's rows or columns sheared by whole
+    cells, within less than a cell of the true ray, and the reach is unbounded.  Invalid cells neither cast nor receive.
+    The default tol (0.1 m) is a choice for 5 m grids, not tuned on real data: it keeps float32 rounding of the
+    heights from shading a plane that runs exactly along the ray.  dsm (grid.height, grid.width) of any real dtype (taken as
+    float32), numpy or a device tensor.
+    -> shade (gh, gw) uint8: 0 invalid, 1 lit, 2 shadowed (and, with return_depth, depth (gh, gw) float32: how far [m] the
+    cell lies under the shadow line, negative where lit, -inf where nothing lies sunward, nodata at invalid cells); numpy if
+    the DSM came as numpy, device tensors otherwise."""
+    terms = sun_terms(grid, azimuth, elevation)
+    tol = _shadow_tol_checked(tol)
+    dsm = _dsm_converted(dsm, grid)
+    z, as_numpy = _to_device(dsm, torch.float32)
+    ws, nbytes = _shadow_workspace(z)
+    shade, depth = _shadow(z, terms, nodata, tol, ws, nbytes, return_depth)
+    shade, depth = _back(as_numpy, shade, depth)
+    return (shade, depth) if return_depth else shade
+
+
+def _gradient(z, grid, nodata):
+    gh, gw = z.shape
+    dzde, dzdn = torch.empty_like(z), torch.empty_like(z)
+    _call(z.device, "smvs_dsm_gradient", z, gw, gh, float(nodata), float(grid.xres), float(grid.yres), dzde, dzdn)
+    return dzde, dzdn
+
+
+def _relief_input(dsm, grid):
+    _grid_checked(grid, "grid")
+    return _to_device(_dsm_converted(dsm, grid), torch.float32)
+
+
+def gradient(dsm, grid, nodata=-999.0):
+    """Horn's 3 x 3 gradient of a DSM (include/satmvs.h smvs_dsm_gradient): dzde [m/m] towards the east, dzdn towards the
+    north; a neighbour off the grid or invalid takes the centre's value; invalid cells get nodata in both.
+    -> (dzde, dzdn) (gh, gw) float32; numpy if the DSM came as numpy, device tensors otherwise."""
+    z, as_numpy = _relief_input(dsm, grid)
+    return _back(as_numpy, *_gradient(z, grid, nodata))
+
+
+def _valid_cells(z, nodata):
+    return torch.isfinite(z) & (z != float(np.float32(nodata)))
+
+
+def slope(dsm, grid, nodata=-999.0, degrees=True):
+    """The steepest slope atan(sqrt(dzde^2 + dzdn^2)) of gradient(), float64 element-wise, in degrees or radians; NaN at
+    invalid cells.  -> (gh, gw) float32."""
+    z, as_numpy = _relief_input(dsm, grid)
+    dzde, dzdn = (t.double() for t in _gradient(z, grid, nodata))
+    s = torch.atan(torch.sqrt(dzde * dzde + dzdn * dzdn))
+    if degrees:
+        s = torch.rad2deg(s)
+    return _back(as_numpy, torch.where(_valid_cells(z, nodata), s, torch.full_like(s, float("nan"))).float())
+
+
+def aspect(dsm, grid, nodata=-999.0):
+    """The downslope azimuth atan2(-dzde, -dzdn) of gradient() in degrees clockwise from north, in [0, 360); NaN on flat
+    cells (both components 0) and at invalid cells.  -> (gh, gw) float32."""
+    z, as_numpy = _relief_input(dsm, grid)
+    dzde, dzdn = (t.double() for t in _gradient(z, grid, nodata))
+    a = torch.rad2deg(torch.atan2(-dzde, -dzdn))
+    a = torch.where(a < 0.0, a + 360.0, a).float()
+    a = torch.where(a >= 360.0, torch.zeros_like(a), a)      # -1e-12 + 360 rounds to 360 in float32
+    flat = (dzde == 0.0) & (dzdn == 0.0)
+    return _back(as_numpy, torch.where(_valid_cells(z, nodata) & ~flat, a, torch.full_like(a, float("nan"))))
+
+
+def _cos_incidence(dzde, dzdn, azimuth, elevation):
+    """max(0, (sinE - cosE (dzde sA + dzdn cA)) / sqrt(1 + dzde^2 + dzdn^2)) in float64, the operations in this order."""
+    sA, cA = math.sin(math.radians(azimuth)), math.cos(math.radians(azimuth))
+    sE, cE = math.sin(math.radians(elevation)), math.cos(math.radians(elevation))
+    num = sE - cE * (dzde * sA + dzdn * cA)
+    return torch.clamp(num / torch.sqrt(1.0 + dzde * dzde + dzdn * dzdn), min=0.0)
+
+
+def hillshade(dsm, grid, azimuth=315.0, elevation=45.0, shadows=False, nodata=-999.0, tol=0.1):
+    """Shaded relief: the cosine of the sun's incidence on the surface of gradient(), cos i = (sinE - cosE (dzde sA + dzdn
+    cA)) / sqrt(1 + dzde^2 + dzdn^2) in float64, clipped at 0; with `shadows`, 0 where cast_shadows(..., tol) says shadowed.
+    azimuth, elevation and tol as in cast_shadows (the default sun, north-west at 45 degrees, is the cartographic habit).
+    -> (gh, gw) float32 in [0, 1], NaN at invalid cells; numpy if the DSM came as numpy, a device tensor otherwise."""
+    azimuth, elevation = _sun_checked(azimuth, elevation)
+    tol = _shadow_tol_checked(tol)
+    terms = sun_terms(grid, azimuth, elevation) if shadows else None
+    z, as_numpy = _relief_input(dsm, grid)
+    dzde, dzdn = (t.double() for t in _gradient(z, grid, nodata))
+    h = _cos_incidence(dzde, dzdn, azimuth, elevation)
+    if shadows:
+        ws, nbytes = _shadow_workspace(z)
+        shade, _ = _shadow(z, terms, nodata, tol, ws, nbytes)
+        h = torch.where(shade == 2, torch.zeros_like(h), h)
+    return _back(as_numpy, torch.where(_valid_cells(z, nodata), h, torch.full_like(h, float("nan"))).float())
+
+
+def sun_exposure(dsm, grid, suns, weights=None, incidence=True, nodata=-999.0, tol=0.1):
+    """What a list of suns leaves on every cell: the float64 sum, in the list's order, of w lit (cos i if incidence else 1),
+    lit = 1 where cast_shadows does not say shadowed, cos i as in hillshade.  suns: a list of (azimuth, elevation) pairs, e.g.
+    the sun's positions through a day; weights: one finite number per sun (None: all 1), e.g. hours or irradiance.  One
+    workspace serves the whole list (its size depends on the grid alone).  With the labels of extract_objects,
+    label_stats(labels, n, values=exposure)["mean"] is the sun each roof gets.
+    -> (gh, gw) float32, NaN at invalid cells; numpy if the DSM came as numpy, a device tensor otherwise."""
+    try:
+        suns = [_sun_checked(*s) for s in suns]
+    except TypeError:
+        raise ValueError("suns must be a list of (azimuth, elevation) pairs, got %r" % (suns,)) from None
+    if not suns:
+        raise ValueError("sun_exposure needs at least one sun")
+    weights = [1.0] * len(suns) if weights is None else [_finite(w, "a weight") for w in weights]
+    if len(weights) != len(suns):
+        raise ValueError("one weight per sun: %d suns, %d weights" % (len(suns), len(weights)))
+    tol = _shadow_tol_checked(tol)
+    terms = [sun_terms(grid, az, el) for az, el in suns]
+    z, as_numpy = _relief_input(dsm, grid)
+    ws, nbytes = _shadow_workspace(z)
+    total = torch.zeros(z.shape, dtype=torch.float64, device=z.device)
+    if incidence:
+        dzde, dzdn = (t.double() for t in _gradient(z, grid, nodata))
+    for (az, el), w, t in zip(suns, weights, terms):
+        shade, _ = _shadow(z, t, nodata, tol, ws, nbytes)
+        term = _cos_incidence(dzde, dzdn, az, el) * w if incidence else torch.full_like(total, w)
+        total = total + torch.where(shade == 2, torch.zeros_like(term), term)
+    return _back(as_numpy, torch.where(_valid_cells(z, nodata), total, torch.full_like(total, float("nan"))).float())
