@@ -754,7 +754,43 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   in this order, every operation rounded by itself (8 xres and 8 yres are one product each); invalid cells get
  *   (float)nodata in both outputs.  One lane per cell; bit-identical to its numpy statement.
  *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers; gw, gh >= 1, gw * gh < 2^31; finite
- *   resolutions > 0; dzde and dzdn distinct from dsm and from each other. */
+ *   resolutions > 0; dzde and dzdn distinct from dsm and from each other.
+ *
+ * Horizon (csrc/dsm_horizon.hip).
+ * smvs_dsm_horizon: for n_dirs azimuths in one call, the tangent of the elevation angle of the highest thing that stands
+ *   towards the azimuth, for every cell.  dsm (gh, gw) float32 (device), read only.
+ *   Validity and heights.  A cell is valid iff it is finite, != (float)nodata and |z| <= 32768.  q = llrint((double)z 256),
+ *   halves to even: the height in units of 2^-8 m, as in the registration.
+ *   Directions.  dirs is a HOST array of n_dirs x 4 doubles (ucol, urow, a, b).  (ucol, urow) is the horizontal direction
+ *   TOWARDS the azimuth in cell-index units (columns run east, rows south), exactly as for smvs_dsm_shadow; (a, b) =
+ *   (256 xres sin A, -256 yres cos A).  There is no trigonometry in the library: dsm.horizon_terms derives the four doubles.
+ *   Lines.  The orientation, s(i) = floor(m i + 0.5), the line L of a cell and the order "towards the azimuth" are those of
+ *   smvs_dsm_shadow with "sun" read as "azimuth": row-major iff |urow| >= |ucol| (a tie included), m = ucol / urow,
+ *   L = c - s(r), ascending r if urow < 0, descending r if urow > 0; otherwise column-major, m = urow / ucol, L = r - s(c),
+ *   ascending c if ucol < 0, descending c if ucol > 0.  A cell's predecessors are the cells of its line that come before it
+ *   in that order: they lie towards the azimuth.
+ *   Positions.  P(r, c) = llrint(a (double)c + b (double)r), halves to even: two products and their sum, each rounded by
+ *   itself, then the rint.  P is the position along the azimuth in units of 2^-8 m.
+ *   The tangent.  For a valid cell i, T(i) is the maximum over the VALID predecessors j of the exact rational
+ *   (q_j - q_i) / (P_j - P_i), whose denominator is positive, and tan_h = (float)((double)(q_j - q_i) / (double)(P_j - P_i))
+ *   for a j that attains it: one IEEE float64 division, then one conversion.  Equal rationals give equal bits, so the
+ *   choice among tied j does not matter.  With no valid predecessor tan_h = -inf; at an invalid cell tan_h = the quiet NaN
+ *   0x7fc00000.  Invalid cells neither occlude nor receive.  tan_h is (n_dirs, gh, gw) float32 (device), in the order of dirs.
+ *   Exactness.  The maximum is the tangent from i to the upper convex hull of its predecessors, kept as a stack along the
+ *   line: pop the top while the slope from i to the element under it is >= the slope from i to the top, read T off the
+ *   top, push i.  Every comparison that prunes a candidate is an exact int64 cross-multiplication, (q1 - q_i)(P2 - P_i)
+ *   against (q2 - q_i)(P1 - P_i), never a comparison of rounded quotients, and the limits below keep every product below
+ *   2^62: the result equals the O(n^2) maximum over all pairs.  The bits are equal from run to run, on any stream, for any
+ *   batching of the directions, and equal to the numpy statement of this rule.  The reach is unbounded.
+ *   The entry writes every element of tan_h; every workspace word a kernel reads was written by a kernel of the same call
+ *   (a workspace full of anything will do); no atomics, no host synchronisation.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call): non-null dsm, dirs, tan_h and workspace; gw, gh >= 1,
+ *   gw * gh < 2^31; 1 <= n_dirs <= 64; every direction finite; (ucol, urow) not (0, 0); a ucol >= 0 and b urow >= 0; the
+ *   term along the scan, |b| if row-major else |a|, >= 4 (this keeps the rounded P strictly monotone along a line: cells
+ *   of at least 1/64 m); |a| gw + |b| gh < 2^37 (with |q_j - q_i| <= 2^24 this bounds the products); dsm, tan_h and
+ *   workspace do not overlap; workspace: smvs_dsm_horizon_workspace_bytes(gw, gh, n_dirs) bytes (0 = unsupported
+ *   arguments): 8 bytes per cell and 8 more per cell and direction, because all directions of a call are in flight at once;
+ *   a caller short of memory passes fewer directions per call, the bits do not depend on it. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -808,6 +844,11 @@ int smvs_dsm_shadow(const float* dsm, int gw, int gh, float nodata,
                     unsigned char* shade, float* depth, void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_gradient(const float* dsm, int gw, int gh, float nodata, double xres, double yres,
                       float* dzde, float* dzdn, void* stream);
+size_t smvs_dsm_horizon_workspace_bytes(int gw, int gh, int n_dirs);
+int smvs_dsm_horizon(const float* dsm, int gw, int gh, float nodata,
+                     const double* dirs /* HOST, n_dirs x 4: ucol, urow, a, b */, int n_dirs,
+                     float* tan_h /* device, (n_dirs, gh, gw) */,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

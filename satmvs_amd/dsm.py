@@ -42,6 +42,14 @@ and the sun over a DSM: cast shadows for a given sun, shaded relief, and exposur
     exposure = sun_exposure(dsm, grid, suns, weights)          # sum of w cos(incidence) over the suns that reach a cell
     per_roof = label_stats(labels, n, values=exposure)         # "how much sun does this roof get"
 
+and horizon maps, which turn every further sun (or satellite) into a comparison per cell and give the sky-view factor:
+
+    azimuths = horizon_azimuths(16)                            # 0, 22.5, ... degrees clockwise from north
+    tan_h = horizon(dsm, grid, azimuths)                       # (16, gh, gw) float32: tangent of the horizon's elevation angle
+    svf = sky_view_factor(tan_h)                               # isotropic sky view of a horizontal surface, in [0, 1]
+    seen = horizon_lit(tan_h, azimuths, azimuth=100.0, elevation=35.0)   # 0 no height, 1 seen from there, 2 hidden
+    exposure = sun_exposure_from_horizon(dsm, grid, tan_h, azimuths, suns, weights)   # sun_exposure without a scan per sun
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -72,6 +80,8 @@ destination cell over a table of up to 64 layers, float64 sums in the list's ord
 smvs_dsm_shadow is an exclusive running maximum of z - tan(elevation) (distance towards the sun) along sheared lines of
 the grid, a lane per line, cut into bands with an exact carry, the east-west directions between tile transposes through LDS;
 smvs_dsm_gradient is Horn's 3 x 3 gradient, one lane per cell.
+smvs_dsm_horizon walks the same sheared lines with the upper convex hull of the cells passed so far as a stack of links in
+memory, slopes compared by exact int64 cross-multiplication, a lane per (direction, line), all directions of a call side by side.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -1526,3 +1536,189 @@ def sun_exposure(dsm, grid, suns, weights=None, incidence=True, nodata=-999.0, t
         term = _cos_incidence(dzde, dzdn, az, el) * w if incidence else torch.full_like(total, w)
         total = total + torch.where(shade == 2, torch.zeros_like(term), term)
     return _back(as_numpy, torch.where(_valid_cells(z, nodata), total, torch.full_like(total, float("nan"))).float())
+
+
+# ---- horizon maps: tangents towards a list of azimuths, sky view, any-sun visibility ---------------------------------------------
+MAX_HORIZON_DIRS = 64                                             # directions of one smvs_dsm_horizon call
+HORIZON_INTERP = ("linear", "nearest")
+
+
+def _azimuths_checked(azimuths):
+    try:
+        out = [float(a) for a in azimuths]
+    except TypeError:
+        raise ValueError("azimuths must be a list of numbers [degrees clockwise from north], got %r" % (azimuths,)) from None
+    if not out:
+        raise ValueError("at least one azimuth is needed")
+    for a in out:
+        if not math.isfinite(a):
+            raise ValueError("azimuth must be finite [degrees clockwise from north], got %r" % a)
+    return out
+
+
+def horizon_terms(grid, azimuth):
+    """The four doubles smvs_dsm_horizon takes for `azimuth` [degrees clockwise from north, any finite value] over `grid`: with
+    sA, cA = sin, cos(radians(azimuth)), ucol = sA / xres, urow = -cA / yres (the direction towards the azimuth in cells; rows
+    run south), a = 256 xres sA, b = -256 yres cA (the position along the azimuth in units of 2^-8 m, per column and per row).
+    -> (ucol, urow, a, b)."""
+    azimuth = _finite(azimuth, "azimuth")
+    _grid_checked(grid, "grid")
+    xres, yres = float(grid.xres), float(grid.yres)
+    sA, cA = math.sin(math.radians(azimuth)), math.cos(math.radians(azimuth))
+    return sA / xres, -cA / yres, 256.0 * xres * sA, -256.0 * yres * cA
+
+
+def horizon_azimuths(n):
+    """n evenly spaced azimuths [degrees] starting at 0 (north), clockwise."""
+    n = _int_checked(n, "n", 1, 1 << 20)
+    return [360.0 * i / n for i in range(n)]
+
+
+def _horizon_dirs(grid, azimuths):
+    """(K, 4) float64 host array of horizon_terms, checked against the limits of smvs_dsm_horizon before any device work."""
+    dirs = np.array([horizon_terms(grid, a) for a in azimuths], dtype=np.float64).reshape(-1, 4)
+    for az, (ucol, urow, a, b) in zip(azimuths, dirs):
+        if (abs(b) if abs(urow) >= abs(ucol) else abs(a)) < 4.0:
+            raise ValueError("the grid's resolution is too fine for a horizon towards %r: cells below 1/64 m" % az)
+        if not abs(a) * grid.width + abs(b) * grid.height < 2.0 ** 37:
+            raise ValueError("the grid is too long for a horizon towards %r: its extent must stay below 2^29 m" % az)
+    return dirs
+
+
+def horizon(dsm, grid, azimuths, nodata=-999.0):
+    """Horizon maps of a DSM (include/satmvs.h smvs_dsm_horizon, DESIGN.md section 9, "Horizon"): for every azimuth of the list
+    [degrees clockwise from north, any finite values, at least one] and every cell, the tangent of the elevation angle of the
+    highest thing that stands towards the azimuth, along the same sheared lines of cells as cast_shadows, with unbounded reach:
+    the maximum of (z_j - z) / (distance towards the azimuth) over the valid cells j of the line that lie towards it, heights
+    and distances in units of 2^-8 m, exact.  -inf where nothing stands towards the azimuth, NaN at invalid cells (not finite,
+    nodata, or beyond +-32768 m).  More than 64 azimuths go in chunks of 64; the bits do not depend on the chunking.  dsm
+    (grid.height, grid.width) of any real dtype (taken as float32), numpy or a device tensor.
+    -> (K, gh, gw) float32; numpy if the DSM came as numpy, a device tensor otherwise."""
+    azimuths = _azimuths_checked(azimuths)
+    dirs = _horizon_dirs(grid, azimuths)
+    dsm = _dsm_converted(dsm, grid)
+    z, as_numpy = _to_device(dsm, torch.float32)
+    gh, gw = z.shape
+    K = len(azimuths)
+    nbytes = _lib.load().smvs_dsm_horizon_workspace_bytes(gw, gh, min(K, MAX_HORIZON_DIRS))
+    if nbytes == 0:
+        raise ValueError("unsupported horizon: %d x %d cells" % (gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    out = torch.empty((K, gh, gw), dtype=torch.float32, device=z.device)
+    for k0 in range(0, K, MAX_HORIZON_DIRS):
+        n = min(MAX_HORIZON_DIRS, K - k0)
+        _call(z.device, "smvs_dsm_horizon", z, gw, gh, float(nodata), np.ascontiguousarray(dirs[k0:k0 + n]), n, out[k0:k0 + n], ws, nbytes)
+    return _back(as_numpy, out)
+
+
+def _tan_h_checked(tan_h, azimuths=None):
+    """(K, gh, gw) float32 maps as a tensor where they are (numpy: on the host), and whether they came as numpy."""
+    as_numpy = not isinstance(tan_h, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(tan_h)) if as_numpy else tan_h
+    if t.ndim != 3 or t.shape[0] < 1 or t.dtype != torch.float32:
+        raise ValueError("tan_h is (K, gh, gw) float32 with K >= 1, got %s of shape %s" % (t.dtype, tuple(t.shape)))
+    if azimuths is not None and len(azimuths) != t.shape[0]:
+        raise ValueError("one azimuth per horizon map: %d azimuths, %d maps" % (len(azimuths), t.shape[0]))
+    return t, as_numpy
+
+
+def sky_view_factor(tan_h):
+    """The isotropic sky-view factor of a horizontal surface from horizon maps: the float64 mean, in the list's order, of
+    1 / (1 + max(t, 0)^2), which is cos^2 of the horizon angle clamped at the horizontal.  1 under an open horizon, NaN at
+    invalid cells.  -> (gh, gw) float64, numpy or tensor as tan_h came."""
+    t, as_numpy = _tan_h_checked(tan_h)
+    total = torch.zeros(t.shape[1:], dtype=torch.float64, device=t.device)
+    for k in range(t.shape[0]):
+        x = torch.clamp(t[k].double(), min=0.0)
+        total = total + 1.0 / (1.0 + x * x)
+    svf = total / float(t.shape[0])
+    svf = torch.where(torch.isnan(t).any(dim=0), torch.full_like(svf, float("nan")), svf)
+    return svf.numpy() if as_numpy else svf
+
+
+def _horizon_bracket(azimuths, azimuth, interp):
+    """[(index, weight)] of the listed azimuths an asked one takes its tangent from: itself (the first listed, weight None)
+    if it is in the list modulo 360; else, for "linear", the nearest listed one below and the nearest above around the circle
+    with weights 1 - w and w, w = (asked - below) / (above - below); for "nearest", the one at the least distance around the
+    circle (the earlier of two at equal distance)."""
+    mods = [a % 360.0 for a in azimuths]
+    x = azimuth % 360.0
+    if x in mods:
+        return [(mods.index(x), None)]
+    if interp == "nearest":
+        dist = [abs((m - x + 180.0) % 360.0 - 180.0) for m in mods]
+        return [(dist.index(min(dist)), None)]
+    below = [(m, i) for i, m in enumerate(mods) if m < x] or [(max(mods) - 360.0, mods.index(max(mods)))]
+    above = [(m, i) for i, m in enumerate(mods) if m > x] or [(min(mods) + 360.0, mods.index(min(mods)))]
+    (lo, i), (hi, j) = max(below, key=lambda p: (p[0], -p[1])), min(above)
+    w = (x - lo) / (hi - lo)
+    return [(i, 1.0 - w), (j, w)]
+
+
+def _interp_checked(interp):
+    if interp not in HORIZON_INTERP:
+        raise ValueError("interp must be one of %s, got %r" % (HORIZON_INTERP, interp))
+    return interp
+
+
+def _horizon_tangent(t, azimuths, azimuth, interp):
+    """The float64 tangent towards `azimuth` from checked maps, as _horizon_bracket says (NaN at invalid cells)."""
+    pick = _horizon_bracket(azimuths, azimuth, interp)
+    if len(pick) == 1:
+        return t[pick[0][0]].double()
+    (i, wi), (j, wj) = pick
+    return wi * t[i].double() + wj * t[j].double()
+
+
+def _horizon_lit(t, azimuths, azimuth, elevation, interp):
+    """horizon_lit on a checked tensor -> uint8 tensor."""
+    hidden = _horizon_tangent(t, azimuths, azimuth, interp) > math.tan(math.radians(elevation))
+    code = torch.where(hidden, 2, 1).to(torch.uint8)
+    return torch.where(torch.isnan(t[0]), torch.zeros_like(code), code)
+
+
+def horizon_lit(tan_h, azimuths, azimuth, elevation, interp="linear"):
+    """Whether a source at `azimuth` [degrees clockwise from north, any finite value] and 0 < `elevation` < 90 degrees (the
+    sun, a satellite) sees each cell, from the horizon maps tan_h of the listed `azimuths`: a cell is hidden iff T >
+    tan(elevation), T = (1 - w) T_below + w T_above in float64 between the two listed azimuths that bracket the asked one around
+    the circle (w the asked azimuth's share of the way), or with interp="nearest" the map of the nearest listed azimuth; an
+    asked azimuth that is in the list (modulo 360) takes that direction's own map bit for bit.
+    -> (gh, gw) uint8 with the codes of cast_shadows: 0 invalid, 1 lit, 2 hidden; numpy or tensor as tan_h came."""
+    azimuths = _azimuths_checked(azimuths)
+    azimuth, elevation = _sun_checked(azimuth, elevation)
+    _interp_checked(interp)
+    t, as_numpy = _tan_h_checked(tan_h, azimuths)
+    code = _horizon_lit(t, azimuths, azimuth, elevation, interp)
+    return code.numpy() if as_numpy else code
+
+
+def sun_exposure_from_horizon(dsm, grid, tan_h, azimuths, suns, weights=None, incidence=True, nodata=-999.0, interp="linear"):
+    """sun_exposure with every sun's `lit` taken from horizon_lit(tan_h, azimuths, ...) instead of a pass of cast_shadows: the
+    float64 sum, in the list's order, of w lit (cos i if incidence else 1); the gradient is computed once and no sun scans the
+    DSM.  tan_h, azimuths: horizon(dsm, grid, azimuths) of the same DSM; suns, weights, incidence as in sun_exposure.
+    -> (gh, gw) float32, NaN at invalid cells; numpy if the DSM came as numpy, a device tensor otherwise."""
+    azimuths = _azimuths_checked(azimuths)
+    _interp_checked(interp)
+    try:
+        suns = [_sun_checked(*s) for s in suns]
+    except TypeError:
+        raise ValueError("suns must be a list of (azimuth, elevation) pairs, got %r" % (suns,)) from None
+    if not suns:
+        raise ValueError("sun_exposure_from_horizon needs at least one sun")
+    weights = [1.0] * len(suns) if weights is None else [_finite(w, "a weight") for w in weights]
+    if len(weights) != len(suns):
+        raise ValueError("one weight per sun: %d suns, %d weights" % (len(suns), len(weights)))
+    t, _ = _tan_h_checked(tan_h, azimuths)
+    if tuple(t.shape[1:]) != (grid.height, grid.width):
+        raise ValueError("tan_h shape %s differs from the grid's (%d, %d)" % (tuple(t.shape[1:]), grid.height, grid.width))
+    z, as_numpy = _relief_input(dsm, grid)
+    t = t.to(z.device)
+    total = torch.zeros(z.shape, dtype=torch.float64, device=z.device)
+    if incidence:
+        dzde, dzdn = (g.double() for g in _gradient(z, grid, nodata))
+    for (az, el), w in zip(suns, weights):
+        hidden = _horizon_tangent(t, azimuths, az, interp) > math.tan(math.radians(el))      # horizon_lit == 2 (invalid cells: below)
+        term = _cos_incidence(dzde, dzdn, az, el) * w if incidence else torch.full_like(total, w)
+        total = total + torch.where(hidden, torch.zeros_like(term), term)
+    ok = _valid_cells(z, nodata) & ~torch.isnan(t[0])
+    return _back(as_numpy, torch.where(ok, total, torch.full_like(total, float("nan"))).float())
