@@ -790,7 +790,42 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   of at least 1/64 m); |a| gw + |b| gh < 2^37 (with |q_j - q_i| <= 2^24 this bounds the products); dsm, tan_h and
  *   workspace do not overlap; workspace: smvs_dsm_horizon_workspace_bytes(gw, gh, n_dirs) bytes (0 = unsupported
  *   arguments): 8 bytes per cell and 8 more per cell and direction, because all directions of a call are in flight at once;
- *   a caller short of memory passes fewer directions per call, the bits do not depend on it. */
+ *   a caller short of memory passes fewer directions per call, the bits do not depend on it.
+ *
+ * Outlines (csrc/dsm_outline.hip).  labels (gh, gw) int32 (device), read only.  A cell has label k iff its value is k and
+ *   1 <= k <= n; every other value and every cell off the grid counts as 0.  Lattice corner (x, y), 0 <= x <= gw,
+ *   0 <= y <= gh, is the upper-left corner of cell (row y, col x).  Side s of a cell with label k (s = 0 south, 1 east,
+ *   2 north, 3 west) is a boundary edge of k iff the cell across it does not have label k; it is directed with its own cell on
+ *   the left, north up: south side heading east, east side north, north side west, west side south.  The successor of edge
+ *   (A, s) with heading h: B = A + h, C = B + one step across side s away from A; side (s + 3) % 4 of C if C has label k, else
+ *   side s of B if B has label k, else side (s + 1) % 4 of A (right first: cells of one label that meet at a corner are
+ *   joined).  The successor is a permutation of the boundary edges and its cycles are the rings.  A ring's vertices are the
+ *   tail corners of those of its edges whose predecessor has another side; the list starts at the ring's smallest corner by
+ *   (y, x), which it passes once, and follows the ring: an exterior ring leaves it heading south (counter-clockwise north up),
+ *   a hole heading east (clockwise).  Rings are ordered by (label, start y, start x).
+ * smvs_dsm_outline_count: counts (device, 3 ints) gets n_edges, n_rings, n_vertices, or -1, -1, -1 if the labels hold more
+ *   than max_edges boundary edges or an index read back from the workspace was out of range (a damaged workspace: never on a
+ *   sound device).  max_edges == 0 counts the edges only (n_edges, 0, 0) in a workspace of
+ *   smvs_dsm_outline_workspace_bytes(gw, gh, 0) bytes; the caller reads n_edges and calls again with max_edges = n_edges and a
+ *   workspace of that size, which then holds the rings.  n == 0 clears counts without a launch.  The doubling runs
+ *   ceil(log2(max_edges)) rounds whatever the workspace holds.  No host synchronisation.
+ * smvs_dsm_outline_write: with the three counts read from the device and the workspace as the second count call left it:
+ *   ring_label[r] int32; area2[r] int64 the shoelace sum north up in cells (> 0 exterior, < 0 hole); edges[2 r ..] int32 the
+ *   unit edges heading E or W and those heading N or S; offset[r] int32, n_rings + 1 entries, into vertices; first_ring[k]
+ *   int32, n + 1 entries, the first ring of label k + 1 (a label without a cell has none: first_ring[k] == first_ring[k + 1]);
+ *   vertices[2 v ..] int32 x, y.  offset[n_rings] is n_vertices, or -1 if the counts differ from the workspace's or an index
+ *   was out of range.  All three counts 0: first_ring and offset[0] are cleared without a launch.  Integer atomics (add)
+ *   only: everything depends on labels and n alone, equal bits from run to run.
+ * smvs_dsm_burn: out (gh, gw) int32 is zeroed; every vertical edge (x, y0) - (x, y1) between consecutive vertices of a ring
+ *   (the last to the first) XORs ring_label[r] into out[row, max(x, 0)] for min(y0, y1) <= row < max(y0, y1), rows clipped to
+ *   the grid, nothing for x >= gw; then every row takes its running XOR: the even-odd rule at cell centres.  Horizontal edges
+ *   do nothing.  flag (device, one int): bit 0 an edge whose ends differ in both coordinates, bit 1 an offset table that is
+ *   not 0 = offset[0] <= ... <= offset[n_rings] = n_vertices.  Integer atomics (xor) only.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers (the ring outputs may be null when the counts are 0,
+ *   the burn's inputs when n_rings or n_vertices is 0); gw, gh >= 1; gw * gh < 2^29 (outline; 4 gw gh edges fit an int32) or
+ *   < 2^31 (burn); n >= 0; 0 <= max_edges <= 4 gw gh; 1 <= n_rings, n_vertices <= n_edges or all three 0; outputs and
+ *   workspace distinct from the inputs and from each other; workspace: smvs_dsm_outline_workspace_bytes(gw, gh, max_edges)
+ *   bytes (0 = unsupported arguments): 5 bytes per corner and 61 per edge. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -849,6 +884,14 @@ int smvs_dsm_horizon(const float* dsm, int gw, int gh, float nodata,
                      const double* dirs /* HOST, n_dirs x 4: ucol, urow, a, b */, int n_dirs,
                      float* tan_h /* device, (n_dirs, gh, gw) */,
                      void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_outline_workspace_bytes(int gw, int gh, int max_edges);
+int smvs_dsm_outline_count(const int* labels, int gw, int gh, int n, int max_edges, int* counts,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n, int n_edges, int n_rings, int n_vertices,
+                           int* ring_label, long long* area2, int* edges, int* offset, int* first_ring, int* vertices,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_burn(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
+                  int gw, int gh, int* out, int* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,668 @@
+// dsm_outline.hip -- the outlines of the labels of a label map as oriented rings of lattice corners, and rings burnt back
+// into a label map ("Outlines"; include/satmvs.h for the rules).
+//
+//   smvs_dsm_outline_count  labels (gh, gw) int32 -> n_edges, n_rings, n_vertices on the device, the rings in the workspace
+//   smvs_dsm_outline_write  the ring table and the vertex list into buffers the caller sized from those counts
+//   smvs_dsm_burn           rings -> labels (gh, gw) int32 by the even-odd rule at cell centres
+//
+// A boundary edge leaves exactly one lattice corner (its tail) with one of four headings, so the edges are kept per corner: a
+// lane per corner builds the 4-bit mask of the edges that leave it (bit s = the edge on side s of its own cell), and an
+// exclusive scan of the masks' bit counts (three levels of 2048-element blocks, as in dsm_label.hip) numbers the edges in the
+// order (tail corner y, x, side).  The successor of an edge leaves the corner the edge arrives at and is chosen there, right
+// first, from the two cells ahead; every edge writes its own number at its successor's place, which gives the predecessor
+// array: a permutation of the edges whose cycles are the rings.
+// One pointer doubling over the predecessors carries a 64-bit word (key << 32 | steps): key = 2 * tail corner + (side == 0),
+// steps = how many edges back the lowest key of the window stands.  After ceil(log2(n_edges)) rounds the window of every edge
+// covers its whole ring, so the word holds the ring's lowest key (the ring's name: its start corner and whether it is a hole)
+// and the edge's rank from the start edge.  The lowest corner of a ring is passed once, so the name is unique and the start
+// edge is the one edge of the ring with 0 steps.  Start edges are numbered by a second scan (corner order), sorted stably by
+// label (one split per bit of n, each a scan), every edge goes to (first edge of its ring + rank), and a last scan over the
+// edges in that order numbers the vertices (the edges whose predecessor has another side).
+// Integer atomics only (add, xor): the bits do not depend on their order.
+//
+// Every loop is bounded by a number the host knows: the doubling runs ceil(log2(max_edges)) rounds, the sort one split per bit
+// of n, the burn at most gh rows per edge.  Every index read from the workspace is checked against its array before it is
+// used; one that is out of range (a damaged workspace) sets the error word, the lane goes on with its own index, and the
+// counts come back as -1 (smvs_dsm_outline_count) or offset[n_rings] as -1 (smvs_dsm_outline_write).
+#include <limits.h>
+#include <stdint.h>
+
+#include "dsm_common.h"
+#include "smvs_host.h"
+
+namespace smvs {
+
+constexpr int OL_THREADS = 256, OL_PER_THREAD = 8, OL_BLOCK = OL_THREADS * OL_PER_THREAD;    // 2048 elements per workgroup of a scan
+enum { OL_NE = 0, OL_NR = 1, OL_NV = 2, OL_ERR = 3, OL_TOTAL = 4 };                          // the workspace's tail words
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ int ol_label(const int* __restrict__ L, int gw, int gh, int n, int x, int y)
+{
+    if ((unsigned)x >= (unsigned)gw || (unsigned)y >= (unsigned)gh) return 0;
+    const int v = L[(size_t)y * gw + x];
+    return (unsigned)v - 1u < (unsigned)n ? v : 0;
+}
+
+// The cell whose side s leaves corner (x, y): s = 0 south side of NE, 1 east side of NW, 2 north side of SW, 3 west side of SE.
+__device__ __forceinline__ void ol_cell_of(int x, int y, int s, int& cx, int& cy)
+{
+    cx = (s == 0 || s == 3) ? x : x - 1;
+    cy = (s == 2 || s == 3) ? y : y - 1;
+}
+
+__device__ __forceinline__ int ol_limit(const int* tail, unsigned cap, int which)
+{
+    const int v = tail[which];
+    return v < 0 ? 0 : (unsigned)v > cap ? (int)cap : v;
+}
+
+// ---- the scan ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int ol_block_exclusive(int v, int& total)
+{
+    __shared__ int wave_sum[OL_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < OL_THREADS / 64; ++k) {
+        const int s = wave_sum[k];
+        if (k < wave) before += s;
+        total += s;
+    }
+    return before + inc - v;
+}
+
+// In-place exclusive scan of the first n elements of a in blocks of 2048 (n = min(*n_dev, cap), or cap without n_dev); the
+// block totals go one level up.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_scan(int* __restrict__ a, unsigned cap, const int* __restrict__ n_dev, int* __restrict__ sums)
+{
+    unsigned n = cap;
+    if (n_dev) n = (unsigned)max(0, min(*n_dev, (int)min(cap, (unsigned)INT_MAX)));
+    const unsigned c0 = blockIdx.x * (unsigned)OL_BLOCK + threadIdx.x * (unsigned)OL_PER_THREAD;
+    int v[OL_PER_THREAD], cnt = 0;
+#pragma unroll
+    for (int k = 0; k < OL_PER_THREAD; ++k) {
+        v[k] = (c0 < n && (unsigned)k < n - c0) ? a[c0 + k] : 0;
+        cnt += v[k];
+    }
+    int total;
+    int at = ol_block_exclusive(cnt, total);
+#pragma unroll
+    for (int k = 0; k < OL_PER_THREAD; ++k) {
+        if (c0 < n && (unsigned)k < n - c0) a[c0 + k] = at;
+        at += v[k];
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(OL_THREADS)
+void ol_scan_add(int* __restrict__ a, unsigned cap, const int* __restrict__ n_dev, const int* __restrict__ s1, const int* __restrict__ s2)
+{
+    unsigned n = cap;
+    if (n_dev) n = (unsigned)max(0, min(*n_dev, (int)min(cap, (unsigned)INT_MAX)));
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (i >= n) return;
+    a[i] += s1[i / OL_BLOCK] + s2[i / OL_BLOCK / OL_BLOCK];
+}
+
+// a[0 .. n) <- its exclusive prefix sums, *total <- the sum.  cap < 2^31, so the third level is one block.
+static int ol_scan_exclusive(int* a, unsigned cap, const int* n_dev, int* s1, int* s2, int* total, hipStream_t s, const char* what)
+{
+    const unsigned nb1 = (cap + OL_BLOCK - 1) / OL_BLOCK, nb2 = (nb1 + OL_BLOCK - 1) / OL_BLOCK;
+    int rc;
+    hipLaunchKernelGGL(ol_scan, dim3(nb1), dim3(OL_THREADS), 0, s, a, cap, n_dev, s1);
+    if ((rc = check_launch(what))) return rc;
+    hipLaunchKernelGGL(ol_scan, dim3(nb2), dim3(OL_THREADS), 0, s, s1, nb1, (const int*)nullptr, s2);
+    if ((rc = check_launch(what))) return rc;
+    hipLaunchKernelGGL(ol_scan, dim3(1), dim3(OL_THREADS), 0, s, s2, nb2, (const int*)nullptr, total);
+    if ((rc = check_launch(what))) return rc;
+    hipLaunchKernelGGL(ol_scan_add, dim3((cap + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, a, cap, n_dev, (const int*)s1, (const int*)s2);
+    return check_launch(what);
+}
+
+// ---- count -------------------------------------------------------------------------------------------------------------------
+// One lane per corner: the mask of the edges that leave it and their number.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_corners(const int* __restrict__ L, int gw, int gh, int n, unsigned nc, unsigned char* __restrict__ cmask, int* __restrict__ cbase)
+{
+    const unsigned t = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (t >= nc) return;
+    const int x = (int)(t % (unsigned)(gw + 1)), y = (int)(t / (unsigned)(gw + 1));
+    const int nw = ol_label(L, gw, gh, n, x - 1, y - 1), ne = ol_label(L, gw, gh, n, x, y - 1);
+    const int sw = ol_label(L, gw, gh, n, x - 1, y), se = ol_label(L, gw, gh, n, x, y);
+    const int m = (ne != 0 && se != ne ? 1 : 0) | (nw != 0 && ne != nw ? 2 : 0) | (sw != 0 && nw != sw ? 4 : 0) | (se != 0 && sw != se ? 8 : 0);
+    cmask[t] = (unsigned char)m;
+    cbase[t] = __popc(m);
+}
+
+// One lane per corner, every edge that leaves it: its tail, its first doubling word, and its number at its successor's place.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_edges(const int* __restrict__ L, int gw, int gh, int n, unsigned nc, const unsigned char* __restrict__ cmask,
+              const int* __restrict__ cbase, unsigned cap, int* tail, int* __restrict__ ecorner, u64* __restrict__ val,
+              int* __restrict__ pred, unsigned char* __restrict__ eside)
+{
+    const unsigned t = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (t >= nc) return;
+    if (tail[OL_NE] < 0 || (unsigned)tail[OL_NE] > cap) {    // more edges than the caller made room for
+        if (t == 0) atomicOr(tail + OL_ERR, 1);
+        return;
+    }
+    const unsigned ne = (unsigned)tail[OL_NE];
+    const int m = cmask[t];
+    if (!m) return;
+    const int x = (int)(t % (unsigned)(gw + 1)), y = (int)(t / (unsigned)(gw + 1));
+    const int hx[4] = {1, 0, -1, 0}, hy[4] = {0, -1, 0, 1};  // the heading of side s; the way out across side s is heading (s + 3) % 4
+    unsigned j = (unsigned)cbase[t];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        if (!((m >> s) & 1)) continue;
+        int ax, ay;
+        ol_cell_of(x, y, s, ax, ay);
+        const int k = ol_label(L, gw, gh, n, ax, ay);
+        const int bx = ax + hx[s], by = ay + hy[s], cx = bx + hx[(s + 3) & 3], cy = by + hy[(s + 3) & 3];
+        int s2 = (s + 1) & 3;                                // left, on the cell itself
+        if (ol_label(L, gw, gh, n, cx, cy) == k) s2 = (s + 3) & 3;           // right first, on the cell diagonally ahead
+        else if (ol_label(L, gw, gh, n, bx, by) == k) s2 = s;                // straight on, on the cell ahead
+        const unsigned h = (unsigned)((y + hy[s]) * (gw + 1) + x + hx[s]);   // the corner the edge arrives at: on the lattice
+        const int hm = cmask[h];
+        const unsigned j2 = (unsigned)cbase[h] + (unsigned)__popc(hm & ((1 << s2) - 1));
+        if (j >= ne || j2 >= ne || !((hm >> s2) & 1)) {
+            atomicOr(tail + OL_ERR, 1);
+        } else {
+            ecorner[j] = (int)t;
+            val[j] = (u64)(2u * t + (s == 0 ? 1u : 0u)) << 32;
+            pred[j2] = (int)j;
+            eside[j2] = (unsigned char)(s2 | (s2 != s ? 4 : 0));
+        }
+        ++j;
+    }
+}
+
+// One round of the doubling: the window of an edge grows by the window of the edge `add` places back.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_double(const int* __restrict__ pin, const u64* __restrict__ vin, int* __restrict__ pout, u64* __restrict__ vout,
+               unsigned add, unsigned cap, int* tail)
+{
+    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    const unsigned ne = (unsigned)ol_limit(tail, cap, OL_NE);
+    if (j >= ne) return;
+    unsigned p = (unsigned)pin[j];
+    if (p >= ne) { atomicOr(tail + OL_ERR, 1); p = j; }
+    unsigned q = (unsigned)pin[p];
+    if (q >= ne) { atomicOr(tail + OL_ERR, 1); q = j; }
+    const u64 a = vin[j], b = vin[p] + add;
+    vout[j] = a < b ? a : b;
+    pout[j] = (int)q;
+}
+
+// Start edges flagged for the scan that numbers the rings; the vertices counted.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_starts(const u64* __restrict__ val, const unsigned char* __restrict__ eside, int* __restrict__ rscan, unsigned cap, int* tail)
+{
+    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    const unsigned ne = (unsigned)ol_limit(tail, cap, OL_NE);
+    bool turn = false;
+    if (j < ne) {
+        rscan[j] = (unsigned)val[j] == 0u;
+        turn = (eside[j] & 4) != 0;
+    }
+    const int cnt = __popcll(__ballot(turn));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(tail + OL_NV, cnt);
+}
+
+__global__ void ol_counts_out(const int* __restrict__ tail, int* __restrict__ counts)
+{
+    if (threadIdx.x < 3) counts[threadIdx.x] = tail[OL_ERR] ? -1 : tail[threadIdx.x];
+}
+
+// ---- write -------------------------------------------------------------------------------------------------------------------
+struct OlRings { int *label, *edges; long long* area2; };   // the per-ring outputs the kernels write through one argument
+
+// The counts the caller sized its buffers from must be the ones the workspace holds; every start edge hands its label and
+// itself to the sort, at its number in corner order.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_ring_init(const int* __restrict__ L, int gw, int gh, int n, const u64* __restrict__ val, const int* __restrict__ rscan,
+                  const int* __restrict__ ecorner, const unsigned char* __restrict__ eside, unsigned ne, unsigned nr, unsigned nv,
+                  unsigned nc, int* tail, int* __restrict__ skey, int* __restrict__ sval)
+{
+    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (j == 0 && ((unsigned)tail[OL_NE] != ne || (unsigned)tail[OL_NR] != nr || (unsigned)tail[OL_NV] != nv)) atomicOr(tail + OL_ERR, 1);
+    if (j >= ne || (unsigned)val[j] != 0u) return;
+    const unsigned q = (unsigned)rscan[j], t = (unsigned)ecorner[j];
+    if (q >= nr || t >= nc) { atomicOr(tail + OL_ERR, 1); return; }
+    int ax, ay;
+    ol_cell_of((int)(t % (unsigned)(gw + 1)), (int)(t / (unsigned)(gw + 1)), eside[j] & 3, ax, ay);
+    skey[q] = ol_label(L, gw, gh, n, ax, ay);
+    sval[q] = (int)j;
+}
+
+__global__ __launch_bounds__(OL_THREADS)
+void ol_sort_flag(const int* __restrict__ skey, int* __restrict__ spos, unsigned nr, int bit)
+{
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (i < nr) spos[i] = !(((unsigned)skey[i] >> bit) & 1u);
+}
+
+// The stable split on one bit: the keys without the bit keep their order in front, the others theirs behind.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_sort_scatter(const int* __restrict__ kin, const int* __restrict__ vin, const int* __restrict__ spos, int* tail,
+                     int* __restrict__ kout, int* __restrict__ vout, unsigned nr, int bit)
+{
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (i >= nr) return;
+    const int k = kin[i];
+    const unsigned before = (unsigned)spos[i], zeros = (unsigned)tail[OL_TOTAL];
+    unsigned d = (((unsigned)k >> bit) & 1u) ? zeros + (i - before) : before;
+    if (d >= nr) { atomicOr(tail + OL_ERR, 1); d = i; }
+    kout[d] = k;
+    vout[d] = vin[i];
+}
+
+// One lane per ring in its final place: its label, its length (the rank of the start edge's predecessor + 1), zeroed sums,
+// and its place written where the edges find it: at its start edge.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_ring_table(const int* __restrict__ skey, const int* __restrict__ sval, const u64* __restrict__ val, const int* __restrict__ pred,
+                   int* __restrict__ rscan, int* __restrict__ ebase, unsigned ne, unsigned nr, int* tail, OlRings o)
+{
+    const unsigned r = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (r >= nr) return;
+    o.label[r] = skey[r];
+    o.area2[r] = 0;
+    o.edges[2 * r] = 0;
+    o.edges[2 * r + 1] = 0;
+    const unsigned j0 = (unsigned)sval[r];
+    unsigned len = 1;
+    if (j0 >= ne) atomicOr(tail + OL_ERR, 1);
+    else {
+        rscan[j0] = (int)r;
+        const unsigned p = (unsigned)pred[j0];
+        if (p >= ne) atomicOr(tail + OL_ERR, 1);
+        else len = (unsigned)val[p] + 1u;
+        if (len > ne) { atomicOr(tail + OL_ERR, 1); len = 1; }
+    }
+    ebase[r] = (int)len;
+}
+
+// first_ring[k], k = 0 .. n: the first ring of label k + 1 = the first whose label is above k; entry n is n_rings.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_first_ring(const int* __restrict__ skey, unsigned nr, int n, int* __restrict__ first_ring)
+{
+    const unsigned k = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (k > (unsigned)n) return;
+    unsigned lo = 0, hi = nr;
+    for (int step = 0; step < 32 && lo < hi; ++step) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if ((unsigned)skey[mid] <= k) lo = mid + 1;
+        else hi = mid;
+    }
+    first_ring[k] = (int)lo;
+}
+
+// Every edge to its place in (ring, rank) order, and its share of the ring's sums.  The lanes of a wave that belong to one
+// ring add up among themselves first, so a ring of a million edges does not mean a million atomics on one word.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_place(int gw, const u64* __restrict__ val, const int* __restrict__ ecorner, const unsigned char* __restrict__ eside,
+              const unsigned char* __restrict__ cmask, const int* __restrict__ cbase, const int* __restrict__ rscan,
+              const int* __restrict__ ebase, unsigned ne, unsigned nr, unsigned nc, int* tail,
+              int* __restrict__ ocorner, int* __restrict__ vpos, OlRings o)
+{
+    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    bool live = j < ne;
+    unsigned r = 0;
+    long long term = 0;
+    int counts = 0;
+    if (live) {
+        const u64 v = val[j];
+        const unsigned key = (unsigned)(v >> 32), rank = (unsigned)v, t0 = key >> 1;
+        live = false;
+        if (t0 >= nc) atomicOr(tail + OL_ERR, 1);
+        else {
+            const unsigned j0 = (unsigned)cbase[t0] + (unsigned)__popc(cmask[t0] & ((key & 1u) ? 0 : 7));
+            r = j0 < ne ? (unsigned)rscan[j0] : nr;
+            const unsigned g = r < nr ? (unsigned)ebase[r] + rank : ne;
+            const unsigned t = (unsigned)ecorner[j];
+            if (r >= nr || g >= ne || g < rank || t >= nc) atomicOr(tail + OL_ERR, 1);
+            else {
+                const int e = eside[j], s = e & 3;
+                const int x = (int)(t % (unsigned)(gw + 1)), y = (int)(t / (unsigned)(gw + 1));
+                ocorner[g] = (e & 4) ? (int)t : ~(int)t;
+                vpos[g] = (e & 4) ? 1 : 0;
+                term = s == 0 ? y : s == 1 ? x : s == 2 ? -y : -x;          // x1 y0 - x0 y1 of a unit edge, north up
+                counts = (s & 1) ? 1 << 16 : 1;
+                live = true;
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    u64 todo = __ballot(live);
+    for (int round = 0; round < 64 && todo; ++round) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const unsigned lr = (unsigned)__shfl((int)r, lead);
+        const bool mine = live && r == lr;
+        long long a = mine ? term : 0;
+        int c = mine ? counts : 0;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            a += __shfl_xor(a, d);
+            c += __shfl_xor(c, d);
+        }
+        if (lane == lead) {
+            atomicAdd((u64*)o.area2 + lr, (u64)a);
+            if (c & 0xffff) atomicAdd(o.edges + 2 * lr, c & 0xffff);
+            if (c >> 16) atomicAdd(o.edges + 2 * lr + 1, c >> 16);
+        }
+        todo &= ~__ballot(mine);
+    }
+}
+
+__global__ __launch_bounds__(OL_THREADS)
+void ol_vertices(int gw, const int* __restrict__ ocorner, const int* __restrict__ vpos, unsigned ne, unsigned nv, unsigned nc,
+                 int* tail, int* __restrict__ vertices)
+{
+    const unsigned g = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (g >= ne) return;
+    const int t = ocorner[g];
+    if (t < 0) return;
+    const unsigned v = (unsigned)vpos[g];
+    if (v >= nv || (unsigned)t >= nc) { atomicOr(tail + OL_ERR, 1); return; }
+    vertices[2 * v] = (int)((unsigned)t % (unsigned)(gw + 1));
+    vertices[2 * v + 1] = (int)((unsigned)t / (unsigned)(gw + 1));
+}
+
+__global__ __launch_bounds__(OL_THREADS)
+void ol_offsets(const int* __restrict__ ebase, const int* __restrict__ vpos, unsigned ne, unsigned nr, unsigned nv, int* tail, int* __restrict__ offset)
+{
+    const unsigned r = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (r == 0 && (unsigned)tail[OL_TOTAL] != nv) atomicOr(tail + OL_ERR, 1);
+    if (r >= nr) return;
+    const unsigned g = (unsigned)ebase[r];
+    if (g >= ne) { atomicOr(tail + OL_ERR, 1); offset[r] = 0; return; }
+    offset[r] = vpos[g];
+}
+
+__global__ void ol_finish(const int* __restrict__ tail, unsigned nr, unsigned nv, int* __restrict__ offset)
+{
+    if (threadIdx.x == 0) offset[nr] = tail[OL_ERR] ? -1 : (int)nv;
+}
+
+// ---- burn --------------------------------------------------------------------------------------------------------------------
+// One lane per vertex = the edge from it to the next vertex of its ring; the first n_rings lanes also check the offset table.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_burn_edges(const int* __restrict__ vertices, const int* __restrict__ offset, const int* __restrict__ ring_label,
+                   unsigned nr, unsigned nv, int gw, int gh, int* __restrict__ out, int* flag)
+{
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    if (i < nr && (offset[i] < 0 || offset[i] > offset[i + 1])) atomicOr(flag, 2);
+    if (i == 0 && (offset[0] != 0 || (unsigned)offset[nr] != nv)) atomicOr(flag, 2);
+    if (i >= nv) return;
+    unsigned lo = 0, hi = nr;                                // the last ring whose offset is <= i
+    for (int step = 0; step < 32 && lo < hi; ++step) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if ((unsigned)offset[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) { atomicOr(flag, 2); return; }
+    const unsigned r = lo - 1, end = (unsigned)offset[r + 1], begin = (unsigned)offset[r];
+    if (end <= i || end > nv) { atomicOr(flag, 2); return; }                 // begin <= i by the search
+    const unsigned i2 = i + 1 == end ? begin : i + 1;
+    const int x0 = vertices[2 * i], y0 = vertices[2 * i + 1], x1 = vertices[2 * i2], y1 = vertices[2 * i2 + 1];
+    if (x0 != x1) {
+        if (y0 != y1) atomicOr(flag, 1);
+        return;
+    }
+    if (x0 >= gw) return;
+    const int x = max(x0, 0), ya = max(min(y0, y1), 0), yb = min(max(y0, y1), gh), k = ring_label[r];
+    for (int y = ya; y < yb; ++y) atomicXor(out + (size_t)y * gw + x, k);
+}
+
+// The running XOR along a row, a wave per row.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_burn_rows(int* __restrict__ out, int gw, int gh)
+{
+    const unsigned row = blockIdx.x * (unsigned)(OL_THREADS / 64) + (threadIdx.x >> 6);
+    if (row >= (unsigned)gh) return;                         // whole waves only
+    const int lane = threadIdx.x & 63;
+    int* p = out + (size_t)row * gw;
+    int carry = 0;
+    for (int x0 = 0; x0 < gw; x0 += 64) {
+        const int x = x0 + lane;
+        int v = x < gw ? p[x] : 0;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int u = __shfl_up(v, d);
+            if (lane >= d) v ^= u;
+        }
+        v ^= carry;
+        if (x < gw) p[x] = v;
+        carry = __shfl(v, 63);
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+struct OutlineWorkspace {
+    size_t tail, s1, s2, cmask, cbase, pred0, preda, predb, vala, valb, ecorner, eside, rscan, skeya, skeyb, svala, svalb, spos, ebase, ocorner, vpos, bytes;
+    unsigned nc;
+};
+
+static OutlineWorkspace outline_workspace(int gw, int gh, size_t max_edges)
+{
+    OutlineWorkspace w;
+    const size_t nc = ((size_t)gw + 1) * ((size_t)gh + 1), top = nc > max_edges ? nc : max_edges, e = max_edges;
+    const size_t nb1 = (top + OL_BLOCK - 1) / OL_BLOCK, nb2 = (nb1 + OL_BLOCK - 1) / OL_BLOCK;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at += align256(bytes); return here; };
+    w.nc = (unsigned)nc;
+    w.tail = take(256);
+    w.s1 = take(nb1 * 4);
+    w.s2 = take(nb2 * 4);
+    w.cmask = take(nc);
+    w.cbase = take(nc * 4);
+    w.pred0 = take(e * 4); w.preda = take(e * 4); w.predb = take(e * 4);
+    w.vala = take(e * 8); w.valb = take(e * 8);
+    w.ecorner = take(e * 4); w.eside = take(e); w.rscan = take(e * 4);
+    w.skeya = take(e * 4); w.skeyb = take(e * 4); w.svala = take(e * 4); w.svalb = take(e * 4); w.spos = take(e * 4);
+    w.ebase = take(e * 4); w.ocorner = take(e * 4); w.vpos = take(e * 4);
+    w.bytes = at;
+    return w;
+}
+
+static const char* outline_check(int gw, int gh, int n, long long max_edges)
+{
+    if (gw < 1 || gh < 1) return "non-positive grid size";
+    if ((long long)gw * gh >= (1ll << 29)) return "grid too large: gw * gh must be below 2^29 cells";
+    if (n < 0) return "n must be >= 0";
+    if (max_edges < 0 || max_edges > 4ll * gw * gh) return "max_edges must be in 0 .. 4 gw gh";
+    return nullptr;
+}
+
+static int outline_rounds(unsigned max_edges)
+{
+    int rounds = 0;
+    while (rounds < 31 && (1u << rounds) < max_edges) ++rounds;
+    return rounds;
+}
+
+struct OlBuf { const void* p; size_t bytes; const char* name; };
+
+static const char* first_overlap(const OlBuf* buf, int nbuf, const char*& other)
+{
+    for (int i = 1; i < nbuf; ++i)
+        for (int j = 0; j < i; ++j)
+            if (buf[i].bytes && buf[j].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes)) {
+                other = buf[j].name;
+                return buf[i].name;
+            }
+    return nullptr;
+}
+
+}  // namespace smvs
+
+extern "C" {
+
+SMVS_EXPORT size_t smvs_dsm_outline_workspace_bytes(int gw, int gh, int max_edges)
+{
+    using namespace smvs;
+    if (outline_check(gw, gh, 0, max_edges)) return 0;
+    return outline_workspace(gw, gh, (size_t)max_edges).bytes;
+}
+
+SMVS_EXPORT int smvs_dsm_outline_count(const int* labels, int gw, int gh, int n, int max_edges, int* counts,
+                                       void* workspace, size_t workspace_bytes, void* stream)
+{
+    using namespace smvs;
+    if (!labels || !counts || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (const char* msg = outline_check(gw, gh, n, max_edges)) return fail(SMVS_ERR_ARG, "%s", msg);
+    const OutlineWorkspace w = outline_workspace(gw, gh, (size_t)max_edges);
+    if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+    const OlBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {counts, 12, "counts"}, {workspace, w.bytes, "workspace"}};
+    const char* other = nullptr;
+    if (const char* name = first_overlap(buf, 3, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)workspace;
+    int* tail = (int*)(base + w.tail);
+    if (hipMemsetAsync(tail, 0, 256, s) != hipSuccess) return check_launch("dsm_outline_count (clearing the counts)");
+    if (n == 0) {
+        if (hipMemsetAsync(counts, 0, 12, s) != hipSuccess) return check_launch("dsm_outline_count (clearing the counts)");
+        return SMVS_OK;
+    }
+    int *s1 = (int*)(base + w.s1), *s2 = (int*)(base + w.s2), *cbase = (int*)(base + w.cbase);
+    unsigned char* cmask = (unsigned char*)(base + w.cmask);
+    const unsigned corner_blocks = (w.nc + OL_THREADS - 1) / OL_THREADS;
+    int rc;
+    hipLaunchKernelGGL(ol_corners, dim3(corner_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, w.nc, cmask, cbase);
+    if ((rc = check_launch("ol_corners"))) return rc;
+    if ((rc = ol_scan_exclusive(cbase, w.nc, nullptr, s1, s2, tail + OL_NE, s, "ol_scan (edges)"))) return rc;
+    if (max_edges > 0) {
+        const unsigned cap = (unsigned)max_edges, edge_blocks = (cap + OL_THREADS - 1) / OL_THREADS;
+        int *pred[3] = {(int*)(base + w.pred0), (int*)(base + w.preda), (int*)(base + w.predb)};
+        u64* val[2] = {(u64*)(base + w.vala), (u64*)(base + w.valb)};
+        int *ecorner = (int*)(base + w.ecorner), *rscan = (int*)(base + w.rscan);
+        unsigned char* eside = (unsigned char*)(base + w.eside);
+        hipLaunchKernelGGL(ol_edges, dim3(corner_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, w.nc, (const unsigned char*)cmask,
+                           (const int*)cbase, cap, tail, ecorner, val[0], pred[0], eside);
+        if ((rc = check_launch("ol_edges"))) return rc;
+        const int rounds = outline_rounds(cap);
+        for (int r = 0; r < rounds; ++r) {                   // (pred0, vala) -> (preda, valb) -> (predb, vala) -> (preda, valb) ...
+            hipLaunchKernelGGL(ol_double, dim3(edge_blocks), dim3(OL_THREADS), 0, s, (const int*)pred[r == 0 ? 0 : 1 + (r + 1) % 2],
+                               (const u64*)val[r % 2], pred[1 + r % 2], val[(r + 1) % 2], 1u << r, cap, tail);
+            if ((rc = check_launch("ol_double"))) return rc;
+        }
+        hipLaunchKernelGGL(ol_starts, dim3(edge_blocks), dim3(OL_THREADS), 0, s, (const u64*)val[rounds % 2], (const unsigned char*)eside, rscan, cap, tail);
+        if ((rc = check_launch("ol_starts"))) return rc;
+        if ((rc = ol_scan_exclusive(rscan, cap, tail + OL_NE, s1, s2, tail + OL_NR, s, "ol_scan (rings)"))) return rc;
+    }
+    hipLaunchKernelGGL(ol_counts_out, dim3(1), dim3(64), 0, s, (const int*)tail, counts);
+    return check_launch("ol_counts_out");
+}
+
+SMVS_EXPORT int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n, int n_edges, int n_rings, int n_vertices,
+                                       int* ring_label, long long* area2, int* edges, int* offset, int* first_ring, int* vertices,
+                                       void* workspace, size_t workspace_bytes, void* stream)
+{
+    using namespace smvs;
+    if (!labels || !offset || !first_ring || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (const char* msg = outline_check(gw, gh, n, n_edges)) return fail(SMVS_ERR_ARG, "%s", msg);
+    if (n_rings < 0 || n_rings > n_edges || n_vertices < 0 || n_vertices > n_edges || (n_edges > 0) != (n_rings > 0) || (n_edges > 0) != (n_vertices > 0))
+        return fail(SMVS_ERR_ARG, "n_rings (%d) and n_vertices (%d) must be in 1 .. n_edges (%d), or all three 0", n_rings, n_vertices, n_edges);
+    if (n_edges > 0 && n == 0) return fail(SMVS_ERR_ARG, "edges without labels (n == 0)");
+    if (n_edges > 0 && (!ring_label || !area2 || !edges || !vertices)) return fail(SMVS_ERR_ARG, "null pointer argument");
+    const OutlineWorkspace w = outline_workspace(gw, gh, (size_t)n_edges);
+    if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+    const size_t m = (size_t)n_rings;
+    const OlBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {workspace, w.bytes, "workspace"}, {ring_label, m * 4, "ring_label"},
+                         {area2, m * 8, "area2"}, {edges, m * 8, "edges"}, {offset, (m + 1) * 4, "offset"},
+                         {first_ring, ((size_t)n + 1) * 4, "first_ring"}, {vertices, (size_t)n_vertices * 8, "vertices"}};
+    const char* other = nullptr;
+    if (const char* name = first_overlap(buf, 8, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_edges == 0) {                                      // no ring: the two tables that still have entries
+        if (hipMemsetAsync(first_ring, 0, ((size_t)n + 1) * 4, s) != hipSuccess || hipMemsetAsync(offset, 0, 4, s) != hipSuccess)
+            return check_launch("dsm_outline_write (empty tables)");
+        return SMVS_OK;
+    }
+    char* base = (char*)workspace;
+    int *tail = (int*)(base + w.tail), *s1 = (int*)(base + w.s1), *s2 = (int*)(base + w.s2), *cbase = (int*)(base + w.cbase);
+    const unsigned char *cmask = (const unsigned char*)(base + w.cmask), *eside = (const unsigned char*)(base + w.eside);
+    const int rounds = outline_rounds((unsigned)n_edges);
+    const u64* val = (const u64*)(base + (rounds % 2 ? w.valb : w.vala));
+    const int *pred0 = (const int*)(base + w.pred0), *ecorner = (const int*)(base + w.ecorner);
+    int *rscan = (int*)(base + w.rscan), *skey[2] = {(int*)(base + w.skeya), (int*)(base + w.skeyb)};
+    int *sval[2] = {(int*)(base + w.svala), (int*)(base + w.svalb)}, *spos = (int*)(base + w.spos);
+    int *ebase = (int*)(base + w.ebase), *ocorner = (int*)(base + w.ocorner), *vpos = (int*)(base + w.vpos);
+    const unsigned ne = (unsigned)n_edges, nr = (unsigned)n_rings, nv = (unsigned)n_vertices;
+    const unsigned edge_blocks = (ne + OL_THREADS - 1) / OL_THREADS, ring_blocks = (nr + OL_THREADS - 1) / OL_THREADS;
+    const OlRings o = {ring_label, edges, area2};
+    int rc;
+    hipLaunchKernelGGL(ol_ring_init, dim3(edge_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, val, (const int*)rscan, ecorner, eside,
+                       ne, nr, nv, w.nc, tail, skey[0], sval[0]);
+    if ((rc = check_launch("ol_ring_init"))) return rc;
+    int bits = 0;
+    while (bits < 31 && ((unsigned)n >> bits)) ++bits;
+    for (int b = 0; b < bits; ++b) {
+        hipLaunchKernelGGL(ol_sort_flag, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], spos, nr, b);
+        if ((rc = check_launch("ol_sort_flag"))) return rc;
+        if ((rc = ol_scan_exclusive(spos, nr, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (sort)"))) return rc;
+        hipLaunchKernelGGL(ol_sort_scatter, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], (const int*)sval[b % 2],
+                           (const int*)spos, tail, skey[(b + 1) % 2], sval[(b + 1) % 2], nr, b);
+        if ((rc = check_launch("ol_sort_scatter"))) return rc;
+    }
+    const int *keys = skey[bits % 2], *starts = sval[bits % 2];
+    hipLaunchKernelGGL(ol_ring_table, dim3(ring_blocks), dim3(OL_THREADS), 0, s, keys, starts, val, pred0, rscan, ebase, ne, nr, tail, o);
+    if ((rc = check_launch("ol_ring_table"))) return rc;
+    hipLaunchKernelGGL(ol_first_ring, dim3(((unsigned)n + 1u + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, keys, nr, n, first_ring);
+    if ((rc = check_launch("ol_first_ring"))) return rc;
+    if ((rc = ol_scan_exclusive(ebase, nr, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (ring lengths)"))) return rc;
+    hipLaunchKernelGGL(ol_place, dim3(edge_blocks), dim3(OL_THREADS), 0, s, gw, val, ecorner, eside, cmask, (const int*)cbase, (const int*)rscan,
+                       (const int*)ebase, ne, nr, w.nc, tail, ocorner, vpos, o);
+    if ((rc = check_launch("ol_place"))) return rc;
+    if ((rc = ol_scan_exclusive(vpos, ne, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (vertices)"))) return rc;
+    hipLaunchKernelGGL(ol_vertices, dim3(edge_blocks), dim3(OL_THREADS), 0, s, gw, (const int*)ocorner, (const int*)vpos, ne, nv, w.nc, tail, vertices);
+    if ((rc = check_launch("ol_vertices"))) return rc;
+    hipLaunchKernelGGL(ol_offsets, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)ebase, (const int*)vpos, ne, nr, nv, tail, offset);
+    if ((rc = check_launch("ol_offsets"))) return rc;
+    hipLaunchKernelGGL(ol_finish, dim3(1), dim3(64), 0, s, (const int*)tail, nr, nv, offset);
+    return check_launch("ol_finish");
+}
+
+SMVS_EXPORT int smvs_dsm_burn(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
+                              int gw, int gh, int* out, int* flag, void* stream)
+{
+    using namespace smvs;
+    if (!out || !flag) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
+    if (n_rings < 0 || n_vertices < 0) return fail(SMVS_ERR_ARG, "n_rings and n_vertices must be >= 0, got %d and %d", n_rings, n_vertices);
+    const bool some = n_rings > 0 && n_vertices > 0;
+    if (some && (!vertices || !offset || !ring_label)) return fail(SMVS_ERR_ARG, "null pointer argument");
+    const size_t ncells = (size_t)gw * gh;
+    const OlBuf buf[] = {{out, ncells * 4, "out"}, {flag, 4, "flag"}, {vertices, some ? (size_t)n_vertices * 8 : 0, "vertices"},
+                         {offset, some ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {ring_label, some ? (size_t)n_rings * 4 : 0, "ring_label"}};
+    const char* other = nullptr;
+    if (const char* name = first_overlap(buf, 2, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    for (int i = 2; i < 5; ++i)
+        for (int j = 0; j < 2; ++j)
+            if (buf[i].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
+                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[j].name, buf[i].name);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(out, 0, ncells * 4, s) != hipSuccess || hipMemsetAsync(flag, 0, 4, s) != hipSuccess)
+        return check_launch("dsm_burn (clearing the grid)");
+    if (!some) return SMVS_OK;
+    int rc;
+    const unsigned lanes = (unsigned)(n_vertices > n_rings ? n_vertices : n_rings);     // a lane per vertex, and one per entry of the offset table
+    hipLaunchKernelGGL(ol_burn_edges, dim3((lanes + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, vertices, offset, ring_label,
+                       (unsigned)n_rings, (unsigned)n_vertices, gw, gh, out, flag);
+    if ((rc = check_launch("ol_burn_edges"))) return rc;
+    hipLaunchKernelGGL(ol_burn_rows, dim3(((unsigned)gh + OL_THREADS / 64 - 1) / (OL_THREADS / 64)), dim3(OL_THREADS), 0, s, out, gw, gh);
+    return check_launch("ol_burn_rows");
+}
+
+}  // extern "C"

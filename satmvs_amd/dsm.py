@@ -21,6 +21,12 @@ and the objects that stand on the ground (connected components in scipy.ndimage.
     labels, n = label(above > 10.0, connectivity=4)            # the building block; label_stats(), sieve_labels()
     voids, n_voids = label(~(np.isfinite(dsm) & (dsm != -999.0)))   # the void regions fill_voids could not reach
 
+and their outlines as vector data, one polygon with holes per object, and polygons put back on the grid:
+
+    rings = outlines(labels, len(stats["area"]), grid)         # rings of lattice corners: exterior counter-clockwise, holes clockwise
+    write_geojson("objects.geojson", rings, grid, stats)       # a FeatureCollection with the statistics as properties
+    again = burn_rings(rings["vertices"], rings["offset"], rings["label"], labels.shape)   # == labels; for label_stats over footprints
+
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
     reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
@@ -72,6 +78,9 @@ smvs_dsm_morph / smvs_dsm_ground take window minima and maxima as row and column
 doubling in LDS whose cost does not grow with the radius but with its logarithm.
 smvs_dsm_label is a union-find over cell indices (tiles in LDS, tile borders with integer min atomics, a three-level scan
 for the numbering); smvs_dsm_label_stats reduces along rows and columns on chip before its integer atomics.
+smvs_dsm_outline_count / _write keep the boundary edges per lattice corner, find every ring's start and every edge's rank by
+one pointer doubling over the predecessor permutation, and order rings and vertices by scans; smvs_dsm_burn toggles labels
+along vertical edges with integer XOR atomics and takes a running XOR along the rows.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -89,6 +98,7 @@ the image bilinearly.
 from __future__ import annotations
 
 import ctypes
+import json
 import math
 import os
 from dataclasses import dataclass
@@ -724,6 +734,180 @@ def extract_objects(above, grid, min_height=2.5, min_area_m2=50.0, connectivity=
     labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
     stats = {k: t[kept] for k, t in stats.items()}
     return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}
+
+
+# ---- outlines: a label map as oriented rings of lattice corners, GeoJSON, and rings burnt back into a label map ---------------
+MAX_OUTLINE_CELLS = 2 ** 29                                       # 4 edges per cell in an int32
+
+
+def _label_count_checked(n):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31:
+        raise ValueError("n must be an integer in 0 .. 2^31 - 1, got %r" % (n,))
+    return int(n)
+
+
+def _int32_array(a, name, ndim, like):
+    """A numpy array or tensor of `like`'s kind, int32 with ndim axes, never converted."""
+    if isinstance(a, torch.Tensor) != isinstance(like, torch.Tensor):
+        raise ValueError("%s and vertices must both be numpy arrays or both be tensors" % name)
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+    if a.dtype not in (np.int32, torch.int32):
+        raise ValueError("%s is int32, got %s" % (name, a.dtype))
+    if a.ndim != ndim:
+        raise ValueError("%s has %d axes, got shape %s" % (name, ndim, tuple(a.shape)))
+    return a
+
+
+def outlines(labels, n, grid=None):
+    """The outlines of the labels 1 .. n of a label map as polygon rings (include/satmvs.h smvs_dsm_outline_count / _write,
+    DESIGN.md section 9, "Outlines"): labels (gh, gw) int32 from label(), extract_objects() or changes(), fewer than 2^29 cells;
+    values outside 1 .. n count as background.  Corner (x, y) of the lattice is the upper-left corner of cell (row y, col x).
+    -> dict: label int32 (n_rings); area2 int64 (n_rings), twice the enclosed area in cells, > 0 for an exterior ring
+      (counter-clockwise north up), < 0 for a hole (clockwise); edges int32 (n_rings, 2), unit edges heading E or W and N or S;
+      offset int32 (n_rings + 1) into vertices; first_ring int32 (n + 1), the rings of label k + 1 are first_ring[k] ..
+      first_ring[k + 1] - 1, the exterior first; vertices int32 (n_vertices, 2) x, y, no collinear points, a ring not closed
+      (its last vertex joins its first).  Rings are sorted by (label, start y, start x), a ring starts at its smallest corner.
+      with grid (a DSMGrid of the labels' shape): vertices_en float64 (n_vertices, 2) east, north; perimeter_m float64
+      (n_rings); label_perimeter_m float64 (n) and n_holes int32 (n) per label.
+    Connectivity-8 labels can give a ring that touches itself at a corner; label with connectivity 4 for strictly simple rings.
+    Everything depends on labels and n alone, bit for bit.  numpy if the labels came as numpy, device tensors otherwise.  The
+    host reads the device's counts twice; for device tensors a damaged workspace shows as offset[-1] == -1 and is not raised."""
+    labels = _labels_checked(labels)
+    n = _label_count_checked(n)
+    gh, gw = int(labels.shape[0]), int(labels.shape[1])
+    if gh * gw >= MAX_OUTLINE_CELLS:
+        raise ValueError("outlines take fewer than 2^29 cells, got %d x %d" % (gh, gw))
+    if grid is not None:
+        _on_grid(labels, grid)
+    lab, as_numpy = _to_device(labels)
+    dev = lab.device
+    ne = nr = nv = 0
+    ws = nbytes = None
+    if n:
+        lib = _lib.load()
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        nbytes = lib.smvs_dsm_outline_workspace_bytes(gw, gh, 0)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _call(dev, "smvs_dsm_outline_count", lab, gw, gh, n, 0, counts, ws, nbytes)
+        ne = int(counts[0].item())
+        if ne > 0:
+            nbytes = lib.smvs_dsm_outline_workspace_bytes(gw, gh, ne)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _call(dev, "smvs_dsm_outline_count", lab, gw, gh, n, ne, counts, ws, nbytes)
+            ne, nr, nv = counts.tolist()
+        if ne < 0:
+            raise _lib.SatMVSNativeError("smvs_dsm_outline_count gave up: an index out of range in its workspace (n_edges = %d)" % ne)
+    out = {"label": torch.empty(nr, dtype=torch.int32, device=dev), "area2": torch.empty(nr, dtype=torch.int64, device=dev),
+           "edges": torch.empty((nr, 2), dtype=torch.int32, device=dev), "offset": torch.zeros(nr + 1, dtype=torch.int32, device=dev),
+           "first_ring": torch.zeros(n + 1, dtype=torch.int32, device=dev), "vertices": torch.empty((nv, 2), dtype=torch.int32, device=dev)}
+    if ne:
+        _call(dev, "smvs_dsm_outline_write", lab, gw, gh, n, ne, nr, nv, out["label"], out["area2"], out["edges"], out["offset"],
+              out["first_ring"], out["vertices"], ws, nbytes)
+    if grid is not None:
+        xres, yres = float(grid.xres), float(grid.yres)
+        v = out["vertices"].double()
+        out["vertices_en"] = torch.stack([float(grid.e0) + (v[:, 0] - 0.5) * xres, float(grid.n0) - (v[:, 1] - 0.5) * yres], dim=1)
+        out["perimeter_m"] = out["edges"][:, 0].double() * xres + out["edges"][:, 1].double() * yres
+        k = out["label"].long() - 1
+        per_label = torch.zeros((n, 2), dtype=torch.int64, device=dev).index_add_(0, k, out["edges"].long())       # integer sums
+        out["label_perimeter_m"] = per_label[:, 0].double() * xres + per_label[:, 1].double() * yres
+        out["n_holes"] = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, k, (out["area2"] < 0).long()).to(torch.int32)
+    out = {key: _back(as_numpy, t) for key, t in out.items()}
+    if as_numpy and out["offset"][-1] != nv:
+        raise _lib.SatMVSNativeError("smvs_dsm_outline_write gave up: an index out of range in its workspace")
+    return out
+
+
+def burn_rings(vertices, offset, ring_label, shape):
+    """Rings burnt into a label map, the reverse of outlines() (include/satmvs.h smvs_dsm_burn): vertices (n_vertices, 2) int32
+    x, y on the lattice of outlines(), offset (n_rings + 1) int32 into them, ring_label (n_rings) int32, shape = (gh, gw).
+    Every vertical ring edge toggles its label along its rows and every row takes its running XOR: the even-odd rule at cell
+    centres, so a hole empties what its exterior ring fills and a ring given twice cancels.  Rings may lie partly or wholly off
+    the grid.  Edges run along the lattice: one whose ends differ in both coordinates is a ValueError.
+    burn_rings(r["vertices"], r["offset"], r["label"], labels.shape) of r = outlines(labels, n) is labels with the values outside
+    1 .. n zeroed.  -> labels (gh, gw) int32; numpy if the vertices came as numpy, a device tensor otherwise."""
+    if not isinstance(vertices, torch.Tensor):
+        vertices = np.asarray(vertices)
+    vertices = _int32_array(vertices, "vertices", 2, vertices)
+    if vertices.shape[1] != 2:
+        raise ValueError("vertices are (n_vertices, 2) x, y, got shape %s" % (tuple(vertices.shape),))
+    offset = _int32_array(offset, "offset", 1, vertices)
+    ring_label = _int32_array(ring_label, "ring_label", 1, vertices)
+    nv, nr = int(vertices.shape[0]), int(ring_label.shape[0])
+    if int(offset.shape[0]) != nr + 1:
+        raise ValueError("offset has n_rings + 1 = %d entries, got %d" % (nr + 1, int(offset.shape[0])))
+    gh, gw = _int_pair(shape, "shape")
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("shape has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    if not isinstance(offset, torch.Tensor) and (offset[0] != 0 or offset[-1] != nv or (np.diff(offset) < 0).any()):
+        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+    v, as_numpy = _to_device(vertices)
+    dev = v.device
+    off, _ = _to_device(offset, dev=dev)
+    lab, _ = _to_device(ring_label, dev=dev)
+    out = torch.empty((gh, gw), dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_burn", v, off, lab, nr, nv, gw, gh, out, flag)
+    bits = int(flag.item())
+    if bits & 2:
+        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+    if bits & 1:
+        raise ValueError("a ring edge whose ends differ in both coordinates: burn_rings takes edges along the lattice only")
+    return _back(as_numpy, out)
+
+
+def _json_value(x):
+    """A property of a feature: numpy scalars and arrays as what the json module writes; a float that is not finite as null."""
+    if isinstance(x, np.ndarray):
+        return [_json_value(e) for e in x]
+    if isinstance(x, (np.bool_, bool)):
+        return bool(x)
+    if isinstance(x, (np.integer, int)):
+        return int(x)
+    x = float(x)
+    return x if math.isfinite(x) else None
+
+
+def write_geojson(path, rings, grid, stats=None, projection=None):
+    """The rings of outlines() as a GeoJSON FeatureCollection (RFC 7946 winding: exterior rings counter-clockwise, holes
+    clockwise): one Feature per label that has a ring, a Polygon with the label's exterior ring first and then its holes, every
+    ring closed by repeating its first vertex.  Coordinates are east, north on `grid`; with `projection` (a
+    TransverseMercator) lon, lat through its EastNorth2latlon.  properties: label, and from `stats` (the dict of label_stats,
+    extract_objects or changes, entry k for label k + 1) every 1-D entry as a scalar and every 2-D entry (bbox, centroid) as a
+    list.  A label map in which one label has several components gives a Polygon with several counter-clockwise rings, which
+    is not valid GeoJSON: label first.  Plain json, no GIS library.  -> the number of features."""
+    host = {k: (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for k, t in rings.items()}
+    label, offset, first, v = host["label"], host["offset"], host["first_ring"], host["vertices"]
+    n = len(first) - 1
+    if v.ndim != 2 or v.shape[1] != 2 or len(offset) != len(label) + 1 or (len(label) and first[-1] != len(label)):
+        raise ValueError("rings is the dict of outlines()")
+    _grid_checked(grid, "grid")
+    table = {}
+    for key, t in (stats or {}).items():
+        t = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if t.ndim not in (1, 2) or t.shape[0] != n:
+            raise ValueError("stats[%r] has shape %s: one entry per label (%d) expected" % (key, tuple(t.shape), n))
+        table[key] = t
+    en = np.stack([float(grid.e0) + (v[:, 0].astype(np.float64) - 0.5) * float(grid.xres),
+                   float(grid.n0) - (v[:, 1].astype(np.float64) - 0.5) * float(grid.yres)], axis=1)
+    if projection is not None and len(en):
+        en = np.asarray(projection.EastNorth2latlon(en))[:, ::-1]
+    features = []
+    for k in range(n):
+        if first[k] == first[k + 1]:
+            continue
+        polygon = []
+        for r in range(first[k], first[k + 1]):
+            ring = en[offset[r]:offset[r + 1]].tolist()
+            polygon.append(ring + ring[:1])
+        properties = {"label": k + 1}
+        properties.update({key: _json_value(t[k]) for key, t in table.items()})
+        features.append({"type": "Feature", "properties": properties, "geometry": {"type": "Polygon", "coordinates": polygon}})
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+        f.write("\n")
+    return len(features)
 
 
 # ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
