@@ -334,7 +334,9 @@ void costvol_dma_kernel(const CostVolParams p)
 
     // zero cells behind each buffer: a tap whose footprint misses the image reads these, so it
     // contributes 0 * weight exactly like four masked gathers (0, or NaN for a NaN coordinate)
-    for (int i = lane; i < ZPAD_DW; i += 64) tile[DM_NBUF * BUF_DW + i] = 0u;
+    static_assert(ZPAD_DW % 4 == 0 && ZPAD_DW / 4 <= 64 && (DM_NBUF * BUF_DW) % 4 == 0, "one 16-byte LDS store per lane zeroes the pad");
+    if constexpr (SHARED) { for (int i = lane; i < ZPAD_DW; i += 64) tile[DM_NBUF * BUF_DW + i] = 0u; }
+    else if (lane < ZPAD_DW / 4) reinterpret_cast<uint4*>(tile + DM_NBUF * BUF_DW)[lane] = make_uint4(0u, 0u, 0u, 0u);
 
     const float fV = (float)p.V;
     const float rV = p.rV;
@@ -383,12 +385,21 @@ void costvol_dma_kernel(const CostVolParams p)
 
     bool use_pc = false;
     // ---- A: taps of the group's planes -----------------------------------------------------------
+    // Bookkeeping of a tap: ONE packed word, its cell + (1, 1) (smvs_device.h, "packed 16-bit tap cells"), or TAP_NONE for a
+    // tap that reads the zero cells: its footprint misses the image, or its lane / plane stores nothing (a lane outside the
+    // image, a tail plane).  The word is the tap's LDS offset (tap_cell_addr) and what the box extents are taken of.
+    // PKC: the per-wave instances.  The workgroup-shared form keeps a dword index (txy), an in-image bit per tap (okmask) and
+    // four 32-bit extents: its four-source shard measured 2.4 % SLOWER with packed cells (0.630-0.639 -> 0.646-0.655 ms,
+    // five alternating pairs, profiles/tap_bookkeeping.txt) although it issues fewer instructions.
+    constexpr bool PKC = !SHARED;
     TapD tap[DP][NSRC];
-    uint32_t txy[DP][NSRC];
-    uint32_t okmask = 0;
+    uint32_t cell[DP][NSRC];                                 // PKC: packed cell or TAP_NONE; else txy, the dword index relative to image corner (-1,-1)
+    uint32_t okmask = 0;                                     // !PKC
+    uint32_t lo_c[NSRC], hi_c[NSRC];                         // PKC: packed unsigned min / signed max of the lane's cells
     int lo_x[NSRC], hi_x[NSRC], lo_y[NSRC], hi_y[NSRC];
 #pragma unroll
-    for (int s = 0; s < NSRC; ++s) { lo_x[s] = lo_y[s] = INT_MAX; hi_x[s] = hi_y[s] = INT_MIN; }
+    for (int s = 0; s < NSRC; ++s) { lo_c[s] = hi_c[s] = TAP_NONE; lo_x[s] = lo_y[s] = INT_MAX; hi_x[s] = hi_y[s] = INT_MIN; }
+    const uint32_t pk_ones = 0x00010001u, pk_wh = ((uint32_t)H << 16) | (uint32_t)W;
 
     double lat[DP], lon[DP];
 #pragma unroll
@@ -425,9 +436,11 @@ void costvol_dma_kernel(const CostVolParams p)
     // source cubics, smvs_device.h); else the trivariate chain.
     auto planes_and_sources = [&](auto pc_tag, const float (&hh)[DP]) __attribute__((always_inline)) {
         constexpr bool PC = decltype(pc_tag)::value;
-        okmask = 0;
+        if constexpr (!PKC) {
+            okmask = 0;
 #pragma unroll
-        for (int s = 0; s < NSRC; ++s) { lo_x[s] = lo_y[s] = INT_MAX; hi_x[s] = hi_y[s] = INT_MIN; }
+            for (int s = 0; s < NSRC; ++s) { lo_x[s] = lo_y[s] = INT_MAX; hi_x[s] = hi_y[s] = INT_MIN; }
+        }
         if (GEO == 0) {
             // ref view, image -> ground: plane-invariant part once per pixel, Horner in the height per plane.  (Formed inside, so that the
             // 24 registers of the pixel part die before the source passes: a wave that has to redo its planes forms them again.)
@@ -496,13 +509,23 @@ void costvol_dma_kernel(const CostVolParams p)
                         tap[pl][s].wn.x = so * e; tap[pl][s].wn.y = so * w;
                         tap[pl][s].ws.x = n * e;  tap[pl][s].ws.y = n * w;
                     }
-                    const int ix0 = cvt_i32_sat(xw), iy0 = cvt_i32_sat(yn);
-                    const bool ok = ((uint32_t)(ix0 + 1) <= (uint32_t)W) && ((uint32_t)(iy0 + 1) <= (uint32_t)H);
-                    txy[pl][s] = (uint32_t)((iy0 + 1) * (2 * BW) + (ix0 + 1)); // dword index relative to image corner (-1,-1); used only if ok
-                    if (ok) okmask |= 1u << (pl * NSRC + s);
-                    if (ok && active && pl < np) {
-                        lo_x[s] = min(lo_x[s], ix0); hi_x[s] = max(hi_x[s], ix0);
-                        lo_y[s] = min(lo_y[s], iy0); hi_y[s] = max(hi_y[s], iy0);
+                    if constexpr (PKC) {
+                        // in-image test (ix0 + 1) <= W && (iy0 + 1) <= H, unsigned, on the packed cell: W, H <= TAP_MAX_DIM
+                        const uint32_t t = tap_cell_pk(cvt_i32_sat(xw), cvt_i32_sat(yn), pk_ones);
+                        const bool ok = pk_min_u16_s(t, pk_wh) == t;
+                        const uint32_t q = (ok && active && pl < np) ? t : TAP_NONE;
+                        cell[pl][s] = q;
+                        if (pl == 0) lo_c[s] = hi_c[s] = q;          // min / max of TAP_NONE and q
+                        else { lo_c[s] = pk_min_u16(lo_c[s], q); hi_c[s] = pk_max_i16(hi_c[s], q); }
+                    } else {
+                        const int ix0 = cvt_i32_sat(xw), iy0 = cvt_i32_sat(yn);
+                        const bool ok = ((uint32_t)(ix0 + 1) <= (uint32_t)W) && ((uint32_t)(iy0 + 1) <= (uint32_t)H);
+                        cell[pl][s] = (uint32_t)((iy0 + 1) * (2 * BW) + (ix0 + 1));      // used only if ok
+                        if (ok) okmask |= 1u << (pl * NSRC + s);
+                        if (ok && active && pl < np) {
+                            lo_x[s] = min(lo_x[s], ix0); hi_x[s] = max(hi_x[s], ix0);
+                            lo_y[s] = min(lo_y[s], iy0); hi_y[s] = max(hi_y[s], iy0);
+                        }
                     }
                 }
             }
@@ -533,10 +556,11 @@ void costvol_dma_kernel(const CostVolParams p)
     }
     if (!geometry_done) planes_and_sources(std::false_type(), hf);
 
-    if constexpr (GEO == 0 && DP > 1) {
-        // A group cut short by the end of the sweep: its tail planes carry the last plane's height, but a pass of the
-        // bivariate chain read the records of the planes BEHIND the sweep for them -- give them the last plane's taps
-        // (what the trivariate chain computes for them; they are never stored).  Wave-uniform, taken by tail groups only.
+    // A group cut short by the end of the sweep: its tail planes carry the last plane's height, but a pass of the bivariate
+    // chain read the records of the planes BEHIND the sweep for them.  PKC: whatever came of that stays in registers, a tail
+    // plane's taps are TAP_NONE, read the zero cells and are never stored.  Else: give them the last plane's taps (what the
+    // trivariate chain computes for them; they are never stored).  Wave-uniform, taken by tail groups only.
+    if constexpr (GEO == 0 && DP > 1 && !PKC) {
         if (use_pc && np < DP) {
 #pragma unroll
             for (int pl = 1; pl < DP; ++pl)
@@ -544,7 +568,7 @@ void costvol_dma_kernel(const CostVolParams p)
 #pragma unroll
                     for (int s = 0; s < NSRC; ++s) {
                         tap[pl][s] = tap[pl - 1][s];
-                        txy[pl][s] = txy[pl - 1][s];
+                        cell[pl][s] = cell[pl - 1][s];
                         const uint32_t bit = (okmask >> ((pl - 1) * NSRC + s)) & 1u;
                         okmask = (okmask & ~(1u << (pl * NSRC + s))) | (bit << (pl * NSRC + s));
                     }
@@ -562,7 +586,13 @@ void costvol_dma_kernel(const CostVolParams p)
 #pragma unroll
     for (int s = 0; s < NSRC; ++s) {
         int a0 = lo_x[s], a1 = hi_x[s], b0 = lo_y[s], b1 = hi_y[s];
+        if constexpr (PKC) {
+            // halves of the lane's packed extents (cells + 1; no cell: 65535 / -1), reduced over the wave, then back to cells
+            a0 = (int)(lo_c[s] & 0xffffu); a1 = (int)(int16_t)(uint16_t)hi_c[s];
+            b0 = (int)(lo_c[s] >> 16); b1 = (int)hi_c[s] >> 16;
+        }
         wave_minmax4(a0, a1, b0, b1);
+        if constexpr (PKC) { a0 -= 1; a1 -= 1; b0 -= 1; b1 -= 1; }
         if constexpr (SHARED) {
             if (lane == 0) { xch[wave][s][0] = a0; xch[wave][s][1] = a1; xch[wave][s][2] = b0; xch[wave][s][3] = b1; }
         }
@@ -639,7 +669,7 @@ void costvol_dma_kernel(const CostVolParams p)
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int slot = 64 * j + lane;
-            const int row = slot / (2 * C4), rem = slot - row * (2 * C4);
+            const int row = (int)__umulhi((uint32_t)slot, 0xffffffffu / (2 * C4) + 1u), rem = slot - row * (2 * C4);     // slot / (2 C4), exact below 2^16
             const int ch = rem >= C4 ? 1 : 0, col = (rem - ch * C4) * 4;
             const int rel = (row * W + col) * 4 + ch * HW * 4;
 #pragma unroll
@@ -651,16 +681,29 @@ void costvol_dma_kernel(const CostVolParams p)
         }
         }
 #pragma unroll
-        for (int pl = 0; pl < DP; ++pl)
+        for (int s = 0; s < NSRC; ++s) {
+            // A cell of the box lies in buffer 0, below the zero cells at z, and so does its twin in buffer 1; TAP_NONE lands
+            // 65535 * (8 BW + 4) bytes behind the origin, which is at most 4 * 32767 * (2 BW + 1) bytes below the tile
+            // (W, H <= TAP_MAX_DIM): above z in both, without wrapping.  So the unsigned min with z IS the select.
+            static_assert(65535ll * (8 * BW + 4) - 4ll * TAP_MAX_DIM * (2 * BW + 1) > 4ll * TILE_DW &&
+                          65535ll * (8 * BW + 4) + 8ll * TILE_DW < (1ll << 31), "TAP_NONE falls behind the zero cells");
+            const int box0 = s * SRC_DW - ((by0[s] + 1) * (2 * BW) + bx0[s] + 1);          // wave-uniform
+            const uint32_t origin = tile_lds + 4u * (uint32_t)box0;
+            const uint32_t z = tile_lds + 4u * (uint32_t)(DM_NBUF * BUF_DW);
 #pragma unroll
-            for (int s = 0; s < NSRC; ++s) {
-                const bool ok = (okmask >> (pl * NSRC + s)) & 1u;
-                const int box0 = s * SRC_DW - ((by0[s] + 1) * (2 * BW) + bx0[s] + 1);      // wave-uniform
-                const uint32_t a = tile_lds + 4u * (uint32_t)((int)txy[pl][s] + box0);
-                const uint32_t z = tile_lds + 4u * (uint32_t)(DM_NBUF * BUF_DW);
-                tap[pl][s].base[0] = ok ? a : z;
-                tap[pl][s].base[1] = ok ? a + 4u * (uint32_t)BUF_DW : z;
+            for (int pl = 0; pl < DP; ++pl) {
+                if constexpr (PKC) {
+                    const uint32_t a = tap_cell_addr(cell[pl][s], 8u * BW, origin);
+                    tap[pl][s].base[0] = min(a, z);
+                    tap[pl][s].base[1] = min(a + 4u * (uint32_t)BUF_DW, z);
+                } else {
+                    const bool ok = (okmask >> (pl * NSRC + s)) & 1u;
+                    const uint32_t a = tile_lds + 4u * (uint32_t)((int)cell[pl][s] + box0);
+                    tap[pl][s].base[0] = ok ? a : z;
+                    tap[pl][s].base[1] = ok ? a + 4u * (uint32_t)BUF_DW : z;
+                }
             }
+        }
         uint32_t ovo[DP];                                 // per-plane byte offset of this pixel inside one channel volume
 #pragma unroll
         for (int pl = 0; pl < DP; ++pl)
@@ -995,9 +1038,9 @@ static hipError_t launch_ct(CostVolParams p, hipStream_t st)
     const int nd = p.d_end - p.d_begin;
     {
         // one channel volume of the output < 2 GiB: the store descriptor spans two of them (num_records is 32-bit)
-        // and 2^31 is the offset that marks a dropped store; 2 <= W,H < 65535: packed tap coordinates and the
-        // exact-division argument of div_half_int
-        const bool staged_ok = (p.C == 8 || p.C == 16 || p.C == 32) && p.W >= 2 && p.H >= 2 && p.W < 65535 && p.H < 65535 &&
+        // and 2^31 is the offset that marks a dropped store; 2 <= W,H <= TAP_MAX_DIM: packed tap cells (and the
+        // exact-division argument of div_half_int, which holds below 65536)
+        const bool staged_ok = (p.C == 8 || p.C == 16 || p.C == 32) && p.W >= 2 && p.H >= 2 && p.W <= TAP_MAX_DIM && p.H <= TAP_MAX_DIM &&
                                (long long)p.D_out * p.H * p.W * 4 < (1ll << 31);
         if (staged_ok) {
             if (nd == 1) return launch_staged<GEO, NSRC, 1, AR>(p, st);

@@ -544,6 +544,37 @@ __device__ __forceinline__ int cvt_i32_sat(float x)
     return r;
 }
 
+// ---- packed 16-bit tap cells (staged cost-volume build) ------------------------------------------------------
+// A tap's north-west cell (ix0, iy0) travels as ONE word: {iy0 + 1, ix0 + 1} as two 16-bit halves, formed from the saturated
+// int32 cells by one saturating pack and one packed add.  For an image of at most 32767 x 32767 a cell whose footprint touches
+// the image has both halves in [0, W] x [0, H]; every other cell (saturated ones included: -32768 + 1 and 32767 + 1 are above
+// 32767 as unsigned halves) has a half above it, so "(ix0 + 1) <= W && (iy0 + 1) <= H, unsigned" is one packed unsigned min and
+// one 32-bit compare.  TAP_NONE (both halves 0xffff) stands for a tap that takes no part: it is above every cell for the
+// unsigned min, below every cell (-1) for the signed max, and far behind the staging buffers as an LDS address.
+constexpr uint32_t TAP_NONE = 0xffffffffu;
+constexpr int TAP_MAX_DIM = 32767;      // widest / tallest image whose cells (+1) fit the 16-bit halves
+
+__device__ __forceinline__ uint32_t tap_cell_pk(int ix0, int iy0, uint32_t ones /* 0x00010001, wave-uniform */)
+{
+    uint32_t r;
+    asm("v_cvt_pk_i16_i32 %0, %1, %2\n\t"
+        "v_pk_add_u16 %0, %0, %3" : "=&v"(r) : "v"(ix0), "v"(iy0), "s"(ones));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) { uint32_t r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ uint32_t pk_max_i16(uint32_t a, uint32_t b) { uint32_t r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// ... with a wave-uniform second operand (an SGPR: the packed image size)
+__device__ __forceinline__ uint32_t pk_min_u16_s(uint32_t a, uint32_t b) { uint32_t r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
+// LDS byte address of a packed cell: origin + 4 * (cell.x + pitch_dw * cell.y), pitch4 = 4 * pitch_dw (wave-uniform, < 2^16).
+// Two 16 x 16 + 32 bit multiply-adds, the row half picked by op_sel.  TAP_NONE lands 65535 * (pitch4 + 4) bytes behind origin.
+__device__ __forceinline__ uint32_t tap_cell_addr(uint32_t cell, uint32_t pitch4, uint32_t origin)
+{
+    uint32_t r;
+    asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]\n\t"
+        "v_mad_u32_u16 %0, %1, 4, %0" : "=&v"(r) : "v"(cell), "s"(pitch4), "v"(origin));
+    return r;
+}
+
 // ---- wave reductions on the DPP network (no LDS traffic, unlike ds_bpermute shuffles) ------------
 // min(a), max(b), min(c), max(d) over the 64 lanes, the four reductions interleaved so that every DPP
 // instruction is three instructions away from the write it reads (the DPP read-after-VALU-write hazard needs two
