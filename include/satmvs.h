@@ -825,7 +825,53 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   the burn's inputs when n_rings or n_vertices is 0); gw, gh >= 1; gw * gh < 2^29 (outline; 4 gw gh edges fit an int32) or
  *   < 2^31 (burn); n >= 0; 0 <= max_edges <= 4 gw gh; 1 <= n_rings, n_vertices <= n_edges or all three 0; outputs and
  *   workspace distinct from the inputs and from each other; workspace: smvs_dsm_outline_workspace_bytes(gw, gh, max_edges)
- *   bytes (0 = unsupported arguments): 5 bytes per corner and 61 per edge. */
+ *   bytes (0 = unsupported arguments): 5 bytes per corner and 61 per edge.
+ * smvs_dsm_burn_polygons: smvs_dsm_burn for edges of any direction, same arguments.  An edge (x0, y0) - (x1, y1) with
+ *   D = y1 - y0 != 0 visits every row r with min(y0, y1) <= r < max(y0, y1), clipped to the grid; it crosses the row's centre
+ *   line y = r + 1/2 at x_c = x0 + (x1 - x0)(2 r + 1 - 2 y0) / (2 D), and the first toggled column is c = floor(x_c + 1/2), the
+ *   first cell whose centre lies strictly right of the edge: floor((2 D x0 + (x1 - x0)(2 r + 1 - 2 y0) + D) / (2 D)) as one
+ *   int64 floor division, the sign of D taken out first.  ring_label[r] is XORed into out[r, max(c, 0)], nothing for c >= gw;
+ *   then the running XOR of every row.  A cell centre exactly on an edge shared by two polygons is in exactly one of them.  On
+ *   rings whose edges run along the lattice the result is smvs_dsm_burn's bit for bit.  Vertices may lie off the grid,
+ *   |x|, |y| < 2^20 (the numerator fits an int64).  flag: bit 0 is never set, bit 1 as in smvs_dsm_burn, bit 2 a coordinate
+ *   outside |x|, |y| < 2^20 (the edge is left out).  Limits as for smvs_dsm_burn.
+ *
+ * Simplified outlines (csrc/dsm_simplify.hip): Douglas-Peucker on closed rings in exact integers.  Rings as smvs_dsm_outline_write
+ *   gives them, or any: vertices (n_vertices, 2) int32 x, y with 0 <= x, y <= 32767 (every product below stays under 2^63),
+ *   offset (n_rings + 1) int32 rising from 0 to n_vertices, both on the device, read only.  tol16 = floor(16 tol), tol in
+ *   cells, 0 <= tol16 <= 65535.  A ring v_0 .. v_(m-1) is the open chain v_0 .. v_m with v_m = v_0.
+ *   Anchors: v_0 is kept, and v_j for the j that maximises |v_j - v_0|^2, ties to the lowest j.  A ring with m < 3 or with all
+ *   vertices equal keeps every vertex.
+ *   Key of vertex i in the segment (a, b), a < i < b, d = v_b - v_a, u = v_i - v_a, L = |d|^2, t = u . d:
+ *   |u|^2 L if t <= 0; |v_i - v_b|^2 L if t >= L; (d x u)^2 otherwise; |u|^2 if L == 0 (a ring that touches itself): the
+ *   squared distance to the segment, not to the line, times L.  All keys are below 2^62.
+ *   Split: i* maximises the key, ties to the smallest |2 i - a - b| (nearest the segment's middle), then to the lower i.  The
+ *   segment splits at i* (i* is kept) iff key > (tol16^2 L) >> 8, for L == 0 iff key > tol16^2 >> 8: the distance is strictly
+ *   above tol16 / 16.  Otherwise every vertex strictly between a and b is dropped.  Segments are independent, so the kept set
+ *   does not depend on the order; a round treats every live segment once.
+ *   Fall-back: the twice-area of a ring is the shoelace sum of x1 y0 - x0 y1 over its edges (north up, as area2 of the
+ *   outlines).  A ring of which fewer than 3 vertices are kept, or whose kept vertices have twice-area 0 or one of another
+ *   sign than the ring as given, keeps all its vertices and has simplified[r] = 0.  n_rings and the ring order never change.
+ *   Nothing else is repaired: a large tolerance can make a ring cross itself or its neighbour.
+ * smvs_dsm_simplify_begin: flag (device, one int) <- bit 0 a coordinate outside 0 .. 32767, bit 1 an offset table that is not
+ *   0 = offset[0] <= ... <= offset[n_rings] = n_vertices; the anchors and the first two segments of every ring in the
+ *   workspace.  With a flag set the later entries stay in bounds and their results mean nothing.
+ * smvs_dsm_simplify_rounds: `rounds` rounds (0 .. 4096) on the workspace as begin or an earlier call left it; status (device,
+ *   2 ints) <- the number of segments that split in the call's last round, and the number of rounds run since begin up to and
+ *   with the first in which none split (it stops counting there; further rounds find nothing to do).  -1, -1 if an index
+ *   read back from the workspace was out of range.  The caller repeats the call until status[0] == 0; a ring of m vertices
+ *   needs at most m rounds.  No host synchronisation.
+ * smvs_dsm_simplify_count: n_out (device, one int) <- the number of vertices of the result, the fall-back applied, or -1.
+ * smvs_dsm_simplify_write: with n_out read from the device: out_offset (n_rings + 1) int32, out_vertices (n_out, 2) int32,
+ *   area2 (n_rings) int64 of the rings as written, kept (n_out) int32 the index of every output vertex in the input list,
+ *   simplified (n_rings) uint8.  out_offset[n_rings] is n_out, or -1 if n_out differs from the workspace's or an index was
+ *   out of range.  Without vertices the tables are cleared without a launch.
+ *   Integer atomics (max, min, add) only: equal bits from run to run.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers (vertices and the vertex outputs may be null when
+ *   their counts are 0, offset, area2 and simplified when n_rings is 0); 0 <= n_rings, n_vertices < 2^31, no vertices without
+ *   rings; 0 <= tol16 <= 65535; 0 <= rounds <= 4096; 0 <= n_out <= n_vertices; outputs, inputs and workspace distinct;
+ *   workspace: smvs_dsm_simplify_workspace_bytes(n_rings, n_vertices) bytes (0 = unsupported arguments): 56 bytes per vertex
+ *   and 29 per ring. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -892,6 +938,18 @@ int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n, int n_edges
                            void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_burn(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
                   int gw, int gh, int* out, int* flag, void* stream);
+int smvs_dsm_burn_polygons(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
+                           int gw, int gh, int* out, int* flag, void* stream);
+size_t smvs_dsm_simplify_workspace_bytes(int n_rings, int n_vertices);
+int smvs_dsm_simplify_begin(const int* vertices, const int* offset, int n_rings, int n_vertices, int* flag,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_simplify_rounds(const int* vertices, const int* offset, int n_rings, int n_vertices, int tol16, int rounds,
+                             int* status, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_simplify_count(const int* vertices, const int* offset, int n_rings, int n_vertices, int* n_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_simplify_write(const int* vertices, const int* offset, int n_rings, int n_vertices, int n_out,
+                            int* out_offset, int* out_vertices, long long* area2, int* kept, unsigned char* simplified,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

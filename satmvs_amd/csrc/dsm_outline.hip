@@ -4,10 +4,11 @@
 //   smvs_dsm_outline_count  labels (gh, gw) int32 -> n_edges, n_rings, n_vertices on the device, the rings in the workspace
 //   smvs_dsm_outline_write  the ring table and the vertex list into buffers the caller sized from those counts
 //   smvs_dsm_burn           rings -> labels (gh, gw) int32 by the even-odd rule at cell centres
+//   smvs_dsm_burn_polygons  the same for rings whose edges have any direction
 //
 // A boundary edge leaves exactly one lattice corner (its tail) with one of four headings, so the edges are kept per corner: a
 // lane per corner builds the 4-bit mask of the edges that leave it (bit s = the edge on side s of its own cell), and an
-// exclusive scan of the masks' bit counts (three levels of 2048-element blocks, as in dsm_label.hip) numbers the edges in the
+// exclusive scan of the masks' bit counts (three levels of 2048-element blocks, dsm_scan.h) numbers the edges in the
 // order (tail corner y, x, side).  The successor of an edge leaves the corner the edge arrives at and is chosen there, right
 // first, from the two cells ahead; every edge writes its own number at its successor's place, which gives the predecessor
 // array: a permutation of the edges whose cycles are the rings.
@@ -28,11 +29,11 @@
 #include <stdint.h>
 
 #include "dsm_common.h"
+#include "dsm_scan.h"
 #include "smvs_host.h"
 
 namespace smvs {
 
-constexpr int OL_THREADS = 256, OL_PER_THREAD = 8, OL_BLOCK = OL_THREADS * OL_PER_THREAD;    // 2048 elements per workgroup of a scan
 enum { OL_NE = 0, OL_NR = 1, OL_NV = 2, OL_ERR = 3, OL_TOTAL = 4 };                          // the workspace's tail words
 
 typedef unsigned long long u64;
@@ -55,79 +56,6 @@ __device__ __forceinline__ int ol_limit(const int* tail, unsigned cap, int which
 {
     const int v = tail[which];
     return v < 0 ? 0 : (unsigned)v > cap ? (int)cap : v;
-}
-
-// ---- the scan ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ol_block_exclusive(int v, int& total)
-{
-    __shared__ int wave_sum[OL_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < OL_THREADS / 64; ++k) {
-        const int s = wave_sum[k];
-        if (k < wave) before += s;
-        total += s;
-    }
-    return before + inc - v;
-}
-
-// In-place exclusive scan of the first n elements of a in blocks of 2048 (n = min(*n_dev, cap), or cap without n_dev); the
-// block totals go one level up.
-__global__ __launch_bounds__(OL_THREADS)
-void ol_scan(int* __restrict__ a, unsigned cap, const int* __restrict__ n_dev, int* __restrict__ sums)
-{
-    unsigned n = cap;
-    if (n_dev) n = (unsigned)max(0, min(*n_dev, (int)min(cap, (unsigned)INT_MAX)));
-    const unsigned c0 = blockIdx.x * (unsigned)OL_BLOCK + threadIdx.x * (unsigned)OL_PER_THREAD;
-    int v[OL_PER_THREAD], cnt = 0;
-#pragma unroll
-    for (int k = 0; k < OL_PER_THREAD; ++k) {
-        v[k] = (c0 < n && (unsigned)k < n - c0) ? a[c0 + k] : 0;
-        cnt += v[k];
-    }
-    int total;
-    int at = ol_block_exclusive(cnt, total);
-#pragma unroll
-    for (int k = 0; k < OL_PER_THREAD; ++k) {
-        if (c0 < n && (unsigned)k < n - c0) a[c0 + k] = at;
-        at += v[k];
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(OL_THREADS)
-void ol_scan_add(int* __restrict__ a, unsigned cap, const int* __restrict__ n_dev, const int* __restrict__ s1, const int* __restrict__ s2)
-{
-    unsigned n = cap;
-    if (n_dev) n = (unsigned)max(0, min(*n_dev, (int)min(cap, (unsigned)INT_MAX)));
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (i >= n) return;
-    a[i] += s1[i / OL_BLOCK] + s2[i / OL_BLOCK / OL_BLOCK];
-}
-
-// a[0 .. n) <- its exclusive prefix sums, *total <- the sum.  cap < 2^31, so the third level is one block.
-static int ol_scan_exclusive(int* a, unsigned cap, const int* n_dev, int* s1, int* s2, int* total, hipStream_t s, const char* what)
-{
-    const unsigned nb1 = (cap + OL_BLOCK - 1) / OL_BLOCK, nb2 = (nb1 + OL_BLOCK - 1) / OL_BLOCK;
-    int rc;
-    hipLaunchKernelGGL(ol_scan, dim3(nb1), dim3(OL_THREADS), 0, s, a, cap, n_dev, s1);
-    if ((rc = check_launch(what))) return rc;
-    hipLaunchKernelGGL(ol_scan, dim3(nb2), dim3(OL_THREADS), 0, s, s1, nb1, (const int*)nullptr, s2);
-    if ((rc = check_launch(what))) return rc;
-    hipLaunchKernelGGL(ol_scan, dim3(1), dim3(OL_THREADS), 0, s, s2, nb2, (const int*)nullptr, total);
-    if ((rc = check_launch(what))) return rc;
-    hipLaunchKernelGGL(ol_scan_add, dim3((cap + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, a, cap, n_dev, (const int*)s1, (const int*)s2);
-    return check_launch(what);
 }
 
 // ---- count -------------------------------------------------------------------------------------------------------------------
@@ -396,26 +324,38 @@ __global__ void ol_finish(const int* __restrict__ tail, unsigned nr, unsigned nv
 }
 
 // ---- burn --------------------------------------------------------------------------------------------------------------------
-// One lane per vertex = the edge from it to the next vertex of its ring; the first n_rings lanes also check the offset table.
-__global__ __launch_bounds__(OL_THREADS)
-void ol_burn_edges(const int* __restrict__ vertices, const int* __restrict__ offset, const int* __restrict__ ring_label,
-                   unsigned nr, unsigned nv, int gw, int gh, int* __restrict__ out, int* flag)
+// The offset table checked by the first n_rings lanes, and the edge of lane i: from vertex i to the next vertex of its ring.
+// false: no edge (a lane past the vertices, or an offset table that is not what it should be: flag bit 1).
+__device__ __forceinline__ bool ol_burn_edge(const int* __restrict__ vertices, const int* __restrict__ offset, unsigned nr, unsigned nv,
+                                             unsigned i, int* flag, unsigned& r, int& x0, int& y0, int& x1, int& y1)
 {
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
     if (i < nr && (offset[i] < 0 || offset[i] > offset[i + 1])) atomicOr(flag, 2);
     if (i == 0 && (offset[0] != 0 || (unsigned)offset[nr] != nv)) atomicOr(flag, 2);
-    if (i >= nv) return;
+    if (i >= nv) return false;
     unsigned lo = 0, hi = nr;                                // the last ring whose offset is <= i
     for (int step = 0; step < 32 && lo < hi; ++step) {
         const unsigned mid = lo + (hi - lo) / 2;
         if ((unsigned)offset[mid] <= i) lo = mid + 1;
         else hi = mid;
     }
-    if (lo == 0) { atomicOr(flag, 2); return; }
-    const unsigned r = lo - 1, end = (unsigned)offset[r + 1], begin = (unsigned)offset[r];
-    if (end <= i || end > nv) { atomicOr(flag, 2); return; }                 // begin <= i by the search
+    if (lo == 0) { atomicOr(flag, 2); return false; }
+    r = lo - 1;
+    const unsigned end = (unsigned)offset[r + 1], begin = (unsigned)offset[r];
+    if (end <= i || end > nv) { atomicOr(flag, 2); return false; }           // begin <= i by the search
     const unsigned i2 = i + 1 == end ? begin : i + 1;
-    const int x0 = vertices[2 * i], y0 = vertices[2 * i + 1], x1 = vertices[2 * i2], y1 = vertices[2 * i2 + 1];
+    x0 = vertices[2 * i], y0 = vertices[2 * i + 1], x1 = vertices[2 * i2], y1 = vertices[2 * i2 + 1];
+    return true;
+}
+
+// One lane per vertex = the edge from it to the next vertex of its ring; the first n_rings lanes also check the offset table.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_burn_edges(const int* __restrict__ vertices, const int* __restrict__ offset, const int* __restrict__ ring_label,
+                   unsigned nr, unsigned nv, int gw, int gh, int* __restrict__ out, int* flag)
+{
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    unsigned r;
+    int x0, y0, x1, y1;
+    if (!ol_burn_edge(vertices, offset, nr, nv, i, flag, r, x0, y0, x1, y1)) return;
     if (x0 != x1) {
         if (y0 != y1) atomicOr(flag, 1);
         return;
@@ -423,6 +363,33 @@ void ol_burn_edges(const int* __restrict__ vertices, const int* __restrict__ off
     if (x0 >= gw) return;
     const int x = max(x0, 0), ya = max(min(y0, y1), 0), yb = min(max(y0, y1), gh), k = ring_label[r];
     for (int y = ya; y < yb; ++y) atomicXor(out + (size_t)y * gw + x, k);
+}
+
+// The same lanes for edges of any direction: in every row the edge spans, the first column whose centre lies strictly right of
+// the edge's crossing of the row's centre line, floor(x_c + 1/2) as one exact floor division.
+__global__ __launch_bounds__(OL_THREADS)
+void ol_burn_polygon_edges(const int* __restrict__ vertices, const int* __restrict__ offset, const int* __restrict__ ring_label,
+                           unsigned nr, unsigned nv, int gw, int gh, int* __restrict__ out, int* flag)
+{
+    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
+    unsigned r;
+    int x0, y0, x1, y1;
+    if (!ol_burn_edge(vertices, offset, nr, nv, i, flag, r, x0, y0, x1, y1)) return;
+    const int lim = 1 << 20;
+    if (x0 <= -lim || x0 >= lim || y0 <= -lim || y0 >= lim || x1 <= -lim || x1 >= lim || y1 <= -lim || y1 >= lim) {
+        atomicOr(flag, 4);
+        return;
+    }
+    if (y0 == y1) return;
+    const int ya = max(min(y0, y1), 0), yb = min(max(y0, y1), gh), k = ring_label[r];
+    const long long sign = y1 > y0 ? 1 : -1, den = sign * 2 * (y1 - y0), dx = sign * (x1 - x0);          // den > 0
+    const long long base = den * x0 + den / 2;                                                          // (2 D x0 + D) sign
+    for (int y = ya; y < yb; ++y) {
+        const long long num = base + dx * (2 * y + 1 - 2 * y0);
+        long long c = num / den;
+        if (num % den < 0) --c;                              // the floor of a negative quotient
+        if (c < gw) atomicXor(out + (size_t)y * gw + (c < 0 ? 0 : (int)c), k);
+    }
 }
 
 // The running XOR along a row, a wave per row.
@@ -503,6 +470,36 @@ static const char* first_overlap(const OlBuf* buf, int nbuf, const char*& other)
                 return buf[i].name;
             }
     return nullptr;
+}
+
+static int burn_entry(bool lattice, const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
+                      int gw, int gh, int* out, int* flag, void* stream)
+{
+    if (!out || !flag) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
+    if (n_rings < 0 || n_vertices < 0) return fail(SMVS_ERR_ARG, "n_rings and n_vertices must be >= 0, got %d and %d", n_rings, n_vertices);
+    const bool some = n_rings > 0 && n_vertices > 0;
+    if (some && (!vertices || !offset || !ring_label)) return fail(SMVS_ERR_ARG, "null pointer argument");
+    const size_t ncells = (size_t)gw * gh;
+    const OlBuf buf[] = {{out, ncells * 4, "out"}, {flag, 4, "flag"}, {vertices, some ? (size_t)n_vertices * 8 : 0, "vertices"},
+                         {offset, some ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {ring_label, some ? (size_t)n_rings * 4 : 0, "ring_label"}};
+    const char* other = nullptr;
+    if (const char* name = first_overlap(buf, 2, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    for (int i = 2; i < 5; ++i)
+        for (int j = 0; j < 2; ++j)
+            if (buf[i].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
+                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[j].name, buf[i].name);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(out, 0, ncells * 4, s) != hipSuccess || hipMemsetAsync(flag, 0, 4, s) != hipSuccess)
+        return check_launch("dsm_burn (clearing the grid)");
+    if (!some) return SMVS_OK;
+    int rc;
+    const unsigned lanes = (unsigned)(n_vertices > n_rings ? n_vertices : n_rings);     // a lane per vertex, and one per entry of the offset table
+    hipLaunchKernelGGL(lattice ? ol_burn_edges : ol_burn_polygon_edges, dim3((lanes + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s,
+                       vertices, offset, ring_label, (unsigned)n_rings, (unsigned)n_vertices, gw, gh, out, flag);
+    if ((rc = check_launch(lattice ? "ol_burn_edges" : "ol_burn_polygon_edges"))) return rc;
+    hipLaunchKernelGGL(ol_burn_rows, dim3(((unsigned)gh + OL_THREADS / 64 - 1) / (OL_THREADS / 64)), dim3(OL_THREADS), 0, s, out, gw, gh);
+    return check_launch("ol_burn_rows");
 }
 
 }  // namespace smvs
@@ -637,32 +634,13 @@ SMVS_EXPORT int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n,
 SMVS_EXPORT int smvs_dsm_burn(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
                               int gw, int gh, int* out, int* flag, void* stream)
 {
-    using namespace smvs;
-    if (!out || !flag) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if (const char* msg = grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s", msg);
-    if (n_rings < 0 || n_vertices < 0) return fail(SMVS_ERR_ARG, "n_rings and n_vertices must be >= 0, got %d and %d", n_rings, n_vertices);
-    const bool some = n_rings > 0 && n_vertices > 0;
-    if (some && (!vertices || !offset || !ring_label)) return fail(SMVS_ERR_ARG, "null pointer argument");
-    const size_t ncells = (size_t)gw * gh;
-    const OlBuf buf[] = {{out, ncells * 4, "out"}, {flag, 4, "flag"}, {vertices, some ? (size_t)n_vertices * 8 : 0, "vertices"},
-                         {offset, some ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {ring_label, some ? (size_t)n_rings * 4 : 0, "ring_label"}};
-    const char* other = nullptr;
-    if (const char* name = first_overlap(buf, 2, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
-    for (int i = 2; i < 5; ++i)
-        for (int j = 0; j < 2; ++j)
-            if (buf[i].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[j].name, buf[i].name);
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, ncells * 4, s) != hipSuccess || hipMemsetAsync(flag, 0, 4, s) != hipSuccess)
-        return check_launch("dsm_burn (clearing the grid)");
-    if (!some) return SMVS_OK;
-    int rc;
-    const unsigned lanes = (unsigned)(n_vertices > n_rings ? n_vertices : n_rings);     // a lane per vertex, and one per entry of the offset table
-    hipLaunchKernelGGL(ol_burn_edges, dim3((lanes + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, vertices, offset, ring_label,
-                       (unsigned)n_rings, (unsigned)n_vertices, gw, gh, out, flag);
-    if ((rc = check_launch("ol_burn_edges"))) return rc;
-    hipLaunchKernelGGL(ol_burn_rows, dim3(((unsigned)gh + OL_THREADS / 64 - 1) / (OL_THREADS / 64)), dim3(OL_THREADS), 0, s, out, gw, gh);
-    return check_launch("ol_burn_rows");
+    return smvs::burn_entry(true, vertices, offset, ring_label, n_rings, n_vertices, gw, gh, out, flag, stream);
+}
+
+SMVS_EXPORT int smvs_dsm_burn_polygons(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
+                                       int gw, int gh, int* out, int* flag, void* stream)
+{
+    return smvs::burn_entry(false, vertices, offset, ring_label, n_rings, n_vertices, gw, gh, out, flag, stream);
 }
 
 }  // extern "C"

@@ -819,6 +819,49 @@ def outlines(labels, n, grid=None):
     return out
 
 
+def _rings_checked(vertices, offset, ring_label=None):
+    """The ring table of burn_rings, burn_polygons and simplify_outlines, checked on the host as far as it can be without
+    reading device memory.  -> vertices, offset, ring_label, n_vertices, n_rings."""
+    if not isinstance(vertices, torch.Tensor):
+        vertices = np.asarray(vertices)
+    vertices = _int32_array(vertices, "vertices", 2, vertices)
+    if vertices.shape[1] != 2:
+        raise ValueError("vertices are (n_vertices, 2) x, y, got shape %s" % (tuple(vertices.shape),))
+    offset = _int32_array(offset, "offset", 1, vertices)
+    nv, nr = int(vertices.shape[0]), int(offset.shape[0]) - 1
+    if ring_label is not None:
+        ring_label = _int32_array(ring_label, "ring_label", 1, vertices)
+        nr = int(ring_label.shape[0])
+    if int(offset.shape[0]) != nr + 1 or nr < 0:
+        raise ValueError("offset has n_rings + 1 = %d entries, got %d" % (nr + 1, int(offset.shape[0])))
+    return vertices, offset, ring_label, nv, nr
+
+
+def _offset_rises(offset, nv):
+    if not isinstance(offset, torch.Tensor) and (offset[0] != 0 or offset[-1] != nv or (np.diff(offset) < 0).any()):
+        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+
+
+def _burn(entry, vertices, offset, ring_label, shape):
+    """-> (labels on the device, whether the caller gave numpy, the entry's flag bits)."""
+    vertices, offset, ring_label, nv, nr = _rings_checked(vertices, offset, ring_label)
+    gh, gw = _int_pair(shape, "shape")
+    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
+        raise ValueError("shape has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
+    _offset_rises(offset, nv)
+    v, as_numpy = _to_device(vertices)
+    dev = v.device
+    off, _ = _to_device(offset, dev=dev)
+    lab, _ = _to_device(ring_label, dev=dev)
+    out = torch.empty((gh, gw), dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, entry, v, off, lab, nr, nv, gw, gh, out, flag)
+    bits = int(flag.item())
+    if bits & 2:
+        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+    return out, as_numpy, bits
+
+
 def burn_rings(vertices, offset, ring_label, shape):
     """Rings burnt into a label map, the reverse of outlines() (include/satmvs.h smvs_dsm_burn): vertices (n_vertices, 2) int32
     x, y on the lattice of outlines(), offset (n_rings + 1) int32 into them, ring_label (n_rings) int32, shape = (gh, gw).
@@ -827,34 +870,129 @@ def burn_rings(vertices, offset, ring_label, shape):
     the grid.  Edges run along the lattice: one whose ends differ in both coordinates is a ValueError.
     burn_rings(r["vertices"], r["offset"], r["label"], labels.shape) of r = outlines(labels, n) is labels with the values outside
     1 .. n zeroed.  -> labels (gh, gw) int32; numpy if the vertices came as numpy, a device tensor otherwise."""
-    if not isinstance(vertices, torch.Tensor):
-        vertices = np.asarray(vertices)
-    vertices = _int32_array(vertices, "vertices", 2, vertices)
-    if vertices.shape[1] != 2:
-        raise ValueError("vertices are (n_vertices, 2) x, y, got shape %s" % (tuple(vertices.shape),))
-    offset = _int32_array(offset, "offset", 1, vertices)
-    ring_label = _int32_array(ring_label, "ring_label", 1, vertices)
-    nv, nr = int(vertices.shape[0]), int(ring_label.shape[0])
-    if int(offset.shape[0]) != nr + 1:
-        raise ValueError("offset has n_rings + 1 = %d entries, got %d" % (nr + 1, int(offset.shape[0])))
-    gh, gw = _int_pair(shape, "shape")
-    if gh < 1 or gw < 1 or gh * gw >= 2 ** 31:
-        raise ValueError("shape has positive sizes and fewer than 2^31 cells, got %d x %d" % (gh, gw))
-    if not isinstance(offset, torch.Tensor) and (offset[0] != 0 or offset[-1] != nv or (np.diff(offset) < 0).any()):
-        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
-    v, as_numpy = _to_device(vertices)
-    dev = v.device
-    off, _ = _to_device(offset, dev=dev)
-    lab, _ = _to_device(ring_label, dev=dev)
-    out = torch.empty((gh, gw), dtype=torch.int32, device=dev)
-    flag = torch.empty(1, dtype=torch.int32, device=dev)
-    _call(dev, "smvs_dsm_burn", v, off, lab, nr, nv, gw, gh, out, flag)
-    bits = int(flag.item())
-    if bits & 2:
-        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+    out, as_numpy, bits = _burn("smvs_dsm_burn", vertices, offset, ring_label, shape)
     if bits & 1:
         raise ValueError("a ring edge whose ends differ in both coordinates: burn_rings takes edges along the lattice only")
     return _back(as_numpy, out)
+
+
+MAX_POLYGON_COORD = 2 ** 20                                       # |x|, |y| below it: the crossing's numerator fits an int64
+
+
+def burn_polygons(vertices, offset, ring_label, shape):
+    """burn_rings for rings with edges of any direction (include/satmvs.h smvs_dsm_burn_polygons): the rings of
+    simplify_outlines(), or any polygons with integer vertices |x|, |y| < 2^20, on or off the grid.  A cell belongs to a ring
+    iff its centre is inside by the even-odd rule; a centre exactly on an edge belongs to the side on the edge's left (the cell
+    counts as right of the crossing only if its centre lies strictly right of it), so a centre on the border two polygons share
+    is in exactly one of them.  On rings with lattice edges the result is burn_rings' bit for bit.
+    -> labels (gh, gw) int32; numpy if the vertices came as numpy, a device tensor otherwise."""
+    out, as_numpy, bits = _burn("smvs_dsm_burn_polygons", vertices, offset, ring_label, shape)
+    if bits & 4:
+        raise ValueError("a vertex outside |x|, |y| < 2^20")
+    return _back(as_numpy, out)
+
+
+MAX_SIMPLIFY_COORD = 32767                                        # with it every product of the distance key stays below 2^63
+MAX_TOL16 = 65535
+SIMPLIFY_BATCH = 8                                                # rounds between two reads of the device's status
+
+
+def _tol16_checked(tol):
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not math.isfinite(tol) or tol < 0:
+        raise ValueError("tol is a finite number of cells >= 0, got %r" % (tol,))
+    tol16 = int(math.floor(16.0 * float(tol)))
+    if tol16 > MAX_TOL16:
+        raise ValueError("tol must be below 4096 cells (floor(16 tol) <= %d), got %r" % (MAX_TOL16, tol))
+    return tol16
+
+
+def simplify_outlines(rings, tol, grid=None):
+    """The rings of outlines() simplified by Douglas-Peucker in exact integers (include/satmvs.h, "Simplified outlines"; DESIGN.md
+    section 9): rings is the dict of outlines(), or any dict with vertices (n_vertices, 2) int32 0 <= x, y <= 32767, offset
+    (n_rings + 1) int32, label (n_rings) int32 and first_ring; tol in cells, used as tol16 = floor(16 tol) <= 65535.
+    Every ring keeps its first vertex and the vertex farthest from it; a segment between two kept vertices splits at its
+    farthest vertex (distance to the segment; ties to the vertex nearest the segment's middle, then the lower index) iff that
+    distance is strictly above tol16 / 16, so the whole ring as given lies within tol of the result.  A ring left with fewer than
+    3 vertices, no area or an area of the other sign keeps all its vertices (simplified 0).  Nothing else is repaired: a large
+    tol can make rings cross themselves or each other, and a border shared by two labels is simplified once from each side.
+    -> dict: label, first_ring as given; offset int32 (n_rings + 1); vertices int32 (n_vertices_out, 2); area2 int64 (n_rings),
+      the shoelace sum of the ring as returned; kept int32 (n_vertices_out), the index of every output vertex in the input
+      vertices; simplified uint8 (n_rings); rounds int, the number of rounds up to and with the first in which no segment split
+      (0 without vertices).  with grid: vertices_en float64 (n_vertices_out, 2), perimeter_m float64 (n_rings), the sum of
+      sqrt((dx xres)^2 + (dy yres)^2) over the ring's edges, and n_holes int32 per label.
+    tol 0 returns every ring of outlines() unchanged.  Everything depends on the input alone, bit for bit.  numpy if the
+    vertices came as numpy, device tensors otherwise; write_geojson() and burn_polygons() take the result."""
+    for key in ("vertices", "offset", "label", "first_ring"):
+        if key not in rings:
+            raise ValueError("rings is the dict of outlines(): entry %r is missing" % key)
+    vertices, offset, label, nv, nr = _rings_checked(rings["vertices"], rings["offset"], rings["label"])
+    first_ring = _int32_array(rings["first_ring"], "first_ring", 1, vertices)
+    tol16 = _tol16_checked(tol)
+    _offset_rises(offset, nv)
+    if nv and not isinstance(vertices, torch.Tensor) and (vertices.min() < 0 or vertices.max() > MAX_SIMPLIFY_COORD):
+        raise ValueError("vertices must be in 0 .. %d" % MAX_SIMPLIFY_COORD)
+    if grid is not None:
+        _grid_checked(grid, "grid")
+    v, as_numpy = _to_device(vertices)
+    dev = v.device
+    off, _ = _to_device(offset, dev=dev)
+    lab, _ = _to_device(label, dev=dev)
+    first, _ = _to_device(first_ring, dev=dev)
+    lib = _lib.load()
+    nbytes = lib.smvs_dsm_simplify_workspace_bytes(nr, nv)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    word = torch.empty(2, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_simplify_begin", v, off, nr, nv, word, ws, nbytes)
+    bits = int(word[0].item())
+    if bits & 2:
+        raise ValueError("offset must rise from 0 to n_vertices = %d" % nv)
+    if bits & 1:
+        raise ValueError("vertices must be in 0 .. %d" % MAX_SIMPLIFY_COORD)
+    rounds = 0
+    if nv:
+        longest = int((off[1:] - off[:-1]).max().item())             # a ring of m vertices splits in at most m rounds
+        run = 0
+        while True:
+            _call(dev, "smvs_dsm_simplify_rounds", v, off, nr, nv, tol16, SIMPLIFY_BATCH, word, ws, nbytes)
+            run += SIMPLIFY_BATCH
+            splits, rounds = word.tolist()
+            if splits < 0:
+                raise _lib.SatMVSNativeError("smvs_dsm_simplify_rounds gave up: an index out of range in its workspace")
+            if splits == 0:
+                break
+            if run > longest:
+                raise _lib.SatMVSNativeError("smvs_dsm_simplify_rounds: segments still split after %d rounds, more than the longest ring has vertices (%d)" % (run, longest))
+    _call(dev, "smvs_dsm_simplify_count", v, off, nr, nv, word, ws, nbytes)
+    n_out = int(word[0].item())
+    if n_out < 0:
+        raise _lib.SatMVSNativeError("smvs_dsm_simplify_count gave up: an index out of range in its workspace")
+    out = {"label": lab, "first_ring": first, "offset": torch.zeros(nr + 1, dtype=torch.int32, device=dev),
+           "vertices": torch.empty((n_out, 2), dtype=torch.int32, device=dev), "area2": torch.empty(nr, dtype=torch.int64, device=dev),
+           "kept": torch.empty(n_out, dtype=torch.int32, device=dev), "simplified": torch.empty(nr, dtype=torch.uint8, device=dev)}
+    _call(dev, "smvs_dsm_simplify_write", v, off, nr, nv, n_out, out["offset"], out["vertices"], out["area2"], out["kept"], out["simplified"], ws, nbytes)
+    if grid is not None:
+        xres, yres = float(grid.xres), float(grid.yres)
+        p = out["vertices"].double()
+        out["vertices_en"] = torch.stack([float(grid.e0) + (p[:, 0] - 0.5) * xres, float(grid.n0) - (p[:, 1] - 0.5) * yres], dim=1)
+        o = out["offset"].long()
+        ring_of = torch.repeat_interleave(torch.arange(nr, device=dev), o[1:] - o[:-1], output_size=n_out)
+        at = torch.arange(n_out, device=dev)
+        nxt = torch.where(at + 1 == o[1:][ring_of], o[:-1][ring_of], at + 1)             # the ring's last vertex joins its first
+        d = p[nxt] - p
+        length = torch.sqrt((d[:, 0] * xres) ** 2 + (d[:, 1] * yres) ** 2)
+        # a ring's lengths added one after the other in vertex order: no atomics, so equal bits from run to run
+        out["perimeter_m"] = torch.segment_reduce(length, "sum", lengths=o[1:] - o[:-1], unsafe=True) if nr else length.new_zeros(0)
+        n = int(first.numel()) - 1
+        k = lab.long() - 1
+        inside = (k >= 0) & (k < n)
+        out["n_holes"] = torch.zeros(max(n, 0), dtype=torch.int64, device=dev).index_add_(0, k[inside], (out["area2"] < 0).long()[inside]).to(torch.int32)
+    if as_numpy:
+        torch.cuda.synchronize(dev)
+    result = {key: _back(as_numpy, t) for key, t in out.items()}
+    if int(result["offset"][-1]) != n_out:
+        raise _lib.SatMVSNativeError("smvs_dsm_simplify_write gave up: an index out of range in its workspace")
+    result["rounds"] = int(rounds)
+    return result
 
 
 def _json_value(x):
