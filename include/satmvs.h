@@ -871,7 +871,61 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   their counts are 0, offset, area2 and simplified when n_rings is 0); 0 <= n_rings, n_vertices < 2^31, no vertices without
  *   rings; 0 <= tol16 <= 65535; 0 <= rounds <= 4096; 0 <= n_out <= n_vertices; outputs, inputs and workspace distinct;
  *   workspace: smvs_dsm_simplify_workspace_bytes(n_rings, n_vertices) bytes (0 = unsupported arguments): 56 bytes per vertex
- *   and 29 per ring. */
+ *   and 29 per ring.
+ *
+ * Contours (csrc/dsm_contour.hip): the isolines of dsm (gh, gw) float32 (device, read only) at n_levels levels in one call.
+ *   Nodes, validity, heights.  Node (r, c) is the centre of cell (r, c); its position in index units is x = c, y = r.  A node
+ *   is valid iff it is finite, != (float)nodata and |z| <= 32768.  q = llrint((double)z 256), halves to even, as in the
+ *   registration and the horizon.
+ *   Levels.  A level is an odd integer K in units of 2^-9 m: levels sit on half quanta, so no node ever lies on a contour.
+ *   Node a is ABOVE iff 2 q_a > K.  levels is a HOST array of n_levels int32, odd, strictly rising, |K| < 2^25,
+ *   1 <= n_levels <= 4096; more levels go through several calls, the bits do not depend on the batching.  (dsm.contours maps
+ *   a level in metres to K = 2 floor(256 level) + 1 and reports K / 512.)
+ *   Lattice edges.  eid = 2 (r gw + c) + o: o = 0 the edge from node (r, c) to (r, c + 1) (c < gw - 1), o = 1 the edge from
+ *   (r, c) to (r + 1, c) (r < gh - 1).
+ *   Crossings.  Edge e is crossed at level K iff both ends are valid and exactly one is above; a crossing (K, e) is a
+ *   candidate vertex.  With a the end the eid names and b the other, t = (double)(K - 2 q_a) / (double)(2 q_b - 2 q_a), one
+ *   IEEE division of two exactly representable integers, 0 < t < 1; the vertex is (x, y) = ((double)c + t, (double)r) for
+ *   o = 0 and ((double)c, (double)r + t) for o = 1: one addition.
+ *   Squares.  Square (r, c), 0 <= r < gh - 1, 0 <= c < gw - 1, has the corner nodes (r, c), (r, c + 1), (r + 1, c + 1),
+ *   (r + 1, c); it is live iff all four are valid.
+ *   Direction.  A line runs with the higher ground on its LEFT, north up, which fixes how it passes a crossed edge: o = 0,
+ *   west end above: it heads north, out of square (r, c) into (r - 1, c); o = 0, east end above: south, out of (r - 1, c) into
+ *   (r, c); o = 1, north end above: east, out of (r, c - 1) into (r, c); o = 1, south end above: west, out of (r, c) into
+ *   (r, c - 1).
+ *   Successor.  The crossing enters square S.  If S is off the lattice or not live it has no successor.  Otherwise let H
+ *   (above) and L be the ends of the entry edge, H' the corner of S next to H and L' the one next to L.  H' and L' not above:
+ *   leave through edge H - H' (left).  H' above, L' not: through H' - L' (straight).  Both above: through L - L' (right).  H'
+ *   not above and L' above, the saddle: through L - L' iff the q of the four corners sum to > 2 K (the mean of the corners is
+ *   above, strictly), else through H - H'.  The successor is the crossing (K, exit edge), crossed by construction.  The
+ *   successor is injective, so the crossings of a level fall into open chains and closed rings.
+ *   Lines.  A crossing with neither predecessor nor successor is dropped, so an open chain has at least 2 vertices and a ring
+ *   at least 4.  An open line starts at its crossing without a predecessor; a closed line starts at its smallest eid and is
+ *   NOT repeated at the end.  Consecutive vertices lie on different edges of one square: no segment has zero length.  Lines
+ *   are ordered by (level index, eid of the first vertex), a unique key.  Nothing is smoothed, simplified or joined across
+ *   voids.
+ * smvs_dsm_contour_count: counts (device, 3 ints) gets n_cross (all crossings, the dropped ones included), n_lines,
+ *   n_vertices, or -1, -1, -1 if there are more crossings than max_cross (or than an int32 holds), or an index read back from
+ *   the workspace was out of range.  max_cross == 0 counts the crossings only (n_cross, 0, 0) in a workspace of
+ *   smvs_dsm_contour_workspace_bytes(gw, gh, n_levels, 0) bytes; the caller reads n_cross and calls again with max_cross =
+ *   n_cross and a workspace of that size, which then holds the lines.  The doubling runs ceil(log2(max_cross)) rounds
+ *   whatever the workspace holds.  The level table reaches the device through kernel arguments, 512 levels a launch.  No
+ *   host synchronisation.
+ * smvs_dsm_contour_write: with the three counts read from the device, the same dsm and levels, and the workspace as a count
+ *   call with max_cross == n_cross left it (the layout follows max_cross): line_level[i] int32, the index into levels;
+ *   line_closed[i] uint8; offset[i] int32, n_lines + 1 entries, into vertices; first_line[k] int32, n_levels + 1 entries, the
+ *   first line of level k (a level without a line: first_line[k] == first_line[k + 1]); vertices[2 v ..] float64 x, y;
+ *   vertex_edge[v] int32, the eid (may be null).  offset[n_lines] is n_vertices, or -1 if the counts or max_cross differ from
+ *   the workspace's or an index was out of range.  n_lines == 0: first_line and offset[0] are cleared without a launch.  The
+ *   call leaves the workspace as it found it but for its own tables, so it may be repeated.
+ *   Every workspace word a kernel reads was written by a kernel of the count call or of the write call (a workspace full of
+ *   anything will do); integer atomics (add, or) only: everything depends on dsm, nodata and levels alone, equal bits from run
+ *   to run and on any stream, and equal to the numpy statement of this rule, the float64 coordinates included.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers (the line and vertex outputs may be null when
+ *   n_lines is 0, vertex_edge always); gw, gh >= 1, gw * gh < 2^29; levels as above; 0 <= max_cross, n_cross < 2^31; n_lines
+ *   and n_vertices both 0 or 2 n_lines <= n_vertices <= n_cross; inputs, outputs and workspace do not overlap; workspace:
+ *   smvs_dsm_contour_workspace_bytes(gw, gh, n_levels, max_cross) bytes (0 = unsupported arguments): 8 bytes per cell (4 per
+ *   lattice edge), 47 per crossing, the 16 KB level table and the scans' block sums. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -950,6 +1004,14 @@ int smvs_dsm_simplify_count(const int* vertices, const int* offset, int n_rings,
 int smvs_dsm_simplify_write(const int* vertices, const int* offset, int n_rings, int n_vertices, int n_out,
                             int* out_offset, int* out_vertices, long long* area2, int* kept, unsigned char* simplified,
                             void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_contour_workspace_bytes(int gw, int gh, int n_levels, int max_cross);
+int smvs_dsm_contour_count(const float* dsm, int gw, int gh, float nodata,
+                           const int* levels /* HOST, n_levels odd int32 in units of 2^-9 m, rising */, int n_levels,
+                           int max_cross, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float nodata, const int* levels /* HOST */, int n_levels,
+                           int n_cross, int n_lines, int n_vertices, int* line_level, unsigned char* line_closed,
+                           int* offset, int* first_line, double* vertices, int* vertex_edge /* may be null */,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,11 @@ and their outlines as vector data, one polygon with holes per object, and polygo
     write_geojson("objects.geojson", rings, grid, stats)       # a FeatureCollection with the statistics as properties
     again = burn_rings(rings["vertices"], rings["offset"], rings["label"], labels.shape)   # == labels; for label_stats over footprints
 
+and the terrain as vector data, contour lines at many levels in one call:
+
+    lines = contours(dtm, interval=2.5, grid=grid)             # ordered float64 vertex lists: open chains and closed rings
+    write_contours("contours.geojson", lines, grid)            # a FeatureCollection of LineStrings: level_m, closed, length_m
+
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
     reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
@@ -81,6 +86,9 @@ for the numbering); smvs_dsm_label_stats reduces along rows and columns on chip 
 smvs_dsm_outline_count / _write keep the boundary edges per lattice corner, find every ring's start and every edge's rank by
 one pointer doubling over the predecessor permutation, and order rings and vertices by scans; smvs_dsm_burn toggles labels
 along vertical edges with integer XOR atomics and takes a running XOR along the rows.
+smvs_dsm_contour_count / _write number the crossings (level, lattice edge) by a scan over the edges of the levels that cross
+each, link every crossing to its successor in the square it enters, rank open chains and rings by the same pointer doubling,
+and write float64 vertices; all levels of a call are in flight at once.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1042,6 +1050,201 @@ def write_geojson(path, rings, grid, stats=None, projection=None):
         properties = {"label": k + 1}
         properties.update({key: _json_value(t[k]) for key, t in table.items()})
         features.append({"type": "Feature", "properties": properties, "geometry": {"type": "Polygon", "coordinates": polygon}})
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+        f.write("\n")
+    return len(features)
+
+
+# ---- contour lines ---------------------------------------------------------------------------------------------------------------
+MAX_CONTOUR_LEVELS = 4096                                         # levels of one native call; more go in chunks
+MAX_CONTOUR_Z = 32768.0
+MAX_CONTOUR_LIST = 2 ** 20                                        # levels of one contours() call
+
+
+def _contour_dsm(dsm, grid=None):
+    """A (gh, gw) DSM of any real dtype, numpy taken as float32 (a tensor is converted on its way to the device), fewer than
+    2^29 cells; checked before any device work."""
+    if not isinstance(dsm, torch.Tensor):
+        dsm = np.asarray(dsm, dtype=np.float32)
+    if dsm.ndim != 2:
+        raise ValueError("a DSM is (gh, gw), got shape %s" % (tuple(dsm.shape),))
+    gh, gw = int(dsm.shape[0]), int(dsm.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= MAX_OUTLINE_CELLS:
+        raise ValueError("contours take positive sizes and fewer than 2^29 cells, got %d x %d" % (gh, gw))
+    if grid is not None:
+        _on_grid(dsm, _grid_checked(grid, "grid"))
+    return dsm
+
+
+def _interval_checked(interval, base):
+    if isinstance(interval, bool) or not isinstance(interval, (int, float, np.integer, np.floating)) or not math.isfinite(interval) or interval <= 0:
+        raise ValueError("interval is a finite number of metres > 0, got %r" % (interval,))
+    return float(interval), _finite(base, "base")
+
+
+def contour_levels(dsm, interval, base=0.0, nodata=-999.0):
+    """The levels base + k interval, k an integer, that lie strictly inside the range of the DSM's valid heights (finite,
+    != nodata, |z| <= 32768 m) -> float64 numpy, rising; empty without two different valid heights.  numpy stays on the host."""
+    interval, base = _interval_checked(interval, base)
+    dsm = _contour_dsm(dsm)
+    if isinstance(dsm, torch.Tensor):
+        z = dsm.to(torch.float32)
+        z = z[torch.isfinite(z) & (z != float(np.float32(nodata))) & (z.abs() <= MAX_CONTOUR_Z)]
+        if z.numel() == 0:
+            return np.zeros(0, np.float64)
+        lo, hi = float(z.min().item()), float(z.max().item())
+    else:
+        with np.errstate(invalid="ignore"):
+            z = dsm[np.isfinite(dsm) & (dsm != np.float32(nodata)) & (np.abs(dsm) <= np.float32(MAX_CONTOUR_Z))]
+        if z.size == 0:
+            return np.zeros(0, np.float64)
+        lo, hi = float(z.min()), float(z.max())
+    k0, k1 = math.floor((lo - base) / interval), math.ceil((hi - base) / interval)
+    if k1 - k0 + 1 > MAX_CONTOUR_LIST:
+        raise ValueError("interval %r gives more than 2^20 levels between %r and %r" % (interval, lo, hi))
+    levels = base + np.arange(k0, k1 + 1, dtype=np.float64) * interval
+    return levels[(levels > lo) & (levels < hi)]
+
+
+def _level_keys(levels):
+    """Levels in metres -> the odd int64 K = 2 floor(256 level) + 1 in units of 2^-9 m, rising."""
+    lv = np.asarray(levels.cpu() if isinstance(levels, torch.Tensor) else levels, dtype=np.float64)
+    if lv.ndim != 1:
+        raise ValueError("levels is a list of heights in metres, got shape %s" % (tuple(lv.shape),))
+    if lv.size > MAX_CONTOUR_LIST:
+        raise ValueError("at most 2^20 levels in a call, got %d" % lv.size)
+    if not np.isfinite(lv).all():
+        raise ValueError("levels must be finite")
+    if lv.size and np.abs(lv).max() > MAX_CONTOUR_Z:
+        raise ValueError("levels must lie within +-32768 m")
+    keys = np.sort(2 * np.floor(256.0 * lv).astype(np.int64) + 1)
+    if (np.diff(keys) == 0).any():
+        raise ValueError("two levels fall on the same step of 2^-8 m (levels are used as 2 floor(256 level) + 1 half steps)")
+    return keys
+
+
+def _contour_chunk(z, gw, gh, nodata, keys, want_edge=True):
+    """One native pass over at most 4096 levels -> the device tensors of smvs_dsm_contour_write and n_vertices."""
+    dev = z.device
+    lib = _lib.load()
+    n = len(keys)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    nbytes = lib.smvs_dsm_contour_workspace_bytes(gw, gh, n, 0)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _call(dev, "smvs_dsm_contour_count", z, gw, gh, nodata, keys, n, 0, counts, ws, nbytes)
+    nc, nl, nv = int(counts[0].item()), 0, 0
+    if nc > 0:
+        nbytes = lib.smvs_dsm_contour_workspace_bytes(gw, gh, n, nc)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _call(dev, "smvs_dsm_contour_count", z, gw, gh, nodata, keys, n, nc, counts, ws, nbytes)
+        nc, nl, nv = counts.tolist()
+    if nc < 0:
+        raise _lib.SatMVSNativeError("smvs_dsm_contour_count gave up: more than 2^31 - 1 crossings, or an index out of range in its workspace")
+    out = {"level_index": torch.empty(nl, dtype=torch.int32, device=dev), "closed": torch.empty(nl, dtype=torch.uint8, device=dev),
+           "offset": torch.zeros(nl + 1, dtype=torch.int32, device=dev), "first_line": torch.zeros(n + 1, dtype=torch.int32, device=dev),
+           "vertices": torch.empty((nv, 2), dtype=torch.float64, device=dev), "edge": torch.empty(nv, dtype=torch.int32, device=dev)}
+    if nl:
+        _call(dev, "smvs_dsm_contour_write", z, gw, gh, nodata, keys, n, nc, nl, nv, out["level_index"], out["closed"], out["offset"],
+              out["first_line"], out["vertices"], out["edge"] if want_edge else None, ws, nbytes)
+    return out, nv
+
+
+def contours(dsm, levels=None, interval=None, base=0.0, grid=None, nodata=-999.0):
+    """The contour lines of a DSM (include/satmvs.h smvs_dsm_contour_count / _write, DESIGN.md section 9, "Contours"): dsm
+    (gh, gw) of any real dtype (taken as float32), fewer than 2^29 cells; exactly one of levels [m, any order, used sorted] and
+    interval [m; the levels of contour_levels(dsm, interval, base)].  Heights count in steps of 2^-8 m and a level as
+    K = 2 floor(256 level) + 1 half steps: at most 2^-8 m above what was asked, never on a node.  A vertex lies on a lattice edge
+    between two cell centres, x = column, y = row in index units; a line keeps the higher ground on its left, north up (a ring
+    round a hill runs counter-clockwise); lines end at voids and at the grid's edge and are not joined across them.
+    -> dict: level_index int32 (n_lines) into the sorted levels; level float64 (n_lines), the effective level K / 512;
+      closed bool (n_lines), a closed line's first vertex is not repeated; offset int32 (n_lines + 1) into vertices; first_line
+      int32 (n_levels + 1), the lines of level k are first_line[k] .. first_line[k + 1] - 1; vertices float64 (n_vertices, 2)
+      x, y; edge int32 (n_vertices), the lattice edge 2 (row gw + col) + (0 east, 1 south) of every vertex.  Lines are sorted by
+      (level, edge of the first vertex); an open line starts where it enters, a ring at its smallest edge.
+      with grid (a DSMGrid of the DSM's shape): vertices_en float64 (n_vertices, 2) east, north (cell centres, no half-cell
+      shift) and length_m float64 (n_lines), a ring's closing segment included.
+    More than 4096 levels go through several native calls and give the result of one.  Everything depends on dsm, nodata and
+    the levels alone, bit for bit.  numpy if the DSM came as numpy, device tensors otherwise.  The host reads the device's
+    counts twice per native pass; for device tensors a damaged workspace shows as offset[-1] == -1 and is not raised."""
+    if (levels is None) == (interval is None):
+        raise ValueError("give exactly one of levels and interval")
+    dsm = _contour_dsm(dsm, grid)
+    if interval is not None:
+        levels = contour_levels(dsm, interval, base, nodata)
+    keys = _level_keys(levels)
+    z, as_numpy = _to_device(dsm, torch.float32)
+    dev = z.device
+    gh, gw = z.shape
+    parts, total, n_lines = [], 0, 0
+    for k0 in range(0, len(keys), MAX_CONTOUR_LEVELS):
+        part, nv = _contour_chunk(z, gw, gh, float(nodata), np.ascontiguousarray(keys[k0:k0 + MAX_CONTOUR_LEVELS], np.int32))
+        if parts:                                            # what one call over all the levels would have given
+            part["level_index"] += k0
+            part["offset"] = part["offset"][1:] + total
+            part["first_line"] = part["first_line"][1:] + n_lines
+        parts.append(part)
+        total += nv
+        n_lines += int(part["level_index"].numel())
+    if parts:
+        out = {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
+    else:
+        out = {"level_index": torch.empty(0, dtype=torch.int32, device=dev), "closed": torch.empty(0, dtype=torch.uint8, device=dev),
+               "offset": torch.zeros(1, dtype=torch.int32, device=dev), "first_line": torch.zeros(1, dtype=torch.int32, device=dev),
+               "vertices": torch.empty((0, 2), dtype=torch.float64, device=dev), "edge": torch.empty(0, dtype=torch.int32, device=dev)}
+    out["closed"] = out["closed"].bool()
+    out["level"] = torch.from_numpy(keys.astype(np.float64) / 512.0).to(dev)[out["level_index"].long()]
+    if grid is not None:
+        nl = int(out["level_index"].numel())
+        v, o = out["vertices"], out["offset"].long()
+        en = torch.stack([float(grid.e0) + v[:, 0] * float(grid.xres), float(grid.n0) - v[:, 1] * float(grid.yres)], dim=1)
+        out["vertices_en"] = en
+        line_of = torch.repeat_interleave(torch.arange(nl, device=dev), o[1:] - o[:-1], output_size=total)
+        at = torch.arange(total, device=dev)
+        last = at + 1 == o[1:][line_of]
+        d = en[torch.where(last, o[:-1][line_of], at + 1)] - en                       # a line's last vertex joins its first ...
+        length = torch.sqrt(d[:, 0] ** 2 + d[:, 1] ** 2)
+        length = torch.where(last & ~out["closed"][line_of], torch.zeros_like(length), length)      # ... if the line is closed
+        # a line's lengths added one after the other in vertex order: no atomics, so equal bits from run to run
+        out["length_m"] = torch.segment_reduce(length, "sum", lengths=o[1:] - o[:-1], unsafe=True) if nl else length.new_zeros(0)
+    out = {key: _back(as_numpy, t) for key, t in out.items()}
+    if as_numpy and int(out["offset"][-1]) != total:
+        raise _lib.SatMVSNativeError("smvs_dsm_contour_write gave up: an index out of range in its workspace")
+    return out
+
+
+def write_contours(path, lines, grid, projection=None):
+    """The lines of contours() as a GeoJSON FeatureCollection of LineStrings, one Feature per line in the lines' order; a closed
+    line repeats its first vertex.  Coordinates are east, north on `grid` (E = e0 + x xres, N = n0 - y yres); with `projection`
+    (a TransverseMercator) lon, lat through its EastNorth2latlon.  properties: level_m (the effective level), closed, length_m
+    (on the grid, in metres, a ring's closing segment included).  Plain json, no GIS library.  -> the number of features."""
+    host = {k: (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for k, t in lines.items()}
+    for key in ("level", "closed", "offset", "vertices"):
+        if key not in host:
+            raise ValueError("lines is the dict of contours(): entry %r is missing" % key)
+    level, closed, offset, v = host["level"], host["closed"], host["offset"], host["vertices"]
+    if v.ndim != 2 or v.shape[1] != 2 or len(offset) != len(level) + 1 or len(closed) != len(level) or int(offset[-1]) != len(v):
+        raise ValueError("lines is the dict of contours()")
+    _grid_checked(grid, "grid")
+    en = np.stack([float(grid.e0) + v[:, 0].astype(np.float64) * float(grid.xres),
+                   float(grid.n0) - v[:, 1].astype(np.float64) * float(grid.yres)], axis=1)
+    out = en
+    if projection is not None and len(en):
+        out = np.asarray(projection.EastNorth2latlon(en))[:, ::-1]
+    features = []
+    for i in range(len(level)):
+        a, b = int(offset[i]), int(offset[i + 1])
+        ends = [a] if closed[i] else []
+        if "length_m" in host:
+            length = host["length_m"][i]
+        else:
+            p = en[list(range(a, b)) + ends]
+            length = 0.0
+            for s in np.sqrt(((p[1:] - p[:-1]) ** 2).sum(axis=1)):
+                length += float(s)
+        properties = {"level_m": _json_value(level[i]), "closed": bool(closed[i]), "length_m": _json_value(length)}
+        features.append({"type": "Feature", "properties": properties,
+                         "geometry": {"type": "LineString", "coordinates": out[list(range(a, b)) + ends].tolist()}})
     with open(path, "w") as f:
         json.dump({"type": "FeatureCollection", "features": features}, f)
         f.write("\n")
