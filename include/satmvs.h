@@ -926,6 +926,59 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   and n_vertices both 0 or 2 n_lines <= n_vertices <= n_cross; inputs, outputs and workspace do not overlap; workspace:
  *   smvs_dsm_contour_workspace_bytes(gw, gh, n_levels, max_cross) bytes (0 = unsupported arguments): 8 bytes per cell (4 per
  *   lattice edge), 47 per crossing, the 16 KB level table and the scans' block sums. */
+/* Hydrology ("Hydrology"): depression filling, D8 directions, accumulation and basins on integer heights.
+ *   Cells, heights.  A cell is valid iff it is finite, != (float)nodata and |z| <= 32768.  q = llrint((double)z * 256), halves
+ *   to even.  The neighbours of a cell are numbered k = 0 .. 7: E, SE, S, SW, W, NW, N, NE; columns run east and rows south.  A
+ *   valid cell is an OUTLET iff one of its eight neighbours is off the grid or invalid: water leaves at the grid's edge and
+ *   into voids.
+ *   Flood key.  Every valid cell gets K = (w, d), ordered lexicographically: w the filled height in quanta, d a step count
+ *   within flats.  K is the unique solution of K(c) = (q_c, 0) at an outlet and K(c) = max((q_c, 0), min over the eight
+ *   neighbours n of (w_n, d_n + 1)) elsewhere: the priority-flood with an epsilon per step (Barnes et al. 2014) on integer
+ *   pairs.  The step is monotone and strictly raises its argument, so the solution is unique, and Dijkstra from the outlets
+ *   and any chaotic downward relaxation from +infinity reach it.  w is the classical filled surface (the lowest surface >= q
+ *   without pits, 8-connected); d = 0 exactly at outlets and at cells with a strictly lower neighbour in w, elsewhere one more
+ *   than the smallest d among the neighbours of equal w.  A key is the uint64 ((uint64)(w + 2^31) << 32) | d; an invalid
+ *   cell is all ones; +infinity, the start of the relaxation, is 0xfffffffe00000000.
+ *   Filled DTM.  filled: the cell's own z bits where w == q (untouched cells come back bit for bit), else (float)(w / 256.0),
+ *   exact.  depth: (float)((w - q) / 256.0), exact.  flat_dist: int32 d.  Invalid cells get (float)nodata, (float)nodata, -1.
+ *   D8 direction.  uint8: 255 invalid, 0 outlet, else k + 1 for the receiver k.  If some neighbour has w_n < w_c the receiver
+ *   is the one with the greatest slope (double)(w_c - w_n) / dist[k], one IEEE float64 division per neighbour compared as
+ *   doubles, ties to the lowest k; dist is a HOST array of 8 positive finite doubles (xres, hypot, yres, hypot, ... for a
+ *   DSMGrid; the library takes no square root).  Otherwise (a flat) the receiver is the neighbour with w_n == w_c and the
+ *   smallest d_n, ties to the lowest k; the key equation guarantees one with d_n = d_c - 1.  Along a flow step (w, d) strictly
+ *   falls, so the directions of a fixed point's keys form a forest rooted at the outlets.  (Keys that are no fixed point may
+ *   leave a cell with no lower or level neighbour: it gets 0.)
+ *   Receivers of an arbitrary direction grid.  Accumulation and basins take any uint8 grid: codes 9 .. 254 count as 255; a
+ *   cell with code 1 .. 8 whose target is off the grid or has code 255 is a root, like code 0; a cell that reaches no root is
+ *   CYCLIC (on a cycle or draining into one).  Roots are found by a pointer doubling of a fixed ceil(log2(gw gh)) + 1 rounds:
+ *   a cycle costs nothing extra and nothing can spin.
+ *   Accumulation.  acc int64 = the sum of weight over the cell and everything upstream of it; weight int32 (device) or null
+ *   for 1 per cell; invalid cells get 0; cyclic cells get -1 and set flag bit 0.  Exact integer sums (they wrap as int64 does).
+ *   Basins.  basin int32 = the number of the cell's root, the roots numbered 1 .. n in row-major order of the root cell.  With
+ *   a pour mask (uint8, non-zero = pour point) the pour cells that have a code 0 .. 8 are cut from their receivers and are the
+ *   only numbered roots; every other tree is 0.  Invalid cells are 0; cyclic cells are 0 and set flag bit 0.  n goes to a
+ *   device int.
+ * smvs_dsm_flood_begin writes the keys the relaxation starts from: outlets final, other valid cells +infinity, invalid cells
+ *   all ones.  smvs_dsm_flood_rounds runs `rounds` (1 .. 4096) global rounds and leaves in status (a device int) how many
+ *   tiles changed in the last one: 0 means the keys are the solution.  A round is one workgroup per tile of 32 x 32 cells,
+ *   which relaxes the tile in LDS against a halo of one cell until the tile is at its own fixed point, and writes the
+ *   interior back.  Keys only fall and never below the solution, so a round reads its neighbours' keys as they are.  The
+ *   caller loops; a synchronous relaxation finalises at least one cell a round, so gw gh + 2 rounds bound any grid.
+ *   smvs_dsm_flood_read turns keys into filled, depth and flat_dist (each may be null).
+ * smvs_dsm_flow_dir: keys and dist -> codes, one lane per cell.
+ * smvs_dsm_flow_accumulate ranks an Euler tour of the forest (two elements per cell, successors from the codes of the cell's
+ *   and its receiver's neighbours, children in the order of k) by one pointer doubling with int64 suffix sums of
+ *   ceil(log2(2 gw gh)) rounds, whatever the grid holds: the number of launches grows with log(gw gh), not with the longest
+ *   river.  smvs_dsm_flow_basins numbers the roots by a scan.  No host synchronisation in any entry.  Every workspace word a
+ *   kernel reads was written by a kernel of the same call (a workspace full of anything will do); the only atomic is an
+ *   integer OR into the flag: everything depends on the inputs alone, equal bits from run to run and on any stream, and equal
+ *   to the Python statement of this rule.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers (filled, depth, flat_dist, weight and pour may be
+ *   null); gw, gh >= 1, gw * gh < 2^30 (the tour's 2 gw gh elements are int32); 1 <= rounds <= 4096; dist finite and > 0;
+ *   inputs, outputs and workspace do not overlap; workspace: smvs_dsm_flood_workspace_bytes(gw, gh) = 16 KB of round
+ *   counters for the flood, smvs_dsm_flow_workspace_bytes(gw, gh) for accumulate and basins (0 = unsupported arguments): 56
+ *   bytes per cell (receiver 4, root pointer 4, two copies of the tour's successors 16 and sums 32) and the scan's block
+ *   sums.  No kernel uses scratch. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -1012,6 +1065,21 @@ int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float nodata, const
                            int n_cross, int n_lines, int n_vertices, int* line_level, unsigned char* line_closed,
                            int* offset, int* first_line, double* vertices, int* vertex_edge /* may be null */,
                            void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_flood_workspace_bytes(int gw, int gh);
+int smvs_dsm_flood_begin(const float* dsm, int gw, int gh, float nodata, unsigned long long* keys,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_flood_rounds(const float* dsm, int gw, int gh, float nodata, unsigned long long* keys, int rounds,
+                          int* status, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_flood_read(const float* dsm, int gw, int gh, float nodata, const unsigned long long* keys,
+                        float* filled /* may be null */, float* depth /* may be null */, int* flat_dist /* may be null */,
+                        void* stream);
+int smvs_dsm_flow_dir(const unsigned long long* keys, int gw, int gh, const double* dist /* HOST, 8 */,
+                      unsigned char* dir, void* stream);
+size_t smvs_dsm_flow_workspace_bytes(int gw, int gh);
+int smvs_dsm_flow_accumulate(const unsigned char* dir, const int* weight /* may be null */, int gw, int gh,
+                             long long* acc, int* flag, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_flow_basins(const unsigned char* dir, const unsigned char* pour /* may be null */, int gw, int gh,
+                         int* basin, int* n_out, int* flag, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

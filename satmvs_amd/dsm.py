@@ -32,6 +32,15 @@ and the terrain as vector data, contour lines at many levels in one call:
     lines = contours(dtm, interval=2.5, grid=grid)             # ordered float64 vertex lists: open chains and closed rings
     write_contours("contours.geojson", lines, grid)            # a FeatureCollection of LineStrings: level_m, closed, length_m
 
+and water over the terrain: depressions filled, D8 directions, accumulation, catchments (what every DTM package offers):
+
+    filled, depth, flat = fill_depressions(dtm, return_depth=True)   # the lowest surface without pits; depth = filled - dtm, exact
+    direction = flow_direction(dtm, grid)                      # uint8: 0 outlet, k + 1 towards E, SE, S, SW, W, NW, N, NE, 255 invalid
+    acc = flow_accumulation(direction, grid=grid)              # upstream area [m^2] (cells without a grid; int32 weights)
+    basin, n = basins(direction, pour_points=[(row, col)])     # catchments of the pour points (of every outlet without them)
+    rivers = streams(acc, 1e4)                                 # the cells that drain 1 ha or more
+    labels, stats, depth = depressions(dtm, grid)              # >= 0.5 m deep, >= 50 m^2, as objects: into outlines(), write_geojson()
+
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
     reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
@@ -89,6 +98,10 @@ along vertical edges with integer XOR atomics and takes a running XOR along the 
 smvs_dsm_contour_count / _write number the crossings (level, lattice edge) by a scan over the edges of the levels that cross
 each, link every crossing to its successor in the square it enters, rank open chains and rings by the same pointer doubling,
 and write float64 vertices; all levels of a call are in flight at once.
+smvs_dsm_flood_begin / _rounds / _read fill depressions as a monotone relaxation of 64-bit keys (filled height, steps within a
+flat) over tiles of 32 x 32 cells in LDS, rounds in batches with one read of the device per batch; smvs_dsm_flow_dir is one
+lane per cell; smvs_dsm_flow_accumulate ranks an Euler tour of the flow forest by one pointer doubling with int64 suffix sums
+and smvs_dsm_flow_basins numbers the roots by a scan: launches follow log(cells), not the longest river.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1249,6 +1262,258 @@ def write_contours(path, lines, grid, projection=None):
         json.dump({"type": "FeatureCollection", "features": features}, f)
         f.write("\n")
     return len(features)
+
+
+# ---- hydrology: depression filling, D8 directions, accumulation, basins ---------------------------------------------------------
+MAX_HYDRO_CELLS = 2 ** 30                                         # the Euler tour's 2 gw gh elements in an int32
+FLOOD_BATCH = 8                                                   # rounds of the first batch; one read of the device's status per batch
+MAX_FLOOD_BATCH = 4096                                            # smvs_dsm_flood_rounds takes no more
+FLOW_ENCODINGS = ("index", "esri")
+
+
+def _hydro_dsm(dsm, grid=None):
+    """A (gh, gw) float32 DSM, never converted (filling gives untouched cells back bit for bit), fewer than 2^30 cells."""
+    dsm = _dsm_bits(dsm)
+    if int(dsm.shape[0]) * int(dsm.shape[1]) >= MAX_HYDRO_CELLS:
+        raise ValueError("hydrology takes fewer than 2^30 cells, got %d x %d" % (int(dsm.shape[0]), int(dsm.shape[1])))
+    if grid is not None:
+        _on_grid(dsm, _grid_checked(grid, "grid"))
+    return dsm
+
+
+def _flood(z, nodata, batch=None):
+    """The flood keys of a device DSM -> (keys (gh, gw) int64 holding the uint64 words, rounds run)."""
+    dev = z.device
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_flood_workspace_bytes(gw, gh)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keys = torch.empty((gh, gw), dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_flood_begin", z, gw, gh, nodata, keys, ws, nbytes)
+    run, step, grow = 0, batch or FLOOD_BATCH, batch is None
+    while True:
+        _call(dev, "smvs_dsm_flood_rounds", z, gw, gh, nodata, keys, step, status, ws, nbytes)
+        run += step
+        if int(status.item()) == 0:
+            return keys, run
+        if run > gw * gh + 2:
+            raise _lib.SatMVSNativeError("smvs_dsm_flood_rounds: tiles still change after %d rounds, more than the grid has cells (%d)" % (run, gw * gh))
+        if grow:
+            step = min(2 * step, MAX_FLOOD_BATCH)
+
+
+def fill_depressions(dsm, nodata=-999.0, return_depth=False, return_rounds=False, batch=None):
+    """A DTM without pits (include/satmvs.h, "Hydrology"): dsm (gh, gw) float32, never converted, fewer
+    than 2^30 cells; valid = finite, != nodata and |z| <= 32768 m.  Heights count in steps of 2^-8 m; water leaves at the grid's
+    edge and into voids; the result is the lowest surface >= the input from which every cell drains, 8-connected.  A cell the
+    fill does not raise comes back with its own bits, a raised one as a multiple of 2^-8 m; invalid cells come back as nodata.
+    -> filled (gh, gw) float32; with return_depth also depth (gh, gw) float32 = filled - input, exact, >= 0 (nodata where
+    invalid) and flat_dist (gh, gw) int32, the steps to the flat's way out (0 where a strictly lower neighbour or an outlet is,
+    -1 where invalid); with return_rounds also the global rounds run, a multiple of the batches.  The host reads the device's
+    status once per batch of rounds (8, then doubling; batch=k fixes it).  numpy if the DSM came as numpy, tensors otherwise."""
+    dsm = _hydro_dsm(dsm)
+    if batch is not None:
+        batch = _int_checked(batch, "batch", 1, MAX_FLOOD_BATCH)
+    z, as_numpy = _to_device(dsm)
+    gh, gw = z.shape
+    keys, rounds = _flood(z, float(nodata), batch)
+    filled = torch.empty_like(z)
+    depth = torch.empty_like(z) if return_depth else None
+    flat = torch.empty((gh, gw), dtype=torch.int32, device=z.device) if return_depth else None
+    _call(z.device, "smvs_dsm_flood_read", z, gw, gh, float(nodata), keys, filled, depth, flat)
+    out = (filled,) + ((depth, flat) if return_depth else ())
+    out = _back(as_numpy, *out)
+    if not return_rounds:
+        return out
+    return (out if isinstance(out, tuple) else (out,)) + (rounds,)
+
+
+def flow_codes(encoding="index"):
+    """The uint8 table that turns the library's direction codes into `encoding`: entry c is the code written for c.  "index":
+    the codes as they are (0 outlet, k + 1 towards neighbour k = E, SE, S, SW, W, NW, N, NE, 255 invalid).  "esri": 1, 2, 4, ...,
+    128 for E, SE, ..., NE, 0 for an outlet, 255 for invalid (ArcGIS Hydrology's numbers)."""
+    if encoding not in FLOW_ENCODINGS:
+        raise ValueError("encoding must be one of %s, got %r" % (FLOW_ENCODINGS, encoding))
+    table = np.full(256, 255, np.uint8)
+    table[:9] = np.arange(9) if encoding == "index" else [0] + [1 << k for k in range(8)]
+    return table
+
+
+def flow_distances(grid):
+    """The eight step lengths E, SE, S, SW, W, NW, N, NE on `grid` [m], float64: xres, yres and np.hypot(xres, yres)."""
+    _grid_checked(grid, "grid")
+    x, y = float(grid.xres), float(grid.yres)
+    h = float(np.hypot(x, y))
+    return np.array([x, h, y, h, x, h, y, h], np.float64)
+
+
+def flow_direction(dsm, grid, nodata=-999.0, encoding="index"):
+    """D8 directions of a DSM (include/satmvs.h, "Hydrology"): the flood of fill_depressions(), then every cell's receiver:
+    the neighbour down the steepest slope of the FILLED surface, (w_c - w_n) / distance as one float64 division with the
+    distances of flow_distances(grid), ties to the lowest k; on a flat the neighbour one step nearer the flat's way out.  The
+    directions form a forest rooted at the outlets: no cycles, no pits.
+    -> (gh, gw) uint8 in `encoding` (flow_codes()): "index" 0 outlet, k + 1, 255 invalid; "esri" 1, 2, 4, ..., 128.
+    flow_accumulation() and basins() take the "index" codes.  numpy if the DSM came as numpy, a device tensor otherwise."""
+    dsm = _hydro_dsm(dsm, grid)
+    table = flow_codes(encoding)
+    dist = flow_distances(grid)
+    z, as_numpy = _to_device(dsm)
+    gh, gw = z.shape
+    keys, _ = _flood(z, float(nodata))
+    codes = torch.empty((gh, gw), dtype=torch.uint8, device=z.device)
+    _call(z.device, "smvs_dsm_flow_dir", keys, gw, gh, dist, codes)
+    if encoding != "index":
+        codes = torch.from_numpy(table).to(z.device)[codes.long()]
+    return _back(as_numpy, codes)
+
+
+def _codes_checked(direction):
+    if not isinstance(direction, torch.Tensor):
+        direction = np.asarray(direction)
+    if direction.ndim != 2:
+        raise ValueError("directions are (gh, gw), got shape %s" % (tuple(direction.shape),))
+    if direction.dtype not in (np.uint8, torch.uint8):
+        raise ValueError("directions are uint8 codes (flow_codes('index')), got %s" % (direction.dtype,))
+    gh, gw = int(direction.shape[0]), int(direction.shape[1])
+    if gh < 1 or gw < 1 or gh * gw >= MAX_HYDRO_CELLS:
+        raise ValueError("directions have positive sizes and fewer than 2^30 cells, got %d x %d" % (gh, gw))
+    return direction
+
+
+def _flow_workspace(d):
+    gh, gw = d.shape
+    nbytes = _lib.load().smvs_dsm_flow_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported direction grid: %d x %d cells" % (gw, gh))
+    return torch.empty(nbytes, dtype=torch.uint8, device=d.device), nbytes
+
+
+def flow_accumulation(direction, weights=None, grid=None, cycles="raise"):
+    """Flow accumulation over a direction grid (include/satmvs.h, "Hydrology"): direction (gh, gw) uint8 "index" codes, from
+    flow_direction() or edited; codes 9 .. 254 count as 255; a code whose target is off the grid or invalid makes a root.
+    Every cell gets the sum of `weights` ((gh, gw) int32, never converted; None: 1 per cell) over itself and everything
+    upstream; invalid cells get 0.  A cell on a cycle, or draining into one, has no sum: ValueError, or with cycles="mark" the
+    value -1 in every such cell.  -> (gh, gw) int64 [cells, or units of the weights]; with grid (a DSMGrid of that shape)
+    float64 [m^2] = cells xres yres (and -1 stays -1).  Exact integer sums by an Euler tour of the flow forest: the number of
+    launches follows log(gw gh), not the longest river.  numpy if the directions came as numpy, a device tensor otherwise."""
+    direction = _codes_checked(direction)
+    if cycles not in ("raise", "mark"):
+        raise ValueError("cycles must be 'raise' or 'mark', got %r" % (cycles,))
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor):
+            weights = np.asarray(weights)
+        if weights.dtype not in (np.int32, torch.int32) or tuple(weights.shape) != tuple(direction.shape):
+            raise ValueError("weights are int32 of the directions' shape, got %s %s" % (weights.dtype, tuple(weights.shape)))
+    if grid is not None:
+        _on_grid(direction, _grid_checked(grid, "grid"))
+    d, as_numpy = _to_device(direction)
+    dev = d.device
+    w = None if weights is None else _to_device(weights, dev=dev)[0]
+    gh, gw = d.shape
+    ws, nbytes = _flow_workspace(d)
+    acc = torch.empty((gh, gw), dtype=torch.int64, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_flow_accumulate", d, w, gw, gh, acc, flag, ws, nbytes)
+    cyclic = bool(int(flag.item()) & 1)
+    if cyclic and cycles == "raise":
+        raise ValueError("the directions hold a cycle: some cells reach no root; cycles='mark' gives them -1")
+    if grid is not None:
+        area = acc.double() * (float(grid.xres) * float(grid.yres))
+        acc = torch.where(_cyclic_cells(d, ws, nbytes), torch.full_like(area, -1.0), area) if cyclic else area
+    return _back(as_numpy, acc)
+
+
+def _cyclic_cells(d, ws, nbytes):
+    """The cells of a device direction grid without a root, as the basins see them (valid, and labelled 0 without pour points)."""
+    gh, gw = d.shape
+    basin = torch.empty((gh, gw), dtype=torch.int32, device=d.device)
+    word = torch.empty(2, dtype=torch.int32, device=d.device)
+    _call(d.device, "smvs_dsm_flow_basins", d, None, gw, gh, basin, word[:1], word[1:], ws, nbytes)
+    return (d <= 8) & (basin == 0)
+
+
+def _pour_checked(pour_points, shape):
+    """(whether it is a mask, the mask or the (m, 2) list), checked before any device work."""
+    gh, gw = shape
+    p = pour_points if isinstance(pour_points, torch.Tensor) else np.asarray(pour_points)
+    if tuple(p.shape) == (gh, gw):
+        return True, _mask_checked(p)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("pour_points is a (gh, gw) mask or an (m, 2) list of (row, col), got shape %s" % (tuple(p.shape),))
+    integral = not (p.is_floating_point() or p.is_complex() or p.dtype == torch.bool) if isinstance(p, torch.Tensor) else np.issubdtype(p.dtype, np.integer)
+    if not integral:
+        raise ValueError("pour points (row, col) are integers, got %s" % (p.dtype,))
+    if p.shape[0] and (int(p.min()) < 0 or int(p[:, 0].max()) >= gh or int(p[:, 1].max()) >= gw):
+        raise ValueError("pour points must lie on the %d x %d grid" % (gh, gw))
+    return False, p
+
+
+def _pour_mask(is_mask, p, shape, dev):
+    if is_mask:
+        if not isinstance(p, torch.Tensor):
+            p = np.not_equal(p, 0).view(np.uint8)
+        return (_to_device(p, dev=dev)[0] != 0).to(torch.uint8).contiguous()
+    rc = torch.as_tensor(p).to(dev).long()
+    mask = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    mask[rc[:, 0], rc[:, 1]] = 1
+    return mask
+
+
+def basins(direction, pour_points=None):
+    """Catchments of a direction grid (include/satmvs.h, "Hydrology"): every cell gets the number of the root it drains to,
+    the roots numbered 1 .. n in row-major order; invalid cells and cells on or into a cycle get 0.  With pour_points, a
+    (gh, gw) mask (bool or integer, non-zero = pour point) or an (m, 2) integer list of (row, col): the pour cells are cut from
+    their receivers and are the only numbered roots, so a pour point upstream of another splits its river, and everything that
+    passes no pour point is 0; a pour point on an invalid cell counts for nothing.  A (2, 2) grid takes a (2, 2) array as a mask.
+    -> (labels (gh, gw) int32, n); label_stats(), outlines() and write_geojson() take them.  numpy if the directions came as
+    numpy, a device tensor otherwise.  Reading n is the one synchronisation."""
+    direction = _codes_checked(direction)
+    pour = None if pour_points is None else _pour_checked(pour_points, tuple(direction.shape))
+    d, as_numpy = _to_device(direction)
+    dev = d.device
+    gh, gw = d.shape
+    if pour is not None:
+        pour = _pour_mask(*pour, (gh, gw), dev)
+    ws, nbytes = _flow_workspace(d)
+    basin = torch.empty((gh, gw), dtype=torch.int32, device=dev)
+    word = torch.empty(2, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_flow_basins", d, pour, gw, gh, basin, word[:1], word[1:], ws, nbytes)
+    return _back(as_numpy, basin), int(word[0].item())
+
+
+def streams(acc, threshold):
+    """The cells whose accumulation reaches `threshold` (in the units of acc: cells, or m^2 with a grid) -> bool mask; torch
+    or numpy as acc comes."""
+    threshold = _finite(threshold, "threshold")
+    if not isinstance(acc, torch.Tensor):
+        acc = np.asarray(acc)
+    if acc.ndim != 2:
+        raise ValueError("acc is (gh, gw), got shape %s" % (tuple(acc.shape),))
+    return acc >= threshold
+
+
+def depressions(dsm, grid, min_depth=0.5, min_area_m2=50.0, nodata=-999.0):
+    """The depressions of a DSM as objects: fill_depressions(return_depth=True); foreground = depth >= float32(min_depth);
+    label() (8-connected); label_stats(values=depth, grid=grid); sieve_labels() at ceil(min_area_m2 / (xres yres)) cells, as
+    extract_objects() is built.  In a satellite DTM most are noise and filled voids, which makes depth a quality product.
+    -> (labels (gh, gw) int32, stats: label_stats' dict of the depressions that stay, max = the greatest depth, volume = the
+    water they hold [m^3], depth (gh, gw) float32).  The table goes straight into outlines() / write_geojson().  numpy if the
+    DSM came as numpy, device tensors otherwise."""
+    dsm = _hydro_dsm(dsm, grid)
+    min_depth, min_area_m2 = float(min_depth), float(min_area_m2)
+    if not (math.isfinite(min_depth) and min_depth > 0.0):
+        raise ValueError("min_depth must be finite and > 0, got %r" % min_depth)
+    if not (math.isfinite(min_area_m2) and min_area_m2 >= 0.0):
+        raise ValueError("min_area_m2 must be finite and >= 0, got %r" % min_area_m2)
+    min_cells = _int_checked(int(math.ceil(min_area_m2 / (float(grid.xres) * float(grid.yres)))), "min_area_m2 in cells", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    _, depth, _ = fill_depressions(z, nodata, return_depth=True)
+    fg = torch.isfinite(depth) & (depth != float(np.float32(nodata))) & (depth >= float(np.float32(min_depth)))
+    labels, n = label(fg, 8)
+    stats = label_stats(labels, n, values=depth, grid=grid, nodata=nodata)
+    labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
+    stats = {k: t[kept] for k, t in stats.items()}
+    return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}, _back(as_numpy, depth)
 
 
 # ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
