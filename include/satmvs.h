@@ -979,6 +979,47 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   counters for the flood, smvs_dsm_flow_workspace_bytes(gw, gh) for accumulate and basins (0 = unsupported arguments): 56
  *   bytes per cell (receiver 4, root pointer 4, two copies of the tour's successors 16 and sums 32) and the scan's block
  *   sums.  No kernel uses scratch. */
+/* Stream network ("Stream network"): Strahler orders, links and flow length over a direction grid.
+ *   Inputs.  dir (gh, gw) uint8 "index" codes with the meaning smvs_dsm_flow_accumulate gives them: codes 9 .. 254 count as
+ *   255, a target off the grid or invalid makes a root, edited grids with cycles are allowed.  mask (gh, gw) uint8, non-zero =
+ *   a stream cell; any mask is taken, not only acc >= t.
+ *   Stream cells.  S = the cells with mask != 0 that are tree cells (a code 0 .. 8 and a root).  Cyclic cells are never in S;
+ *   if the grid holds a cyclic cell, masked or not, flag bit 0 is set, as in accumulate.
+ *   Induced forest.  down(c) = c's receiver if that is in S; otherwise c has none and is a MOUTH.  in(c) = the number of cells
+ *   u in S with down(u) = c.  A gap in the mask cuts the network: nothing upstream of a gap counts below it.
+ *   Strahler order.  order(c) = 1 if in(c) = 0.  Otherwise let m be the greatest order among the cells flowing into c:
+ *   order(c) = m + 1 if at least two of them have order m, else m.  The order map is uint8, 0 outside S; below 2^30 cells the
+ *   order is at most 30.
+ *   Links.  A cell of S is a HEAD iff in(c) != 1 (a source or a junction); every head starts one link.  A cell with in = 1
+ *   belongs to the link of the one cell that flows into it.  A link's cells are listed downstream from the head; its last
+ *   cell e has no down (a mouth) or in(down(e)) >= 2.  next_link = the link that down(e) heads, or -1.  Links are numbered
+ *   0 .. n_links - 1 in row-major order of their head cells.
+ *   Vertices.  int32 (col, row) of the link's cells, head first, then down(e) when it exists: adjacent links share the
+ *   junction and the lines connect.  A link of one cell at a mouth has one vertex; it stays in the tables.
+ *   Per link: head (the cell index), order, next_link, offset (n_links + 1 entries into the vertices), steps int32
+ *   (n_links, 3) = the E-W, N-S and diagonal segments of its polyline, the closing one included.  link map int32 (gh, gw):
+ *   link number + 1 on S, 0 elsewhere.  counts, a device int[4]: stream cells, links, vertices, highest order.
+ *   Flow length.  steps int32 (gh, gw, 3): the E-W, N-S and diagonal steps of the cell's path to its root over the whole
+ *   direction grid; a root has (0, 0, 0); invalid and cyclic cells get -1, cyclic ones set flag bit 0.  The length in metres
+ *   is the caller's: (n_ew xres + n_ns yres) + n_diag hypot(xres, yres); the library handles the integers only.
+ * smvs_dsm_stream_order runs the network pass and writes order, link_map (may be null) and counts.  The host reads counts
+ *   once, allocates, and calls smvs_dsm_stream_write with n_links = counts[1] and n_vertices = counts[2].  WRITE REDOES THE
+ *   PASS: it reads nothing of an earlier call, so the workspace may be another one or may have been used in between, and a
+ *   workspace full of anything will do for both.  If n_links or n_vertices differ from the network's counts (too small, for
+ *   one) it writes -1 into offset[n_links] and nothing else; the return value is SMVS_OK, as nothing is read back.
+ *   The pass: receivers and roots as in accumulate; an Euler tour of the induced forest, the trees chained in row-major order
+ *   of their mouths, ranked by one doubling of ceil(log2(2 gw gh)) rounds; at most min(30, floor(log2(gw gh))) order rounds of
+ *   one mark kernel, one scan of the marks at their tour positions and one promotion (a cell rises to k + 1 iff it or
+ *   something upstream of it has two inflowing cells of order >= k), which leave at once on a device counter after the first
+ *   round without a mark; heads numbered by a scan; (head, distance) per cell by ceil(log2(gw gh)) + 1 rounds of an in-place
+ *   doubling.  smvs_dsm_flow_length is one doubling of ceil(log2(gw gh)) rounds with the three counts as sums.  The number
+ *   of launches depends on gw gh alone, never on the longest river or link.  No host synchronisation in any entry; every
+ *   workspace word a kernel reads was written by a kernel of the same call; integer atomics only (adds into the counts and
+ *   the links' step counts, an OR into the flag), so everything is equal bits from run to run and on any stream.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null pointers (link_map may be null); gw, gh >= 1, gw * gh < 2^30;
+ *   0 <= n_links <= gw gh, 0 <= n_vertices <= 2 gw gh; inputs, outputs and workspace do not overlap; workspace:
+ *   smvs_dsm_stream_workspace_bytes(gw, gh) for all three (0 = unsupported arguments): 54 bytes per cell, the scans' block
+ *   sums and 512 bytes of counters; flow length uses the first 32 per cell.  No kernel uses scratch. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -1080,6 +1121,15 @@ int smvs_dsm_flow_accumulate(const unsigned char* dir, const int* weight /* may 
                              long long* acc, int* flag, void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_flow_basins(const unsigned char* dir, const unsigned char* pour /* may be null */, int gw, int gh,
                          int* basin, int* n_out, int* flag, void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_stream_workspace_bytes(int gw, int gh);
+int smvs_dsm_stream_order(const unsigned char* dir, const unsigned char* mask, int gw, int gh, unsigned char* order,
+                          int* link_map /* may be null */, int* counts /* device, 4 */, int* flag,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_stream_write(const unsigned char* dir, const unsigned char* mask, int gw, int gh, int n_links, int n_vertices,
+                          int* head, int* link_order, int* next_link, int* offset, int* vertices, int* steps,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_flow_length(const unsigned char* dir, int gw, int gh, int* steps, int* flag,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,9 @@ _SIGNATURES = {
     "smvs_dsm_flow_dir": [_vp, _i, _i, _vp, _vp, _vp],
     "smvs_dsm_flow_accumulate": [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_flow_basins": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_stream_order": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_stream_write": [_vp, _vp, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp],
+    "smvs_dsm_flow_length": [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
 }
 _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": [_i], "smvs_red_workspace_bytes": [_i] * 4,
                "smvs_red_pred_workspace_bytes": [_i] * 4, "smvs_costreg_packed_floats": [_i],
@@ -127,7 +130,8 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_dsm_shadow_workspace_bytes": [_i] * 2, "smvs_dsm_horizon_workspace_bytes": [_i] * 3,
                "smvs_dsm_outline_workspace_bytes": [_i] * 3,
                "smvs_dsm_simplify_workspace_bytes": [_i] * 2, "smvs_dsm_contour_workspace_bytes": [_i] * 4,
-               "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2}
+               "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2,
+               "smvs_dsm_stream_workspace_bytes": [_i] * 2}
 # host-side queries that return a code, not a status: called on load() directly, never through call()
 _QUERY_FUNCS = {"smvs_conv3x3_variant": [_i] * 8, "smvs_conv3d_variant": [_i] * 7}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + list(_QUERY_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",

@@ -40,6 +40,9 @@ and water over the terrain: depressions filled, D8 directions, accumulation, cat
     basin, n = basins(direction, pour_points=[(row, col)])     # catchments of the pour points (of every outlet without them)
     rivers = streams(acc, 1e4)                                 # the cells that drain 1 ha or more
     labels, stats, depth = depressions(dtm, grid)              # >= 0.5 m deep, >= 50 m^2, as objects: into outlines(), write_geojson()
+    links = stream_links(direction, rivers, grid=grid)         # Strahler orders, links with next_link, polylines, length_m
+    write_streams("streams.geojson", links, grid, proj)        # or extract_streams(dtm, grid) for the whole chain
+    metres = flow_length(direction, grid=grid)                 # every cell's way to its root (step counts without a grid)
 
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
@@ -102,6 +105,9 @@ smvs_dsm_flood_begin / _rounds / _read fill depressions as a monotone relaxation
 flat) over tiles of 32 x 32 cells in LDS, rounds in batches with one read of the device per batch; smvs_dsm_flow_dir is one
 lane per cell; smvs_dsm_flow_accumulate ranks an Euler tour of the flow forest by one pointer doubling with int64 suffix sums
 and smvs_dsm_flow_basins numbers the roots by a scan: launches follow log(cells), not the longest river.
+smvs_dsm_stream_order / _write rank an Euler tour of the forest induced on the stream cells, raise the Strahler order by one
+per round through a scan of junction marks at their tour positions, and find every cell's link head by an in-place pointer
+doubling; smvs_dsm_flow_length is one doubling over the forest with the three step counts as sums.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1514,6 +1520,190 @@ def depressions(dsm, grid, min_depth=0.5, min_area_m2=50.0, nodata=-999.0):
     labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
     stats = {k: t[kept] for k, t in stats.items()}
     return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}, _back(as_numpy, depth)
+
+
+# ---- stream network: Strahler orders, links as polylines, flow length -----------------------------------------------------------
+STREAM_KEYS = ("order_map", "link", "head", "order", "next_link", "offset", "vertices", "steps")
+
+
+def _cycles_checked(cycles):
+    if cycles not in ("raise", "mark"):
+        raise ValueError("cycles must be 'raise' or 'mark', got %r" % (cycles,))
+    return cycles
+
+
+def _stream_inputs(direction, stream, cycles, grid=None):
+    """(codes, mask as uint8 0 / 1, as_numpy), both on the directions' device, everything checked before any device work."""
+    direction = _codes_checked(direction)
+    _cycles_checked(cycles)
+    stream = _mask_checked(stream)
+    if tuple(stream.shape) != tuple(direction.shape):
+        raise ValueError("stream mask shape %s differs from the directions' %s" % (tuple(stream.shape), tuple(direction.shape)))
+    if grid is not None:
+        _on_grid(direction, _grid_checked(grid, "grid"))
+    if not isinstance(stream, torch.Tensor):
+        stream = np.not_equal(stream, 0).view(np.uint8)
+    d, as_numpy = _to_device(direction)
+    m = (_to_device(stream, dev=d.device)[0] != 0).to(torch.uint8).contiguous()
+    return d, m, as_numpy
+
+
+def _stream_workspace(d):
+    gh, gw = d.shape
+    nbytes = _lib.load().smvs_dsm_stream_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported direction grid: %d x %d cells" % (gw, gh))
+    return torch.empty(nbytes, dtype=torch.uint8, device=d.device), nbytes
+
+
+def _stream_order(d, m, ws, nbytes, cycles, want_link=True):
+    """smvs_dsm_stream_order on device tensors -> order map, link map (or None), the four counts read once."""
+    dev = d.device
+    gh, gw = d.shape
+    order = torch.empty((gh, gw), dtype=torch.uint8, device=dev)
+    link = torch.empty((gh, gw), dtype=torch.int32, device=dev) if want_link else None
+    word = torch.empty(5, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_stream_order", d, m, gw, gh, order, link, word[:4], word[4:], ws, nbytes)
+    word = [int(x) for x in word.tolist()]
+    if word[4] & 1 and cycles == "raise":
+        raise ValueError("the directions hold a cycle: some cells reach no root; cycles='mark' leaves them out of the network")
+    return order, link, word[:4]
+
+
+def _steps_length(steps, grid):
+    """(n_ew xres + n_ns yres) + n_diag hypot(xres, yres), float64, one rounding per operation in exactly that order."""
+    s = steps.double()
+    return (s[..., 0] * float(grid.xres) + s[..., 1] * float(grid.yres)) + s[..., 2] * float(np.hypot(float(grid.xres), float(grid.yres)))
+
+
+def stream_order(direction, stream, cycles="raise"):
+    """Strahler orders of a stream mask over a direction grid (include/satmvs.h, "Stream network"):
+    direction (gh, gw) uint8 "index" codes as flow_accumulation() takes them; stream (gh, gw), bool or any integer dtype,
+    non-zero = a stream cell, from streams() or any mask at all.  The stream cells are the masked cells that reach a root; a
+    cell flows into its receiver if that is a stream cell too, so a gap in the mask cuts the network and nothing upstream of it
+    counts below.  A cell without inflow has order 1; otherwise, with m the greatest order flowing in, m + 1 if two inflows
+    have it and m if one.  A cell on a cycle, or draining into one, is no stream cell: ValueError if the grid holds one (masked
+    or not), unless cycles="mark".  -> (gh, gw) uint8, 0 outside the network.  The number of launches follows log(gw gh), not
+    the longest river.  numpy if the directions came as numpy, a device tensor otherwise."""
+    d, m, as_numpy = _stream_inputs(direction, stream, cycles)
+    ws, nbytes = _stream_workspace(d)
+    order, _, _ = _stream_order(d, m, ws, nbytes, cycles, want_link=False)
+    return _back(as_numpy, order)
+
+
+def stream_links(direction, stream, grid=None, cycles="raise"):
+    """The stream network as links (include/satmvs.h, "Stream network"): inputs and orders as stream_order().  A stream cell is
+    a head iff the number of stream cells flowing into it is not 1 (a source or a junction); every head starts one link, which
+    runs downstream until the next cell is a junction or there is none (a mouth).  Links are numbered 0 .. n - 1 in row-major
+    order of their heads.  -> dict:
+      order_map uint8 (gh, gw); link int32 (gh, gw), link number + 1 on the network and 0 elsewhere: label_stats() takes it
+      head int32 (n), the head's cell index row gw + col; order int32 (n); next_link int32 (n), the link the last cell flows
+        into, -1 at a mouth; offset int32 (n + 1) into vertices
+      vertices int32 (n_vertices, 2) col, row: a link's cells, head first, then the junction it flows into, so that lines
+        connect; a link of one cell at a mouth has one vertex
+      steps int32 (n, 3): the E-W, N-S and diagonal segments of the polyline
+      with grid (a DSMGrid of the directions' shape): vertices_en float64 (n_vertices, 2) east, north at cell centres and
+        length_m float64 (n) = (n_ew xres + n_ns yres) + n_diag hypot(xres, yres), exact in its integers.
+    Everything depends on the two inputs alone, bit for bit.  numpy if the directions came as numpy, device tensors otherwise.
+    The host reads the device's counts once between the two native passes."""
+    d, m, as_numpy = _stream_inputs(direction, stream, cycles, grid)
+    dev = d.device
+    gh, gw = d.shape
+    ws, nbytes = _stream_workspace(d)
+    order_map, link, (_, nl, nv, _) = _stream_order(d, m, ws, nbytes, cycles)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)                # noqa: E731
+    out = {"order_map": order_map, "link": link, "head": i32(nl), "order": i32(nl), "next_link": i32(nl), "offset": torch.zeros(nl + 1, dtype=torch.int32, device=dev),
+           "vertices": i32(nv, 2), "steps": i32(nl, 3)}
+    if nl:
+        _call(dev, "smvs_dsm_stream_write", d, m, gw, gh, nl, nv, out["head"], out["order"], out["next_link"], out["offset"], out["vertices"],
+              out["steps"], ws, nbytes)
+        if int(out["offset"][nl].item()) != nv:
+            raise _lib.SatMVSNativeError("smvs_dsm_stream_write: the network's counts differ from n_links = %d, n_vertices = %d" % (nl, nv))
+    if grid is not None:
+        v = out["vertices"].double()
+        out["vertices_en"] = torch.stack([float(grid.e0) + v[:, 0] * float(grid.xres), float(grid.n0) - v[:, 1] * float(grid.yres)], dim=1)
+        out["length_m"] = _steps_length(out["steps"], grid)
+    return {k: _back(as_numpy, t) for k, t in out.items()}
+
+
+def flow_length(direction, grid=None, cycles="raise"):
+    """The length of every cell's flow path to its root (include/satmvs.h, "Stream network"): direction as flow_accumulation()
+    takes it.  -> int32 (gh, gw, 3), the E-W, N-S and diagonal steps of the path; a root has (0, 0, 0); invalid cells get -1, and
+    so do cells on or into a cycle under cycles="mark" (ValueError otherwise).  With grid (a DSMGrid of that shape): float64
+    (gh, gw) metres = (n_ew xres + n_ns yres) + n_diag hypot(xres, yres), NaN at invalid cells and -1 at cyclic ones.  The
+    counts are exact; the number of launches follows log(gw gh).  numpy if the directions came as numpy, a device tensor
+    otherwise."""
+    direction = _codes_checked(direction)
+    _cycles_checked(cycles)
+    if grid is not None:
+        _on_grid(direction, _grid_checked(grid, "grid"))
+    d, as_numpy = _to_device(direction)
+    dev = d.device
+    gh, gw = d.shape
+    ws, nbytes = _stream_workspace(d)
+    steps = torch.empty((gh, gw, 3), dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_flow_length", d, gw, gh, steps, flag, ws, nbytes)
+    if int(flag.item()) & 1 and cycles == "raise":
+        raise ValueError("the directions hold a cycle: some cells reach no root; cycles='mark' gives them -1")
+    if grid is None:
+        return _back(as_numpy, steps)
+    metres = _steps_length(steps, grid)
+    metres = torch.where(steps[..., 0] < 0, torch.full_like(metres, -1.0), metres)
+    return _back(as_numpy, torch.where(d > 8, torch.full_like(metres, float("nan")), metres))
+
+
+def write_streams(path, links, grid, projection=None):
+    """The links of stream_links() as a GeoJSON FeatureCollection of LineStrings, one Feature per link of two vertices or more
+    in the links' order (a link of one cell at a mouth has no line).  Coordinates are east, north at cell centres on `grid`
+    (E = e0 + col xres, N = n0 - row yres); with `projection` (a TransverseMercator) lon, lat through its EastNorth2latlon.
+    properties: link (its number), order (Strahler), next_link (-1 at a mouth), n_cells (the link's own cells, the junction it
+    ends in not counted) and length_m = (n_ew xres + n_ns yres) + n_diag hypot(xres, yres).  Plain json, no GIS library.
+    -> the number of features."""
+    host = {k: (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for k, t in links.items()}
+    for key in ("order", "next_link", "offset", "vertices", "steps"):
+        if key not in host:
+            raise ValueError("links is the dict of stream_links(): entry %r is missing" % key)
+    order, nxt, offset, v, steps = host["order"], host["next_link"], host["offset"], host["vertices"], host["steps"]
+    n = len(order)
+    if v.ndim != 2 or v.shape[1] != 2 or len(offset) != n + 1 or len(nxt) != n or tuple(steps.shape) != (n, 3) or int(offset[-1]) != len(v):
+        raise ValueError("links is the dict of stream_links()")
+    _grid_checked(grid, "grid")
+    en = np.stack([float(grid.e0) + v[:, 0].astype(np.float64) * float(grid.xres),
+                   float(grid.n0) - v[:, 1].astype(np.float64) * float(grid.yres)], axis=1)
+    out = en
+    if projection is not None and len(en):
+        out = np.asarray(projection.EastNorth2latlon(en))[:, ::-1]
+    s = steps.astype(np.float64)
+    length = (s[:, 0] * float(grid.xres) + s[:, 1] * float(grid.yres)) + s[:, 2] * float(np.hypot(float(grid.xres), float(grid.yres)))
+    features = []
+    for i in range(n):
+        a, b = int(offset[i]), int(offset[i + 1])
+        if b - a < 2:
+            continue
+        properties = {"link": i, "order": int(order[i]), "next_link": int(nxt[i]), "n_cells": b - a - (1 if nxt[i] >= 0 else 0),
+                      "length_m": _json_value(length[i])}
+        features.append({"type": "Feature", "properties": properties, "geometry": {"type": "LineString", "coordinates": out[a:b].tolist()}})
+    with open(path, "w") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+        f.write("\n")
+    return len(features)
+
+
+def extract_streams(dtm, grid, min_area_m2=25000.0, nodata=-999.0):
+    """The drainage network of a DTM: flow_direction(dtm, grid) -> flow_accumulation(grid=grid) -> streams(acc, min_area_m2) ->
+    stream_links(grid=grid).  min_area_m2 is the catchment a channel needs before it counts as one; the default (1000 cells of
+    5 m) is a choice for 5 m grids, not tuned on real data.  -> the dict of stream_links() with vertices_en and length_m.
+    numpy if the DTM came as numpy, device tensors otherwise."""
+    dtm = _hydro_dsm(dtm, grid)
+    min_area_m2 = float(min_area_m2)
+    if not (math.isfinite(min_area_m2) and min_area_m2 >= 0.0):
+        raise ValueError("min_area_m2 must be finite and >= 0, got %r" % min_area_m2)
+    z, as_numpy = _to_device(dtm)
+    code = flow_direction(z, grid, nodata)
+    acc = flow_accumulation(code, grid=grid)
+    links = stream_links(code, streams(acc, min_area_m2), grid=grid)
+    return {k: _back(as_numpy, t) for k, t in links.items()}
 
 
 # ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
