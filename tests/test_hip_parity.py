@@ -672,7 +672,7 @@ def test_costvol_backward_matches_torch(dev, oracle):
     dict(B=2, V=3, C=8, D=12, H=40, W=70),                                  # ragged tiles, D not a multiple of the 8-plane chunk, boxed waves
     dict(B=1, V=2, C=4, D=8, H=64, W=96),                                   # one source view
     dict(B=1, V=3, C=6, D=5, H=33, W=130, jitter=False),                    # per-plane heights (B,D), odd sizes
-    dict(B=1, V=5, C=4, D=6, H=48, W=80),                                   # four source views: 4-plane chunks, 64 KB of boxes per workgroup
+    dict(B=1, V=5, C=4, D=6, H=48, W=80),                                   # four source views: 8-plane chunks like 1 - 3 (2 planes beyond four), 64 KB of boxes per workgroup
     dict(B=1, V=6, C=4, D=5, H=24, W=72),                                   # five source views: no boxed path, 64 x 1 patches
     dict(B=1, V=8, C=2, D=3, H=16, W=40),                                   # seven source views
     dict(B=1, V=3, C=4, D=8, H=48, W=96, span=(0.0, 30000.0)),              # tens of cells of parallax per plane: boxes overflow, register scheme
