@@ -278,6 +278,11 @@ int smvs_conv3x3_wgrad_cat(const float* xA, int CA, const float* xB, int CB, con
  * and dgrid_sum (Cgrid, or NULL) are accumulated into (the caller zeroes them). */
 int smvs_conv3x3_wgrad_list(const float* const* win, const float* const* win2, const float* const* grid, int n,
                             float* dw, float* dgrid_sum, int Bper, int CA, int CB, int Cgrid, int H, int W, int stride, void* stream);
+/* How the four entries above cut a launch over B samples in all (the list form: n * Bper per launch of at most 64 tensors) into waves --
+ * the function the launcher itself asks.  Host code only: no HIP call, usable without a GPU.  SMVS_ERR_ARG exactly where the launcher
+ * rejects the dimensions.  plan = {bchunk, nbc, rows, nrc, nxs, waves}: a wave owns 2 window channels x 8 grid channels x one of nxs strips
+ * of 64 columns x one of nrc chunks of `rows` rows x one of nbc chunks of `bchunk` samples (row chunks only at one sample per wave). */
+int smvs_conv3x3_wgrad_plan(int B, int Cin, int Cout, int H, int W, int stride, int plan[6]);
 
 /* Weight gradient of the 3x3x3 / pad 1 layers of the 3-D regulariser CostRegNet (modules/module.py:324-410, 546-577 under
  * loss.backward(), train.py:284 with --model casmvs / ucs) -- the 2-D correlation above with a depth axis:
@@ -293,6 +298,12 @@ int smvs_conv3x3_wgrad_list(const float* const* win, const float* const* win2, c
 size_t smvs_conv3d_wgrad_workspace_floats(int B, int Cwin, int Cgrid, int D, int H, int W);
 int smvs_conv3d_wgrad(const float* window, const float* grid, float* dw, float* workspace, size_t workspace_floats, int B, int Cwin,
                       int Cgrid, int D, int H, int W, int stride, void* stream);
+/* The split smvs_conv3d_wgrad takes, atomic form (two_stage = 0) or with a workspace (two_stage != 0) -- the function the launcher itself
+ * asks; host code only, SMVS_ERR_ARG exactly where the launcher rejects the dimensions.  plan = {dchunk, ndc, rows, nrc, nxs, waves}: a
+ * wave owns 2 window channels x 8 grid channels (1 when Cgrid = 1) x one depth tap x one of nxs column strips x one of nrc row chunks x
+ * one of ndc chunks of `dchunk` grid planes of one sample; waves (all of them) saturates at INT_MAX.  The workspace holds 144 floats per
+ * wave: smvs_conv3d_wgrad_workspace_floats = ceil(Cwin/2) * ceil(Cgrid/8) * 3 * (B * ndc * nxs * nrc) * 144 of the two-stage plan. */
+int smvs_conv3d_wgrad_plan(int B, int Cwin, int Cgrid, int D, int H, int W, int stride, int two_stage, int plan[6]);
 
 /* A single 3x3x3 / pad 1 layer of CostRegNet as a stand-alone call on the kernels of smvs_costreg_fwd (direct or MFMA by channel
  * count) WITHOUT the folded BatchNorm -- the TRAINING forward of its convolutions (modules/module.py:324-410 under autograd, batch

@@ -132,8 +132,10 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_dsm_simplify_workspace_bytes": [_i] * 2, "smvs_dsm_contour_workspace_bytes": [_i] * 4,
                "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2,
                "smvs_dsm_stream_workspace_bytes": [_i] * 2}
-# host-side queries that return a code, not a status: called on load() directly, never through call()
-_QUERY_FUNCS = {"smvs_conv3x3_variant": [_i] * 8, "smvs_conv3d_variant": [_i] * 7}
+# host-side queries (no HIP call, no stream) that return a code, or a status beside a plan written to an int[6]: called on load()
+# directly, never through call()
+_QUERY_FUNCS = {"smvs_conv3x3_variant": [_i] * 8, "smvs_conv3d_variant": [_i] * 7,
+                "smvs_conv3x3_wgrad_plan": [_i] * 6 + [C.POINTER(_i)], "smvs_conv3d_wgrad_plan": [_i] * 8 + [C.POINTER(_i)]}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_SIZE_FUNCS) + list(_QUERY_FUNCS) + ["smvs_version", "smvs_last_error", "smvs_red_set_streams", "smvs_shutdown",
                                                                     "smvs_set_arith", "smvs_get_arith"])
 ARITH_MODES = {"exact": 0, "fused": 1}      # SMVS_ARITH_EXACT / SMVS_ARITH_FUSED of include/satmvs.h

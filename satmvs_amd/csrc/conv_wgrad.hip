@@ -467,6 +467,35 @@ void conv3d_wgrad_fold_kernel(const Wgrad3Params p)
 
 }  // namespace smvs
 
+// The split of a 2-D launch over `B` samples in all (a list: every sample of its tensors), and the dimension checks of the launcher.
+// plan = {bchunk, nbc, rows, nrc, nxs, waves}.  Host code only.
+static int wgrad_plan(int B, int Cin, int Cout, int H, int W, int stride, int plan[6])
+{
+    using namespace smvs;
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
+    if (stride != 1 && stride != 2) return fail(SMVS_ERR_ARG, "stride must be 1 or 2");
+    if ((long long)2 * stride * stride * H * W * 4 >= (1ll << 31) || (long long)8 * H * W * 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "plane too large");
+    const int ncp = (Cin + 1) / 2, ncog = (Cout + 7) / 8, nxs = (W + 63) / 64;
+    // Work per wave: whole samples while that leaves >= ~2048 waves (the window prologue and the lane reduction are paid once per wave),
+    // then single samples cut into row chunks: long enough to amortise the reduction (~3 rows of arithmetic), short enough for ~2048 waves.
+    const long long base = (long long)ncp * ncog * nxs;
+    int bchunk = B, rows = H;
+    while (bchunk > 1 && base * ((B + bchunk - 1) / bchunk) < 2048) bchunk = (bchunk + 1) / 2;
+    const int nbc = (B + bchunk - 1) / bchunk;
+    while (bchunk == 1 && rows > 16 && base * nbc * ((H + rows - 1) / rows) < 2048) rows = (rows + 1) / 2;
+    const int nrc = (H + rows - 1) / rows;
+    const long long units = base * nrc * nbc;
+    if (units >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
+    plan[0] = bchunk; plan[1] = nbc; plan[2] = rows; plan[3] = nrc; plan[4] = nxs; plan[5] = (int)units;
+    return SMVS_OK;
+}
+
+extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad_plan(int B, int Cin, int Cout, int H, int W, int stride, int plan[6])
+{
+    if (!plan) return smvs::fail(SMVS_ERR_ARG, "null pointer argument");
+    return wgrad_plan(B, Cin, Cout, H, W, stride, plan);
+}
+
 // list: nlist > 0 tensors of `B` samples each (x / x2 / dy ignored), else one tensor of B samples
 static int wgrad_launch(const float* x, const float* dy, float* dw, float* db, int B, int Cin, int Cout, int H, int W, int stride, void* stream,
                         const float* x2 = nullptr, int CA = 0, int nlist = 0, const float* const* xl = nullptr, const float* const* x2l = nullptr,
@@ -476,9 +505,9 @@ static int wgrad_launch(const float* x, const float* dy, float* dw, float* db, i
     if (!dw || (!nlist && (!x || !dy)) || (nlist && (!xl || !dyl))) return fail(SMVS_ERR_ARG, "null pointer argument");
     const bool second = nlist ? x2l != nullptr : x2 != nullptr;
     if (second && (CA < 2 || CA >= Cin || (CA & 1))) return fail(SMVS_ERR_ARG, "two-operand window: the first operand needs an even channel count in [2, Cin)");
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || nlist < 0 || nlist > WGRAD_LIST_MAX) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if (stride != 1 && stride != 2) return fail(SMVS_ERR_ARG, "stride must be 1 or 2");
-    if ((long long)2 * stride * stride * H * W * 4 >= (1ll << 31) || (long long)8 * H * W * 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "plane too large");
+    if (B < 1 || nlist < 0 || nlist > WGRAD_LIST_MAX) return fail(SMVS_ERR_ARG, "non-positive dimension");
+    int plan[6];
+    if (const int rc = wgrad_plan(nlist ? nlist * B : B, Cin, Cout, H, W, stride, plan)) return rc;
     WgradParams p{};
     p.x = x; p.dy = dy; p.dw = dw; p.db = db; p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
     p.x2 = x2; p.CA = second ? CA : Cin;
@@ -487,18 +516,9 @@ static int wgrad_launch(const float* x, const float* dy, float* dw, float* db, i
         if (!xl[i] || !dyl[i] || (second && !x2l[i])) return fail(SMVS_ERR_ARG, "null pointer in the tensor list");
         p.xl[i] = xl[i]; p.x2l[i] = second ? x2l[i] : nullptr; p.dyl[i] = dyl[i];
     }
-    p.ncp = (Cin + 1) / 2; p.ncog = (Cout + 7) / 8; p.nxs = (W + 63) / 64;
-    // Work per wave: whole samples while that leaves >= ~2048 waves (the window prologue and the lane reduction are paid once per wave),
-    // then single samples cut into row chunks: long enough to amortise the reduction (~3 rows of arithmetic), short enough for ~2048 waves.
-    const long long base = (long long)p.ncp * p.ncog * p.nxs;
-    int bchunk = p.B, rows = H;
-    while (bchunk > 1 && base * ((p.B + bchunk - 1) / bchunk) < 2048) bchunk = (bchunk + 1) / 2;
-    const int nbc = (p.B + bchunk - 1) / bchunk;
-    while (bchunk == 1 && rows > 16 && base * nbc * ((H + rows - 1) / rows) < 2048) rows = (rows + 1) / 2;
-    p.bchunk = bchunk; p.nbc = nbc;
-    p.rows = rows; p.nrc = (H + rows - 1) / rows;
-    const long long units = base * p.nrc * p.nbc;
-    if (units >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
+    p.ncp = (Cin + 1) / 2; p.ncog = (Cout + 7) / 8; p.nxs = plan[4];
+    p.bchunk = plan[0]; p.nbc = plan[1]; p.rows = plan[2]; p.nrc = plan[3];
+    const long long units = plan[5];
     if (stride == 1) hipLaunchKernelGGL(conv3x3_wgrad_kernel<1>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
     else             hipLaunchKernelGGL(conv3x3_wgrad_kernel<2>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("conv3x3_wgrad");
@@ -519,6 +539,7 @@ extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad_strided(const float* window, const
 extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad_cat(const float* xA, int CA, const float* xB, int CB, const float* dy, float* dw, float* db,
                                                   int B, int Cout, int H, int W, void* stream)
 {
+    if (CB < 0) return smvs::fail(SMVS_ERR_ARG, "negative channel count of the second operand");
     if (CB > 0 && !xB) return smvs::fail(SMVS_ERR_ARG, "null pointer argument");
     return wgrad_launch(xA, dy, dw, db, B, CA + CB, Cout, H, W, 1, stream, CB > 0 ? xB : nullptr, CA);
 }
@@ -530,6 +551,8 @@ extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad_list(const float* const* win, cons
                                                    void* stream)
 {
     if (!win || !grid || n < 1) return smvs::fail(SMVS_ERR_ARG, "empty tensor list");
+    if (CB < 0) return smvs::fail(SMVS_ERR_ARG, "negative channel count of the second operand");
+    if (CB > 0 && !win2) return smvs::fail(SMVS_ERR_ARG, "null pointer argument");      // (it read CA + CB channels from `win` before)
     for (int i = 0; i < n; i += smvs::WGRAD_LIST_MAX) {
         const int m = n - i < smvs::WGRAD_LIST_MAX ? n - i : smvs::WGRAD_LIST_MAX;
         const int rc = wgrad_launch(nullptr, nullptr, dw, dgrid_sum, Bper, CA + CB, Cgrid, H, W, stride, stream, nullptr, CA, m, win + i,
@@ -544,16 +567,17 @@ extern "C" SMVS_EXPORT int smvs_conv3x3_wgrad_list(const float* const* win, cons
 // nn.Conv3d (stride S): window = layer input, grid = output gradient; nn.ConvTranspose3d (stride 2, output_padding 1): window = output
 // gradient, grid = layer input (its weight is (Cin_layer, Cout_layer, 3,3,3) = the same index formula).
 // Replaces MIOpen's weight-gradient kernels under /root/reference/modules/module.py:324-410, 546-577.
-static void wgrad3_split(smvs::Wgrad3Params& p, bool two_stage)
+// The split of a 3-D launch into chunks of grid planes and row chunks: plan = {dchunk, ndc, rows, nrc, nxs, waves}, `waves` (the
+// launch's work units) saturated at INT_MAX.  -> the work units.  Host code only.
+static long long wgrad3_split(int B, int Cwin, int Cgrid, int D, int H, int W, bool two_stage, int plan[6])
 {
-    using namespace smvs;
+    const int ncp = (Cwin + 1) / 2, ncog = (Cgrid + 7) / 8, nxs = (W + 63) / 64;
     // Work per wave.  The chip holds 2048 of these waves at a time (218 VGPRs: two per SIMD), a launch runs in ROUNDS of that many and a
     // round lasts as long as one wave: pick the split into chunks of grid planes x row chunks that minimises
     //     rounds x (rows a wave walks + ~6 rows of prologue per plane + ~12 rows of lane reduction per wave)
     // Two-stage form only; with atomics straight from the waves (no workspace) the first form stays: halve until >= 2048 waves, because
     // every further wave of a group lengthens the chain of serialised atomics on the group's five cache lines.
-    const int D = p.D, H = p.H;
-    const long long base = (long long)p.ncp * p.ncog * p.nxs * 3 * p.B;
+    const long long base = (long long)ncp * ncog * nxs * 3 * B;
     int dchunk = D, rows = H;
     if (two_stage) {
         constexpr long long slots = 2048;                     // the waves the chip holds at a time (above)
@@ -574,19 +598,39 @@ static void wgrad3_split(smvs::Wgrad3Params& p, bool two_stage)
         const int nd = (D + dchunk - 1) / dchunk;
         while (dchunk == 1 && rows > 16 && base * nd * ((H + rows - 1) / rows) < 2048) rows = (rows + 1) / 2;
     }
-    p.dchunk = dchunk; p.ndc = (D + dchunk - 1) / dchunk; p.rows = rows; p.nrc = (H + rows - 1) / rows;
+    const int ndc = (D + dchunk - 1) / dchunk, nrc = (H + rows - 1) / rows;
+    const long long units = base * ndc * nrc;
+    plan[0] = dchunk; plan[1] = ndc; plan[2] = rows; plan[3] = nrc; plan[4] = nxs; plan[5] = units < 0x7fffffffll ? (int)units : 0x7fffffff;
+    return units;
+}
+
+// ... behind the dimension checks of the launcher
+static int wgrad3_plan(int B, int Cwin, int Cgrid, int D, int H, int W, int stride, bool two_stage, int plan[6])
+{
+    using namespace smvs;
+    if (B < 1 || Cwin < 1 || Cgrid < 1 || D < 1 || H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
+    if (stride != 1 && stride != 2) return fail(SMVS_ERR_ARG, "stride must be 1 or 2");
+    const long long S = stride, vol_g = (long long)D * H * W, vol_w = vol_g * S * S * S, plane_w = (long long)H * W * S * S;
+    if ((vol_w + plane_w) * 4 >= (1ll << 31) || (7 * vol_g + (long long)H * W) * 4 >= (1ll << 31))
+        return fail(SMVS_ERR_ARG, "volume too large for the 32-bit channel offsets of conv3d_wgrad (window %lld, grid %lld elements per channel)", vol_w, vol_g);
+    const long long units = wgrad3_split(B, Cwin, Cgrid, D, H, W, two_stage, plan);
+    if ((units + 3) / 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
+    return SMVS_OK;
+}
+
+extern "C" SMVS_EXPORT int smvs_conv3d_wgrad_plan(int B, int Cwin, int Cgrid, int D, int H, int W, int stride, int two_stage, int plan[6])
+{
+    if (!plan) return smvs::fail(SMVS_ERR_ARG, "null pointer argument");
+    return wgrad3_plan(B, Cwin, Cgrid, D, H, W, stride, two_stage != 0, plan);
 }
 
 // floats of workspace the two-stage form of smvs_conv3d_wgrad wants for this shape (0: unsupported arguments)
 extern "C" SMVS_EXPORT size_t smvs_conv3d_wgrad_workspace_floats(int B, int Cwin, int Cgrid, int D, int H, int W)
 {
-    using namespace smvs;
     if (B < 1 || Cwin < 1 || Cgrid < 1 || D < 1 || H < 1 || W < 1) return 0;
-    Wgrad3Params p{};
-    p.B = B; p.Cin = Cwin; p.Cout = Cgrid; p.D = D; p.H = H; p.W = W;
-    p.ncp = (Cwin + 1) / 2; p.ncog = (Cgrid + 7) / 8; p.nxs = (W + 63) / 64;
-    wgrad3_split(p, true);
-    return (size_t)p.ncp * p.ncog * 3 * ((size_t)B * p.ndc * p.nxs * p.nrc) * 144;
+    int plan[6];
+    wgrad3_split(B, Cwin, Cgrid, D, H, W, true, plan);         // (the split depends on neither the stride nor the launcher's limits)
+    return (size_t)((Cwin + 1) / 2) * ((Cgrid + 7) / 8) * 3 * ((size_t)B * plan[1] * plan[4] * plan[3]) * 144;
 }
 
 extern "C" SMVS_EXPORT int smvs_conv3d_wgrad(const float* window, const float* grid, float* dw, float* workspace, size_t workspace_floats,
@@ -594,22 +638,16 @@ extern "C" SMVS_EXPORT int smvs_conv3d_wgrad(const float* window, const float* g
 {
     using namespace smvs;
     if (!window || !grid || !dw) return fail(SMVS_ERR_ARG, "null pointer argument");
-    if (B < 1 || Cwin < 1 || Cgrid < 1 || D < 1 || H < 1 || W < 1) return fail(SMVS_ERR_ARG, "non-positive dimension");
-    if (stride != 1 && stride != 2) return fail(SMVS_ERR_ARG, "stride must be 1 or 2");
-    const long long S = stride, vol_g = (long long)D * H * W, vol_w = vol_g * S * S * S, plane_w = (long long)H * W * S * S;
-    if ((vol_w + plane_w) * 4 >= (1ll << 31) || (7 * vol_g + (long long)H * W) * 4 >= (1ll << 31))
-        return fail(SMVS_ERR_ARG, "volume too large for the 32-bit channel offsets of conv3d_wgrad (window %lld, grid %lld elements per channel)", vol_w, vol_g);
+    int plan[6];
+    if (const int rc = wgrad3_plan(B, Cwin, Cgrid, D, H, W, stride, workspace != nullptr, plan)) return rc;
     Wgrad3Params p{};
     p.x = window; p.dy = grid; p.dw = dw; p.B = B; p.Cin = Cwin; p.Cout = Cgrid; p.D = D; p.H = H; p.W = W;
-    p.ncp = (Cwin + 1) / 2; p.ncog = (Cgrid + 7) / 8; p.nxs = (W + 63) / 64;
+    p.ncp = (Cwin + 1) / 2; p.ncog = (Cgrid + 7) / 8; p.nxs = plan[4];
     const size_t need = workspace ? smvs_conv3d_wgrad_workspace_floats(B, Cwin, Cgrid, D, H, W) : 0;
     if (workspace && workspace_floats < need) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu floats", workspace_floats, need);
-    wgrad3_split(p, workspace != nullptr);
+    p.dchunk = plan[0]; p.ndc = plan[1]; p.rows = plan[2]; p.nrc = plan[3];
     p.part = workspace;
-    const long long base = (long long)p.ncp * p.ncog * p.nxs * 3 * B;
-    const int ndc = p.ndc;
-    const long long units = base * ndc * p.nrc;
-    if ((units + 3) / 4 >= (1ll << 31)) return fail(SMVS_ERR_ARG, "too many work units");
+    const long long units = (long long)p.ncp * p.ncog * p.nxs * 3 * B * p.ndc * p.nrc;
     const dim3 grd((unsigned)((units + 3) / 4));
     if (Cgrid == 1) {
         if (stride == 1) hipLaunchKernelGGL((conv3d_wgrad_kernel<1, 1>), grd, dim3(256), 0, (hipStream_t)stream, p);

@@ -323,6 +323,51 @@ def test_round3_training_entry_points_validate_arguments(lib):
         _lib.call("smvs_costvol_bwd", 0, d, d, arr, 8, d, d, 1, d, arr, 1, 1, 1, 8, 8, None)
 
 
+def test_weight_gradient_entry_points_validate_arguments(lib):
+    """The plan queries of the weight gradients answer bad dimensions and a stride of 3 with SMVS_ERR_ARG (and write no plan), the
+    two-operand entries reject a negative second channel count, and the list entry a second operand announced (CB > 0) but not
+    given -- it used to read CA + CB channels from `win` -- all before any HIP call."""
+    from satmvs_amd import _lib
+    ERR_ARG = 1
+    plan = (C.c_int * 6)(*[-7] * 6)
+    p2, p3 = lib.smvs_conv3x3_wgrad_plan, lib.smvs_conv3d_wgrad_plan
+    assert p2(1, 2, 3, 4, 5, 1, plan) == 0 and list(plan) == [1, 1, 4, 1, 1, 1]
+    assert p3(1, 2, 3, 2, 4, 5, 2, 1, plan) == 0 and min(plan) >= 1
+    plan = (C.c_int * 6)(*[-7] * 6)
+    # (B, Cin, Cout, H, W, stride): a zero in every dimension, strides 0 and 3, a plane of 2^31 bytes over eight grid channels / a window pair
+    for a in [(0, 2, 3, 4, 5, 1), (1, 0, 3, 4, 5, 1), (1, 2, 0, 4, 5, 1), (1, 2, 3, 0, 5, 1), (1, 2, 3, 4, 0, 1), (1, 2, 3, 4, -5, 1),
+              (1, 2, 3, 4, 5, 3), (1, 2, 3, 4, 5, 0), (1, 2, 3, 8192, 8192, 1), (1, 2, 3, 8192, 8192, 2)]:
+        assert p2(*a, plan) == ERR_ARG, a
+        assert lib.smvs_last_error().decode() != ""
+    assert p2(1, 2, 3, 8192, 4096, 2, plan) == 0
+    plan = (C.c_int * 6)(*[-7] * 6)
+    # (B, Cwin, Cgrid, D, H, W, stride, two_stage)
+    for a in [(0, 2, 3, 2, 4, 5, 1, 0), (1, 0, 3, 2, 4, 5, 1, 0), (1, 2, 0, 2, 4, 5, 1, 1), (1, 2, 3, 0, 4, 5, 1, 0), (1, 2, 3, 2, 0, 5, 1, 1),
+              (1, 2, 3, 2, 4, 0, 1, 0), (1, 2, 3, 2, 4, 5, 3, 0), (1, 2, 3, 2, 4, 5, 3, 1), (1, 2, 3, 512, 1024, 1024, 1, 0), (1, 2, 3, 64, 1024, 1024, 2, 1)]:
+        assert p3(*a, plan) == ERR_ARG, a
+        assert lib.smvs_last_error().decode() != ""
+    assert list(plan) == [-7] * 6
+    assert p2(1, 2, 3, 4, 5, 1, None) == ERR_ARG and p3(1, 2, 3, 2, 4, 5, 1, 0, None) == ERR_ARG
+    d = C.c_void_p(4096)
+    arr = (C.c_void_p * 2)(4096, 4096)
+    with pytest.raises(_lib.SatMVSNativeError, match="null pointer"):
+        _lib.call("smvs_conv3x3_wgrad_list", arr, None, arr, 2, d, d, 1, 2, 2, 3, 4, 5, 1, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="negative channel count"):
+        _lib.call("smvs_conv3x3_wgrad_list", arr, arr, arr, 2, d, d, 1, 4, -2, 3, 4, 5, 1, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="negative channel count"):
+        _lib.call("smvs_conv3x3_wgrad_list", arr, None, arr, 2, d, d, 1, 4, -2, 3, 4, 5, 1, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="negative channel count"):
+        _lib.call("smvs_conv3x3_wgrad_cat", d, 4, d, -2, d, d, d, 1, 3, 4, 5, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="negative channel count"):
+        _lib.call("smvs_conv3x3_wgrad_cat", d, 4, None, -2, d, d, d, 1, 3, 4, 5, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="null pointer"):
+        _lib.call("smvs_conv3x3_wgrad_cat", d, 2, None, 2, d, d, d, 1, 3, 4, 5, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="stride must be"):
+        _lib.call("smvs_conv3x3_wgrad_strided", d, d, d, d, 1, 2, 3, 4, 5, 3, None)
+    with pytest.raises(_lib.SatMVSNativeError, match="stride must be"):
+        _lib.call("smvs_conv3d_wgrad", d, d, d, None, 0, 1, 2, 3, 2, 4, 5, 3, None)
+
+
 def test_dataset_assembler_matches_reference(golden):
     """satmvs_amd.dataset (PNG views, sample lists, get_sample / get_pred_sample: SURVEY 8f-4) against the reference's own
     MVSDataset run on the same scene folder (tests/golden/scene/, gen_golden.py::gen_dataset): images, three-scale RPCs,
