@@ -346,7 +346,10 @@ int smvs_conv3d_variant(int kind, int B, int Cin, int Cout, int Di, int Hi, int 
  *   bwd: dx, dgamma (C), dbeta (C) from dy, the layer's INPUT x and saved_mean_rstd; with relu != 0 the gradient passes where the forward's
  *        output was positive (recomputed from x: neither a mask nor the output is kept)
  * x, y, dy, dx: (B,C,N) contiguous float32; workspace: 2*C doubles of scratch, cleared by the call unless `relu` carries
- * SMVS_BN_WORKSPACE_ZERO (the caller hands over zeroed memory: one fill for all the layers of a forward).  relu: bit 0 = apply ReLU. */
+ * SMVS_BN_WORKSPACE_ZERO (the caller hands over zeroed memory: one fill for all the layers of a forward).  relu: bit 0 = apply ReLU.
+ * Neither direction runs in place: y == x (forward) and dx == x (backward) are SMVS_ERR_ARG, because every block of a channel re-reads
+ * the channel's first element of x while the channel's first block would be overwriting it.  saved_mean_rstd[2c] + x[0, c, 0] is the
+ * batch mean of channel c, saved_mean_rstd[2c + 1] its 1 / sqrt(var + eps). */
 #define SMVS_BN_WORKSPACE_ZERO 2
 int smvs_batchnorm_train_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                              long long* num_batches_tracked, float momentum, float eps, int relu, float* y, float* saved_mean_rstd,

@@ -126,7 +126,7 @@ void bn_apply_kernel(const BnArgs a)
     const double ms = a.sums[2 * c] / cnt;                        // mean of (x - pivot), see bn_stats_kernel
     const double m = (double)a.x[(size_t)c * (size_t)a.N] + ms;
     double var = a.sums[2 * c + 1] / cnt - ms * ms;
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;                                  // (a NaN stays one: rstd and running_var of a channel with a NaN in it are NaN, like torch's)
     const float pivot = a.x[(size_t)c * (size_t)a.N];
     const float mean = (float)m, mshift = (float)ms, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
     const float scale = a.gamma[c] * rstd, shift = a.beta[c];      // y = (x - mean) * scale + beta, centred
@@ -139,7 +139,7 @@ void bn_apply_kernel(const BnArgs a)
             a.running_var[c] = (1.0f - a.momentum) * a.running_var[c] + a.momentum * (float)unbiased;
         }
     }
-    auto one = [&](float xv) { const float r = fmaf((xv - pivot) - mshift, scale, shift); return a.relu ? fmaxf(r, 0.0f) : r; };
+    auto one = [&](float xv) { const float r = fmaf((xv - pivot) - mshift, scale, shift); return (!a.relu || r > 0.0f) ? r : (r == r ? 0.0f : r); };      // (not fmaxf: the ReLU of a NaN is NaN, like torch's)
     if (a.vec4) {
         for (long long i = i0 + threadIdx.x * 4; i < i1; i += BN_BLOCK * 4 * BN_UNROLL) {
             float4 xv[BN_UNROLL];
@@ -223,6 +223,8 @@ extern "C" SMVS_EXPORT int smvs_batchnorm_train_fwd(const float* x, const float*
     using namespace smvs;
     if (!x || !gamma || !beta || !y || !saved_mean_rstd || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     if ((running_mean == nullptr) != (running_var == nullptr)) return fail(SMVS_ERR_ARG, "running_mean and running_var go together");
+    // every block of a channel re-reads the pivot x[0, c, 0]; in place the channel's first block would overwrite it under the others
+    if (y == x) return fail(SMVS_ERR_ARG, "y must not be x: the forward does not run in place");
     BnArgs a{};
     const int rc = bn_geometry(a, B, C, N);
     if (rc) return rc;
@@ -244,6 +246,7 @@ extern "C" SMVS_EXPORT int smvs_batchnorm_train_bwd(const float* dy, const float
 {
     using namespace smvs;
     if (!dy || !x || !gamma || !beta || !saved_mean_rstd || !dx || !dgamma || !dbeta || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
+    if (dx == x) return fail(SMVS_ERR_ARG, "dx must not be x: the backward re-reads the pivot x[0, c, 0] in every block");
     BnArgs a{};
     const int rc = bn_geometry(a, B, C, N);
     if (rc) return rc;

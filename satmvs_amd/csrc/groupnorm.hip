@@ -92,7 +92,8 @@ __device__ __forceinline__ void mean_rstd_of(const double* partial, int b, int n
     block_sum2(s, q);
     if (threadIdx.x == 0) {
         const double m = s / (double)n;
-        const double var = fmax(q / (double)n - m * m, 0.0);
+        const double d = q / (double)n - m * m;
+        const double var = d < 0.0 ? 0.0 : d;                // (not fmax: a NaN stays one, so a sample with a NaN in it has a NaN rstd too)
         mr[0] = (float)m;
         mr[1] = (float)(1.0 / sqrt(var + (double)eps));
     }

@@ -323,6 +323,41 @@ def test_round3_training_entry_points_validate_arguments(lib):
         _lib.call("smvs_costvol_bwd", 0, d, d, arr, 8, d, d, 1, d, arr, 1, 1, 1, 8, 8, None)
 
 
+def test_batchnorm_entry_points_validate_arguments(lib):
+    """smvs_batchnorm_train_fwd / _bwd reject every null pointer, exactly one of running_mean / running_var, non-positive B / C / N,
+    more than 65535 channels, and the two in-place forms (y == x, dx == x: the pivot x[0, c, 0] would be overwritten under the blocks
+    that re-read it) before any HIP call."""
+    from satmvs_amd import _lib
+    d, e = C.c_void_p(4096), C.c_void_p(8192)
+
+    def fwd(x=d, gamma=d, beta=d, rm=d, rv=d, nbt=d, y=e, saved=d, ws=d, B=2, Cc=3, N=8):
+        _lib.call("smvs_batchnorm_train_fwd", x, gamma, beta, rm, rv, nbt, 0.1, 1e-5, 1, y, saved, ws, B, Cc, N, None)
+
+    def bwd(dy=d, x=d, gamma=d, beta=d, saved=d, dx=e, dgamma=d, dbeta=d, ws=d, B=2, Cc=3, N=8):
+        _lib.call("smvs_batchnorm_train_bwd", dy, x, gamma, beta, saved, 1, dx, dgamma, dbeta, ws, B, Cc, N, None)
+
+    for name in ("x", "gamma", "beta", "y", "saved", "ws"):
+        with pytest.raises(_lib.SatMVSNativeError, match="null pointer"):
+            fwd(**{name: None})
+    for name in ("dy", "x", "gamma", "beta", "saved", "dx", "dgamma", "dbeta", "ws"):
+        with pytest.raises(_lib.SatMVSNativeError, match="null pointer"):
+            bwd(**{name: None})
+    for one in ("rm", "rv"):
+        with pytest.raises(_lib.SatMVSNativeError, match="go together"):
+            fwd(**{one: None})
+    for call in (fwd, bwd):
+        for dim in ("B", "Cc", "N"):
+            for v in (0, -1):
+                with pytest.raises(_lib.SatMVSNativeError, match="non-positive"):
+                    call(**{dim: v})
+        with pytest.raises(_lib.SatMVSNativeError, match="65535 channels"):
+            call(Cc=65536)
+    with pytest.raises(_lib.SatMVSNativeError, match="y must not be x"):
+        fwd(y=d)
+    with pytest.raises(_lib.SatMVSNativeError, match="dx must not be x"):
+        bwd(dx=d)
+
+
 def test_weight_gradient_entry_points_validate_arguments(lib):
     """The plan queries of the weight gradients answer bad dimensions and a stride of 3 with SMVS_ERR_ARG (and write no plan), the
     two-operand entries reject a negative second channel count, and the list entry a second operand announced (CB > 0) but not
