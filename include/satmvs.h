@@ -806,6 +806,52 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   arguments): 8 bytes per cell and 8 more per cell and direction, because all directions of a call are in flight at once;
  *   a caller short of memory passes fewer directions per call, the bits do not depend on it.
  *
+ * Viewshed (csrc/dsm_viewshed.hip).
+ * smvs_dsm_viewshed: for n_obs observers in one call, which cells an eye on or above the surface sees: one exact line of
+ *   sight per observer and target cell.  dsm (gh, gw) float32 (device), read only.
+ *   Heights.  A cell is valid iff it is finite, != (float)nodata and |z| <= 32768.  q = llrint(256 (double)z), halves to
+ *   even, as for smvs_dsm_horizon.
+ *   Curvature.  The cell at offset (dc, dr) from the observer has the drop D = llrint(c256 (((double)dc xres) ((double)dc
+ *   xres) + ((double)dr yres) ((double)dr yres))): every product and the sum rounded by themselves, nothing contracted.
+ *   c256 is a HOST double >= 0 that the caller derives (dsm.viewshed_terms: c256 = 256 (1 - refraction) / (2 R)); 0 means a
+ *   flat earth.  The effective height q' = q - D is used for intermediate cells and for the target alike; D is 0 at the
+ *   observer.  The same sum of squares d2 serves the range test: a cell is in range iff d2 <= r2max, a HOST double, +inf
+ *   for no limit.
+ *   Observer.  obs is a HOST array of n_obs x 5 int32 (col, row, eye, mode, tgt).  mode 0: the eye is E = q_o + eye, in
+ *   units of 2^-8 m above the observer's own cell; eye is not negative and the cell must be valid.  mode 1: E = eye is
+ *   absolute and the cell may be invalid.  tgt >= 0 is the height added to every target.  The observer's cell lies on the
+ *   grid.
+ *   The line.  For a target (ct, rt): dx = ct - col, dy = rt - row, n = max(|dx|, |dy|).  The line steps along rows iff
+ *   |dy| >= |dx|, a tie included, as the sheared lines of smvs_dsm_shadow; otherwise along columns.  At step i = 1 .. n - 1
+ *   the major coordinate has moved i cells towards the target and, with dm the signed minor difference, the minor
+ *   coordinate has moved floor((2 i dm + n) / (2 n)): floor division of integers, halves towards +inf.  The cell found this
+ *   way is intermediate sample j.  Neither the observer's cell nor the target occludes; invalid samples neither occlude nor
+ *   receive, as in smvs_dsm_horizon.
+ *   The test.  M is the maximum over the valid intermediate samples of the exact rational (q'_j - E) n / i_j, -inf with no
+ *   valid sample; need = ceil(M) - (q'_t - E), an integer (-inf with M).  The target is seen iff need <= tgt, which is
+ *   (q'_j - E) n <= (q'_t + tgt - E) i_j for every j: grazing counts as seen.  Every comparison that decides M is an int64
+ *   cross-multiplication, never a comparison of rounded quotients; under the limits below |q' - E| < 2^31 and n, i < 2^16,
+ *   so every product stays below 2^47.
+ *   Outputs (device).  seen (n_obs, gh, gw) uint8 and above (n_obs, gh, gw) float32 (may be null): 0 and (float)nodata at
+ *   an invalid target; 1 and +0.0 at a seen one; 2 and (float)((double)need / 256.0), what must stand on the cell to be
+ *   seen (one exact division, one conversion), at a hidden one; 3 and (float)nodata at a valid one out of range.  The
+ *   observer's own cell (n = 0) is 1 if valid.  status (n_obs) int32: 0 for a mode-0 observer on an invalid cell, whose maps
+ *   are 0 and (float)nodata everywhere; otherwise 1.
+ *   The entry writes every element of its outputs; every workspace word a kernel reads was written by a kernel of the same
+ *   call; no atomics, no host synchronisation.  The bits are equal from run to run, on any stream, for any batching of the
+ *   observers, and equal to the numpy statement of this rule.
+ *   Limits (SMVS_ERR_ARG with a message, checked before any HIP call; nothing is written): non-null dsm, obs, seen, status
+ *   and workspace; 1 <= gw, gh <= 65536, gw * gh < 2^31; 1 <= n_obs <= 64; every observer on the grid, mode 0 or 1,
+ *   |eye| <= 2^23 with eye >= 0 in mode 0, 0 <= tgt <= 2^23; xres, yres finite and > 0; c256 finite and >= 0 with
+ *   c256 ((gw xres)^2 + (gh yres)^2) < 2^30, so that D fits; r2max > 0 or +inf, not NaN; no overlap among the buffers;
+ *   workspace: smvs_dsm_viewshed_workspace_bytes(gw, gh, n_obs) bytes (0 = unsupported arguments): 4 bytes per cell.
+ * smvs_dsm_los: the same rule, by the same device function, for a DEVICE list of n_pairs x 7 int32 (col_o, row_o, eye,
+ *   mode, col_t, row_t, tgt), each pair with its own target height: seen (n_pairs) uint8, above (n_pairs) float32 (may be
+ *   null).  Code 0 also covers an invalid mode-0 observer and a pair with a field out of range (a cell off the grid, a mode
+ *   other than 0 and 1, eye or tgt beyond their limits): the kernel tests the fields before it reads a cell.  No workspace:
+ *   q is taken straight from the floats.  Limits: those of smvs_dsm_viewshed on the grid and the four doubles; non-null
+ *   dsm, pairs and seen; 1 <= n_pairs < 2^31; no overlap among the buffers.
+ *
  * Outlines (csrc/dsm_outline.hip).  labels (gh, gw) int32 (device), read only.  A cell has label k iff its value is k and
  *   1 <= k <= n; every other value and every cell off the grid counts as 0.  Lattice corner (x, y), 0 <= x <= gw,
  *   0 <= y <= gh, is the upper-left corner of cell (row y, col x).  Side s of a cell with label k (s = 0 south, 1 east,
@@ -1092,6 +1138,14 @@ int smvs_dsm_horizon(const float* dsm, int gw, int gh, float nodata,
                      const double* dirs /* HOST, n_dirs x 4: ucol, urow, a, b */, int n_dirs,
                      float* tan_h /* device, (n_dirs, gh, gw) */,
                      void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_viewshed_workspace_bytes(int gw, int gh, int n_obs);
+int smvs_dsm_viewshed(const float* dsm, int gw, int gh, float nodata, double xres, double yres, double c256, double r2max,
+                      const int* obs /* HOST, n_obs x 5: col, row, eye, mode, tgt */, int n_obs,
+                      unsigned char* seen, float* above /* may be NULL */, int* status,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_los(const float* dsm, int gw, int gh, float nodata, double xres, double yres, double c256, double r2max,
+                 const int* pairs /* DEVICE, n_pairs x 7: col_o, row_o, eye, mode, col_t, row_t, tgt */, int n_pairs,
+                 unsigned char* seen, float* above /* may be NULL */, void* stream);
 size_t smvs_dsm_outline_workspace_bytes(int gw, int gh, int max_edges);
 int smvs_dsm_outline_count(const int* labels, int gw, int gh, int n, int max_edges, int* counts,
                            void* workspace, size_t workspace_bytes, void* stream);

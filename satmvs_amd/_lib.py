@@ -99,6 +99,8 @@ _SIGNATURES = {
     "smvs_dsm_shadow": [_vp, _i, _i, _f] + [C.c_double] * 5 + [_vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_gradient": [_vp, _i, _i, _f, C.c_double, C.c_double, _vp, _vp, _vp],
     "smvs_dsm_horizon": [_vp, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp],
+    "smvs_dsm_viewshed": [_vp, _i, _i, _f] + [C.c_double] * 4 + [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_los": [_vp, _i, _i, _f] + [C.c_double] * 4 + [_vp, _i, _vp, _vp, _vp],
     "smvs_dsm_outline_count": [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "smvs_dsm_outline_write": [_vp] + [_i] * 6 + [_vp] * 7 + [_sz, _vp],
     "smvs_dsm_burn": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
@@ -128,6 +130,7 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_dsm_morph_workspace_bytes": [_i] * 3, "smvs_dsm_label_workspace_bytes": [_i] * 2,
                "smvs_dsm_shift_workspace_bytes": [_i] * 5, "smvs_dsm_dist_workspace_bytes": [_i] * 3,
                "smvs_dsm_shadow_workspace_bytes": [_i] * 2, "smvs_dsm_horizon_workspace_bytes": [_i] * 3,
+               "smvs_dsm_viewshed_workspace_bytes": [_i] * 3,
                "smvs_dsm_outline_workspace_bytes": [_i] * 3,
                "smvs_dsm_simplify_workspace_bytes": [_i] * 2, "smvs_dsm_contour_workspace_bytes": [_i] * 4,
                "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2,

@@ -1,5 +1,5 @@
 // dsm_common.h -- what the DSM sources (dsm.hip, dsm_render.hip, dsm_post.hip, dsm_morph.hip, dsm_label.hip, dsm_coreg.hip,
-// dsm_mosaic.hip, dsm_sun.hip, dsm_horizon.hip, dsm_outline.hip, dsm_contour.hip, dsm_hydro.hip, dsm_stream.hip) share: the validity test of a cell, the order-preserving uint32 image of a float, the register sorting
+// dsm_mosaic.hip, dsm_sun.hip, dsm_horizon.hip, dsm_viewshed.hip, dsm_outline.hip, dsm_contour.hip, dsm_hydro.hip, dsm_stream.hip) share: the validity test of a cell, the order-preserving uint32 image of a float, the register sorting
 // network, and the host-side grid-size and aliasing checks.
 #pragma once
 #include <math.h>

@@ -73,6 +73,12 @@ and horizon maps, which turn every further sun (or satellite) into a comparison 
     seen = horizon_lit(tan_h, azimuths, azimuth=100.0, elevation=35.0)   # 0 no height, 1 seen from there, 2 hidden
     exposure = sun_exposure_from_horizon(dsm, grid, tan_h, azimuths, suns, weights)   # sun_exposure without a scan per sun
 
+and viewsheds, what an eye on or above the surface sees (a mast, a roof, a road), with earth curvature and refraction:
+
+    seen = viewshed(dsm, grid, [(row, col)], observer_height=1.6)   # (1, gh, gw) uint8: 0 no height, 1 seen, 2 hidden, 3 out of range
+    count = visibility_count(seen)                             # how many observers see each cell
+    code = line_of_sight(dsm, grid, a, b)                      # the same rule for pairs of cells; intervisibility(dsm, grid, points)
+
 and the reverse direction, a DSM rendered into one view's image-space heights (e.g. `height/` ground truth for a tile):
 
     dsm, grid = read_dsm("gt.tif")                             # float32 + its world file
@@ -118,6 +124,10 @@ the grid, a lane per line, cut into bands with an exact carry, the east-west dir
 smvs_dsm_gradient is Horn's 3 x 3 gradient, one lane per cell.
 smvs_dsm_horizon walks the same sheared lines with the upper convex hull of the cells passed so far as a stack of links in
 memory, slopes compared by exact int64 cross-multiplication, a lane per (direction, line), all directions of a call side by side.
+smvs_dsm_viewshed walks one line of sight per (observer, target cell) over heights quantised once per call, the minor
+coordinate from an integer error accumulator and every sample compared with the target by an int64 cross-multiplication, a
+wave an 8 x 8 block of targets, all observers of a call in one launch.  smvs_dsm_los runs the same device function over a
+device list of pairs, reading the floats themselves.
 smvs_rpc_ortho projects every cell into a view, marches the ray up through the same surface to test occlusion, and samples
 the image bilinearly.
 `proj` is a transverse_mercator.TransverseMercator (whu_tlc_projection() for WHU-TLC).  There is no CPU fallback.
@@ -2702,3 +2712,182 @@ def sun_exposure_from_horizon(dsm, grid, tan_h, azimuths, suns, weights=None, in
         total = total + torch.where(hidden, torch.zeros_like(term), term)
     ok = _valid_cells(z, nodata) & ~torch.isnan(t[0])
     return _back(as_numpy, torch.where(ok, total, torch.full_like(total, float("nan"))).float())
+
+
+# ---- viewsheds: exact lines of sight from observers on or above the surface ------------------------------------------------------
+MAX_VIEWSHED_OBSERVERS = 64                                       # observers of one smvs_dsm_viewshed call
+VIEWSHED_MAX_SIDE = 65536                                         # cells along a side of the grid
+VIEWSHED_MAX_UNITS = 1 << 23                                      # eye and target heights, in units of 2^-8 m (32768 m)
+INVALID_OBSERVER = ("raise", "mark")
+
+
+def viewshed_terms(grid, curvature=True, refraction=0.13, earth_radius=6371008.8, max_distance=None):
+    """The four doubles smvs_dsm_viewshed and smvs_dsm_los take over `grid`: xres, yres, c256 = 256 (1 - refraction) / (2
+    earth_radius) -- the drop of the surface below the observer's horizontal plane per squared metre of distance, in units
+    of 2^-8 m, lessened by the bending of the ray; 0 without `curvature` -- and r2max = max_distance^2 [m^2], +inf for None.
+    Checked against the limits of the entries.  -> (xres, yres, c256, r2max)."""
+    _grid_checked(grid, "grid")
+    gw, gh = int(grid.width), int(grid.height)
+    if gw > VIEWSHED_MAX_SIDE or gh > VIEWSHED_MAX_SIDE:
+        raise ValueError("a viewshed's grid has at most %d cells along a side, got %d x %d" % (VIEWSHED_MAX_SIDE, gw, gh))
+    xres, yres = float(grid.xres), float(grid.yres)
+    refraction = _finite(refraction, "refraction")
+    if refraction > 1.0:
+        raise ValueError("refraction must be at most 1, got %r" % refraction)
+    earth_radius = _finite(earth_radius, "earth_radius")
+    if not earth_radius > 0.0:
+        raise ValueError("earth_radius must be > 0 [m], got %r" % earth_radius)
+    c256 = 256.0 * (1.0 - refraction) / (2.0 * earth_radius) if curvature else 0.0
+    w, h = gw * xres, gh * yres
+    if not c256 * (w * w + h * h) < 2.0 ** 30:
+        raise ValueError("the grid is too long for a viewshed: the drop across it must stay below 2^22 m")
+    r2max = math.inf
+    if max_distance is not None:
+        max_distance = _finite(max_distance, "max_distance")
+        r2max = max_distance * max_distance
+        if not (max_distance > 0.0 and r2max > 0.0):
+            raise ValueError("max_distance must be > 0 [m] or None, got %r" % max_distance)
+    return xres, yres, c256, r2max
+
+
+def _cells_checked(cells, shape, name):
+    """An (m, 2) list of (row, col) with m >= 1, every cell on the grid -> int64 host array."""
+    gh, gw = shape
+    p = cells.cpu().numpy() if isinstance(cells, torch.Tensor) else np.asarray(cells)
+    if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+        raise ValueError("%s is an (m, 2) list of (row, col) with m >= 1, got shape %s" % (name, tuple(p.shape)))
+    if not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("%s (row, col) are integers, got %s" % (name, p.dtype))
+    if int(p.min()) < 0 or int(p[:, 0].max()) >= gh or int(p[:, 1].max()) >= gw:
+        raise ValueError("%s must lie on the %d x %d grid" % (name, gh, gw))
+    return p.astype(np.int64)
+
+
+def _height_units(h, m, name, lowest):
+    """Heights [m], a number or one per item, as int32 units of 2^-8 m: rint(256 h), within lowest .. 2^23."""
+    a = np.asarray(h, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(m, float(a))
+    if a.shape != (m,):
+        raise ValueError("%s is a number or one number per item (%d), got shape %s" % (name, m, tuple(a.shape)))
+    if not np.isfinite(a).all():
+        raise ValueError("%s must be finite, got %r" % (name, h))
+    units = np.rint(256.0 * a)
+    if (units < lowest).any() or (units > VIEWSHED_MAX_UNITS).any():
+        raise ValueError("%s must lie in %g .. 32768 m, got %r" % (name, lowest / 256.0, h))
+    return units.astype(np.int32)
+
+
+def _invalid_observers(z, rc, nodata):
+    """Indices of the cells of rc (row, col) that hold no height by the rule of smvs_dsm_viewshed (one read of the device)."""
+    at = torch.as_tensor(rc, device=z.device)
+    zo = z[at[:, 0], at[:, 1]]
+    ok = torch.isfinite(zo) & (zo != float(np.float32(nodata))) & (zo.abs() <= 32768.0)
+    return (~ok).nonzero().flatten().cpu().tolist()
+
+
+def viewshed(dsm, grid, observers, observer_height=1.6, target_height=0.0, absolute=False, max_distance=None, curvature=True,
+             refraction=0.13, nodata=-999.0, return_above=False, invalid_observer="raise"):
+    """Viewsheds of a DSM (include/satmvs.h smvs_dsm_viewshed, DESIGN.md section 9, "Viewshed"): for every observer of the
+    list and every cell, whether an eye observer_height [m] above the observer's own cell (with `absolute`, at that height
+    itself) sees a point target_height [m] above the cell, along one exact line of sight per cell: the cells the line steps
+    through, heights in units of 2^-8 m, the earth's curvature and the `refraction` of the ray as a drop that grows with the
+    squared distance (curvature=False: a flat earth), every comparison exact, grazing counted as seen.  observers: an (m, 2)
+    list of (row, col) cells on the grid, m >= 1 (DSMGrid.cell_of gives them from map coordinates); the heights are numbers
+    or one per observer, not negative unless absolute; max_distance [m] puts cells further away out of range.  More than 64
+    observers go in chunks of 64; the bits do not depend on the chunking.  An observer that stands (not absolute) on a cell
+    without a height raises ValueError; with invalid_observer="mark" its map is 0 everywhere instead, which tells it from any
+    other observer's: an observer that stands sees at least its own cell (the entry's status words are not returned).  dsm (grid.height,
+    grid.width) of any real dtype (taken as float32), numpy or a device tensor.
+    -> seen (m, gh, gw) uint8: 0 no height, 1 seen, 2 hidden, 3 out of range (and, with return_above, above (m, gh, gw)
+    float32: what must stand on a hidden cell [m] to be seen, 0 at seen cells, nodata at codes 0 and 3); numpy if the DSM came
+    as numpy, device tensors otherwise."""
+    xres, yres, c256, r2max = viewshed_terms(grid, curvature, refraction, max_distance=max_distance)
+    if invalid_observer not in INVALID_OBSERVER:
+        raise ValueError("invalid_observer must be one of %s, got %r" % (INVALID_OBSERVER, invalid_observer))
+    rc = _cells_checked(observers, (grid.height, grid.width), "observers")
+    m = rc.shape[0]
+    eye = _height_units(observer_height, m, "observer_height", -VIEWSHED_MAX_UNITS if absolute else 0)
+    tgt = _height_units(target_height, m, "target_height", 0)
+    dsm = _dsm_converted(dsm, grid)
+    z, as_numpy = _to_device(dsm, torch.float32)
+    gh, gw = z.shape
+    if not absolute and invalid_observer == "raise":
+        bad = _invalid_observers(z, rc, nodata)
+        if bad:
+            raise ValueError("observer %d stands on cell (row %d, col %d), which holds no height" % (bad[0], rc[bad[0], 0], rc[bad[0], 1]))
+    obs = np.stack([rc[:, 1], rc[:, 0], eye, np.full(m, 1 if absolute else 0), tgt], axis=1).astype(np.int32)
+    nbytes = _lib.load().smvs_dsm_viewshed_workspace_bytes(gw, gh, min(m, MAX_VIEWSHED_OBSERVERS))
+    if nbytes == 0:
+        raise ValueError("unsupported viewshed: %d x %d cells" % (gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    seen = torch.empty((m, gh, gw), dtype=torch.uint8, device=z.device)
+    above = torch.empty((m, gh, gw), dtype=torch.float32, device=z.device) if return_above else None
+    status = torch.empty(m, dtype=torch.int32, device=z.device)
+    for k0 in range(0, m, MAX_VIEWSHED_OBSERVERS):
+        n = min(MAX_VIEWSHED_OBSERVERS, m - k0)
+        _call(z.device, "smvs_dsm_viewshed", z, gw, gh, float(nodata), xres, yres, c256, r2max, np.ascontiguousarray(obs[k0:k0 + n]), n,
+              seen[k0:k0 + n], None if above is None else above[k0:k0 + n], status[k0:k0 + n], ws, nbytes)
+    seen, above = _back(as_numpy, seen, above)
+    return (seen, above) if return_above else seen
+
+
+def visibility_count(seen):
+    """The cumulative viewshed: how many observers of viewshed()'s seen (m, gh, gw) uint8 see each cell (code 1), summed by
+    torch on the device.  -> (gh, gw) int32, numpy or tensor as seen came."""
+    as_numpy = not isinstance(seen, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(seen)) if as_numpy else seen
+    if t.ndim != 3 or t.shape[0] < 1 or t.dtype != torch.uint8:
+        raise ValueError("seen is (m, gh, gw) uint8 with m >= 1, got %s of shape %s" % (t.dtype, tuple(t.shape)))
+    t, _ = _to_device(t)
+    return _back(as_numpy, (t == 1).sum(dim=0, dtype=torch.int32))
+
+
+def _los(z, grid, pairs, terms, nodata, return_above):
+    """smvs_dsm_los over an (n, 7) int32 host array of pairs -> (seen (n) uint8, above (n) float32 or None) on z's device."""
+    gh, gw = z.shape
+    n = pairs.shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 lines of sight go in one call, got %d" % n)
+    p = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(z.device)
+    seen = torch.empty(n, dtype=torch.uint8, device=z.device)
+    above = torch.empty(n, dtype=torch.float32, device=z.device) if return_above else None
+    _call(z.device, "smvs_dsm_los", z, gw, gh, float(nodata), terms[0], terms[1], terms[2], terms[3], p, n, seen, above)
+    return seen, above
+
+
+def line_of_sight(dsm, grid, a, b, observer_height=1.6, target_height=0.0, absolute=False, max_distance=None, curvature=True,
+                  refraction=0.13, nodata=-999.0, return_above=False):
+    """Lines of sight between pairs of cells by the rule of viewshed() (include/satmvs.h smvs_dsm_los): pair k has its eye
+    observer_height above cell a[k] (with `absolute`, at that height) and its target target_height above cell b[k].  a, b:
+    (m, 2) lists of (row, col) of equal length; the heights are numbers or one per pair.
+    -> code (m) uint8: 0 no height at the target or (not absolute) under the observer, 1 seen, 2 hidden, 3 out of range (and,
+    with return_above, above (m) float32 as in viewshed); numpy if the DSM came as numpy, device tensors otherwise."""
+    terms = viewshed_terms(grid, curvature, refraction, max_distance=max_distance)
+    shape = (grid.height, grid.width)
+    a, b = _cells_checked(a, shape, "a"), _cells_checked(b, shape, "b")
+    m = a.shape[0]
+    if b.shape[0] != m:
+        raise ValueError("a and b hold one cell per line of sight: %d and %d cells" % (m, b.shape[0]))
+    eye = _height_units(observer_height, m, "observer_height", -VIEWSHED_MAX_UNITS if absolute else 0)
+    tgt = _height_units(target_height, m, "target_height", 0)
+    z, as_numpy = _to_device(_dsm_converted(dsm, grid), torch.float32)
+    pairs = np.stack([a[:, 1], a[:, 0], eye, np.full(m, 1 if absolute else 0), b[:, 1], b[:, 0], tgt], axis=1)
+    seen, above = _back(as_numpy, *_los(z, grid, pairs, terms, nodata, return_above))
+    return (seen, above) if return_above else seen
+
+
+def intervisibility(dsm, grid, points, height=1.6, max_distance=None, curvature=True, refraction=0.13, nodata=-999.0):
+    """Which of `points` see each other: entry (i, j) is line_of_sight from `height` [m, a number >= 0] above points[i] to
+    `height` above points[j], all m^2 lines in one smvs_dsm_los call.  The diagonal is 1 at points with a height; the matrix
+    need not be symmetric (a line samples other cells than its reverse).  points: an (m, 2) list of (row, col).
+    -> (m, m) uint8 with the codes of line_of_sight; numpy if the DSM came as numpy, a device tensor otherwise."""
+    terms = viewshed_terms(grid, curvature, refraction, max_distance=max_distance)
+    p = _cells_checked(points, (grid.height, grid.width), "points")
+    m = p.shape[0]
+    units = _height_units(height, 1, "height", 0)[0]
+    z, as_numpy = _to_device(_dsm_converted(dsm, grid), torch.float32)
+    i, j = np.repeat(np.arange(m), m), np.tile(np.arange(m), m)
+    pairs = np.stack([p[i, 1], p[i, 0], np.full(m * m, units), np.zeros(m * m, np.int64), p[j, 1], p[j, 0], np.full(m * m, units)], axis=1)
+    seen, _ = _los(z, grid, pairs, terms, nodata, False)
+    return _back(as_numpy, seen.reshape(m, m))
