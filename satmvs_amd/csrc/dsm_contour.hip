@@ -30,28 +30,18 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "dsm_chain.h"
 #include "dsm_common.h"
-#include "dsm_scan.h"
 #include "smvs_host.h"
 
 namespace smvs {
 
-enum { CT_NC = 0, CT_NL = 1, CT_NV = 2, CT_ERR = 3, CT_TOTAL = 4, CT_CAP = 5, CT_SUM64 = 6 };   // the workspace's tail words (6, 7: a 64-bit sum)
+enum { CT_CAP = 5, CT_SUM64 = 6 };                           // the tail words past dsm_chain.h's five (6, 7: a 64-bit sum)
 constexpr int CT_MAX_LEVELS = 4096, CT_CHUNK = 512;
-constexpr float CT_MAX_Z = 32768.0f;
-constexpr unsigned CT_NONE = 0xffffffffu;                    // no predecessor
-
-typedef unsigned long long u64;
 
 struct CtChunk { int v[CT_CHUNK]; };                         // a piece of the host's level table, passed by value
 
-__device__ __forceinline__ bool ct_node(const float* __restrict__ dsm, size_t i, float nodata, int& q)
-{
-    const float z = dsm[i];
-    if (!(dsm_cell_valid(z, nodata) && fabsf(z) <= CT_MAX_Z)) return false;
-    q = (int)__double2ll_rn(__dmul_rn((double)z, 256.0));
-    return true;
-}
+__device__ __forceinline__ bool ct_node(const float* __restrict__ dsm, size_t i, float nodata, int& q) { return dsm_quantum(dsm[i], nodata, q); }
 
 // The first level above x (x even, the levels odd: never equal).
 __device__ __forceinline__ int ct_first_above(const int* lev, int n, int x)
@@ -66,11 +56,13 @@ __device__ __forceinline__ int ct_first_above(const int* lev, int n, int x)
 }
 
 // The number of crossings the kernels past the count work on: none if there are more than the caller made room for.
-__device__ __forceinline__ int ct_limit(const int* tail, unsigned cap)
-{
-    const int v = tail[CT_NC];
-    return *(const u64*)(tail + CT_SUM64) > (u64)cap || v < 0 || (unsigned)v > cap ? 0 : v;
-}
+struct CtLimit {
+    __device__ __forceinline__ int operator()(const int* tail, unsigned cap) const
+    {
+        const int v = tail[CH_N];
+        return *(const u64*)(tail + CT_SUM64) > (u64)cap || v < 0 || (unsigned)v > cap ? 0 : v;
+    }
+};
 
 // The two ends of lattice edge e, if it exists and both hold a height: a the end the eid names, b the other.
 __device__ __forceinline__ bool ct_edge(const float* __restrict__ dsm, int gw, int gh, float nodata, unsigned e, int& r, int& c, int& o, int& qa, int& qb)
@@ -123,7 +115,7 @@ __global__ void ct_room(unsigned cap, int* tail)
 {
     if (threadIdx.x != 0) return;
     const u64 all = *(const u64*)(tail + CT_SUM64);
-    if (all > (u64)INT_MAX || (int)all != tail[CT_NC] || (cap > 0 && all > cap)) tail[CT_ERR] = 1;
+    if (all > (u64)INT_MAX || (int)all != tail[CH_N] || (cap > 0 && all > cap)) tail[CH_ERR] = 1;
     tail[CT_CAP] = (int)cap;
 }
 
@@ -136,7 +128,7 @@ void ct_link(const float* __restrict__ dsm, int gw, int gh, float nodata, const 
 {
     __shared__ int lev_s[CT_MAX_LEVELS];
     ct_levels_to_lds(lev, nl, lev_s);
-    const unsigned nc = (unsigned)ct_limit(tail, cap);       // the same for every lane: no kernel of this launch writes these words
+    const unsigned nc = (unsigned)CtLimit()(tail, cap);       // the same for every lane: no kernel of this launch writes these words
     if (nc == 0) return;                                     // more crossings than room: nothing is written
     const unsigned e = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -149,7 +141,7 @@ void ct_link(const float* __restrict__ dsm, int gw, int gh, float nodata, const 
             cnt = ct_first_above(lev_s, nl, 2 * max(qa, qb)) - lo;
         }
         b0 = (unsigned)base[e];
-        if (cnt && (b0 > nc || (unsigned)cnt > nc - b0)) { atomicOr(tail + CT_ERR, 1); cnt = 0; }
+        if (cnt && (b0 > nc || (unsigned)cnt > nc - b0)) { atomicOr(tail + CH_ERR, 1); cnt = 0; }
     }
     int inc = cnt;
 #pragma unroll
@@ -171,7 +163,7 @@ void ct_link(const float* __restrict__ dsm, int gw, int gh, float nodata, const 
         if (i0 + lane >= total) continue;
         const unsigned ek = e_wave + (unsigned)k;
         int r, c, o, qa, qb;
-        if (id >= nc || ek >= n_edges || !ct_edge(dsm, gw, gh, nodata, ek, r, c, o, qa, qb) || (unsigned)l >= (unsigned)nl) { atomicOr(tail + CT_ERR, 1); continue; }
+        if (id >= nc || ek >= n_edges || !ct_edge(dsm, gw, gh, nodata, ek, r, c, o, qa, qb) || (unsigned)l >= (unsigned)nl) { atomicOr(tail + CH_ERR, 1); continue; }
         const int K = lev_s[l];
         const bool a_above = 2 * qa > K;
         // H the end above, L the other; the line passes with H on its left, so it heads from the edge by (dr, dc)
@@ -194,7 +186,7 @@ void ct_link(const float* __restrict__ dsm, int gw, int gh, float nodata, const 
             const unsigned e2 = 2u * ((unsigned)min(pr, sr) * (unsigned)gw + (unsigned)min(pc, sc)) + (pr != sr ? 1u : 0u);
             const int lo2 = ct_first_above(lev_s, nl, 2 * min(qp, qs));
             const unsigned id2 = (unsigned)base[e2] + (unsigned)(l - lo2);
-            if (l < lo2 || id2 >= nc) { atomicOr(tail + CT_ERR, 1); succ = false; }
+            if (l < lo2 || id2 >= nc) { atomicOr(tail + CH_ERR, 1); succ = false; }
             else pred[id2] = id;
         }
         cedge[id] = (int)ek;
@@ -208,39 +200,15 @@ __global__ __launch_bounds__(OL_THREADS)
 void ct_init(const unsigned* __restrict__ pred, u64* __restrict__ val, unsigned cap, const int* tail)
 {
     const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (j >= (unsigned)ct_limit(tail, cap)) return;
-    val[j] = (u64)(j | (pred[j] != CT_NONE ? 0x80000000u : 0u)) << 32;
-}
-
-// One round of the doubling: the window of a crossing grows by the window of the crossing `add` places back, unless it has
-// reached the start of an open chain.
-__global__ __launch_bounds__(OL_THREADS)
-void ct_double(const unsigned* __restrict__ pin, const u64* __restrict__ vin, unsigned* __restrict__ pout, u64* __restrict__ vout,
-               unsigned add, unsigned cap, int* tail)
-{
-    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    const unsigned nc = (unsigned)ct_limit(tail, cap);
-    if (j >= nc) return;
-    const u64 a = vin[j];
-    unsigned p = pin[j];
-    if (p != CT_NONE && p >= nc) { atomicOr(tail + CT_ERR, 1); p = CT_NONE; }
-    if (p == CT_NONE) {
-        vout[j] = a;
-        pout[j] = CT_NONE;
-        return;
-    }
-    unsigned q = pin[p];
-    if (q != CT_NONE && q >= nc) { atomicOr(tail + CT_ERR, 1); q = CT_NONE; }
-    const u64 b = vin[p] + add;
-    vout[j] = a < b ? a : b;
-    pout[j] = q;
+    if (j >= (unsigned)CtLimit()(tail, cap)) return;
+    val[j] = (u64)(j | (pred[j] != CH_NONE ? 0x80000000u : 0u)) << 32;
 }
 
 // What a crossing is after the doubling: 0 dropped (neither predecessor nor successor), 1 inside a line, 2 its first vertex,
 // 3 the last vertex of an open chain (2 | 1 cannot happen: a line has two vertices).
 __device__ __forceinline__ int ct_role(u64 v, unsigned p0, int has_succ)
 {
-    if (p0 == CT_NONE && !has_succ) return 0;
+    if (p0 == CH_NONE && !has_succ) return 0;
     if ((unsigned)v == 0u) return 2;
     return has_succ ? 1 : 3;
 }
@@ -251,7 +219,7 @@ void ct_starts(const u64* __restrict__ val, const unsigned* __restrict__ pred0, 
                int* __restrict__ lscan, int* __restrict__ llen, unsigned cap, int* tail)
 {
     const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    const unsigned nc = (unsigned)ct_limit(tail, cap);
+    const unsigned nc = (unsigned)CtLimit()(tail, cap);
     bool vertex = false;
     if (j < nc) {
         const u64 v = val[j];
@@ -260,17 +228,12 @@ void ct_starts(const u64* __restrict__ val, const unsigned* __restrict__ pred0, 
         lscan[j] = role == 2;
         if (role == 3) {
             const unsigned start = (unsigned)(v >> 32) & 0x7fffffffu;
-            if (start >= nc) atomicOr(tail + CT_ERR, 1);
+            if (start >= nc) atomicOr(tail + CH_ERR, 1);
             else llen[start] = (int)((unsigned)v + 1u);
         }
     }
     const int cnt = __popcll(__ballot(vertex));
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(tail + CT_NV, cnt);
-}
-
-__global__ void ct_counts_out(const int* __restrict__ tail, int* __restrict__ counts)
-{
-    if (threadIdx.x < 3) counts[threadIdx.x] = tail[CT_ERR] ? -1 : tail[threadIdx.x];
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(tail + CH_VERTICES, cnt);
 }
 
 // ---- write -------------------------------------------------------------------------------------------------------------------
@@ -282,35 +245,13 @@ void ct_line_init(const u64* __restrict__ val, const unsigned* __restrict__ pred
                   int* tail, int* __restrict__ skey, int* __restrict__ sval)
 {
     const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (j == 0 && ((unsigned)tail[CT_NC] != nc || (unsigned)tail[CT_NL] != nl || (unsigned)tail[CT_NV] != nv || (unsigned)tail[CT_CAP] != nc))
-        atomicOr(tail + CT_ERR, 1);                          // the layout of the workspace follows max_cross: it must have been n_cross
+    if (j == 0 && ((unsigned)tail[CH_N] != nc || (unsigned)tail[CH_LINES] != nl || (unsigned)tail[CH_VERTICES] != nv || (unsigned)tail[CT_CAP] != nc))
+        atomicOr(tail + CH_ERR, 1);                          // the layout of the workspace follows max_cross: it must have been n_cross
     if (j >= nc || ct_role(val[j], pred0[j], cflag[j] & 1) != 2) return;
     const unsigned q = (unsigned)lscan[j], l = clev[j];
-    if (q >= nl || l >= (unsigned)n_levels) { atomicOr(tail + CT_ERR, 1); return; }
+    if (q >= nl || l >= (unsigned)n_levels) { atomicOr(tail + CH_ERR, 1); return; }
     skey[q] = (int)l;
     sval[q] = (int)j;
-}
-
-__global__ __launch_bounds__(OL_THREADS)
-void ct_sort_flag(const int* __restrict__ skey, int* __restrict__ spos, unsigned nl, int bit)
-{
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (i < nl) spos[i] = !(((unsigned)skey[i] >> bit) & 1u);
-}
-
-// The stable split on one bit: the keys without the bit keep their order in front, the others theirs behind.
-__global__ __launch_bounds__(OL_THREADS)
-void ct_sort_scatter(const int* __restrict__ kin, const int* __restrict__ vin, const int* __restrict__ spos, int* tail,
-                     int* __restrict__ kout, int* __restrict__ vout, unsigned nl, int bit)
-{
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (i >= nl) return;
-    const int k = kin[i];
-    const unsigned before = (unsigned)spos[i], zeros = (unsigned)tail[CT_TOTAL];
-    unsigned d = (((unsigned)k >> bit) & 1u) ? zeros + (i - before) : before;
-    if (d >= nl) { atomicOr(tail + CT_ERR, 1); d = i; }
-    kout[d] = k;
-    vout[d] = vin[i];
 }
 
 // One lane per line in its final place: its level, whether it is closed, its length, and its place written where its
@@ -326,33 +267,18 @@ void ct_line_table(const int* __restrict__ skey, const int* __restrict__ sval, c
     const unsigned j0 = (unsigned)sval[r];
     unsigned len = 0;
     bool closed = false;
-    if (j0 >= nc) atomicOr(tail + CT_ERR, 1);
+    if (j0 >= nc) atomicOr(tail + CH_ERR, 1);
     else {
         lline[j0] = (int)r;
         const unsigned p = pred0[j0];
-        closed = p != CT_NONE;
+        closed = p != CH_NONE;
         if (!closed) len = (unsigned)llen[j0];
-        else if (p >= nc) atomicOr(tail + CT_ERR, 1);
+        else if (p >= nc) atomicOr(tail + CH_ERR, 1);
         else len = (unsigned)val[p] + 1u;
-        if (len < 2 || len > nv) { atomicOr(tail + CT_ERR, 1); len = 0; }
+        if (len < 2 || len > nv) { atomicOr(tail + CH_ERR, 1); len = 0; }
     }
     line_closed[r] = closed ? 1 : 0;
     ebase[r] = (int)len;
-}
-
-// first_line[k], k = 0 .. n_levels: the first line whose level index is k or above; entry n_levels is n_lines.
-__global__ __launch_bounds__(OL_THREADS)
-void ct_first_line(const int* __restrict__ skey, unsigned nl, int n_levels, int* __restrict__ first_line)
-{
-    const unsigned k = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (k > (unsigned)n_levels) return;
-    unsigned lo = 0, hi = nl;
-    for (int step = 0; step < 32 && lo < hi; ++step) {
-        const unsigned mid = lo + (hi - lo) / 2;
-        if ((unsigned)skey[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    first_line[k] = (int)lo;
 }
 
 // Every crossing of a line: its vertex at (offset of its line + its rank).
@@ -373,7 +299,7 @@ void ct_vertices(const float* __restrict__ dsm, int gw, int gh, float nodata, co
     const unsigned e = (unsigned)cedge[j], l = clev[j];
     int r, c, o, qa, qb;
     if (line >= nl || at >= nv || at < rank || e >= n_edges || l >= (unsigned)n_levels || !ct_edge(dsm, gw, gh, nodata, e, r, c, o, qa, qb) || qa == qb) {
-        atomicOr(tail + CT_ERR, 1);
+        atomicOr(tail + CH_ERR, 1);
         return;
     }
     const double t = __ddiv_rn((double)(lev[l] - 2 * qa), (double)(2 * qb - 2 * qa));
@@ -386,13 +312,13 @@ __global__ __launch_bounds__(OL_THREADS)
 void ct_offsets(const int* __restrict__ ebase, unsigned nl, unsigned nv, int* tail, int* __restrict__ offset)
 {
     const unsigned r = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (r == 0 && (unsigned)tail[CT_TOTAL] != nv) atomicOr(tail + CT_ERR, 1);
+    if (r == 0 && (unsigned)tail[CH_TOTAL] != nv) atomicOr(tail + CH_ERR, 1);
     if (r < nl) offset[r] = ebase[r];
 }
 
 __global__ void ct_finish(const int* __restrict__ tail, unsigned nl, unsigned nv, int* __restrict__ offset)
 {
-    if (threadIdx.x == 0) offset[nl] = tail[CT_ERR] ? -1 : (int)nv;
+    if (threadIdx.x == 0) offset[nl] = tail[CH_ERR] ? -1 : (int)nv;
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -442,26 +368,6 @@ static const char* levels_check(const int* levels, int n_levels)
     return nullptr;
 }
 
-static int contour_rounds(unsigned max_cross)
-{
-    int rounds = 0;
-    while (rounds < 31 && (1u << rounds) < max_cross) ++rounds;
-    return rounds;
-}
-
-struct CtBuf { const void* p; size_t bytes; const char* name; };
-
-static const char* contour_overlap(const CtBuf* buf, int nbuf, const char*& other)
-{
-    for (int i = 1; i < nbuf; ++i)
-        for (int j = 0; j < i; ++j)
-            if (buf[i].p && buf[j].p && buf[i].bytes && buf[j].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes)) {
-                other = buf[j].name;
-                return buf[i].name;
-            }
-    return nullptr;
-}
-
 // The host's level table into the workspace, 512 levels a launch through the kernel arguments: no copy from pageable memory.
 static int contour_upload(const int* levels, int n_levels, int* lev, hipStream_t s)
 {
@@ -469,8 +375,7 @@ static int contour_upload(const int* levels, int n_levels, int* lev, hipStream_t
         CtChunk chunk;
         const int n = n_levels - at < CT_CHUNK ? n_levels - at : CT_CHUNK;
         for (int i = 0; i < CT_CHUNK; ++i) chunk.v[i] = i < n ? levels[at + i] : 0;
-        hipLaunchKernelGGL(ct_upload, dim3(CT_CHUNK / OL_THREADS), dim3(OL_THREADS), 0, s, chunk, at, n, lev);
-        if (int rc = check_launch("ct_upload")) return rc;
+        DSM_LAUNCH(ct_upload, CT_CHUNK, OL_THREADS, s, chunk, at, n, lev);
     }
     return SMVS_OK;
 }
@@ -495,49 +400,38 @@ SMVS_EXPORT int smvs_dsm_contour_count(const float* dsm, int gw, int gh, float n
     if (const char* msg = levels_check(levels, n_levels)) return fail(SMVS_ERR_ARG, "%s", msg);
     const ContourWorkspace w = contour_workspace(gw, gh, (size_t)max_cross);
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-    const CtBuf buf[] = {{dsm, (size_t)gw * gh * 4, "dsm"}, {counts, 12, "counts"}, {workspace, w.bytes, "workspace"}};
+    const DsmBuf buf[] = {{dsm, (size_t)gw * gh * 4, "dsm"}, {counts, 12, "counts"}, {workspace, w.bytes, "workspace"}};
     const char* other = nullptr;
-    if (const char* name = contour_overlap(buf, 3, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    if (const char* name = dsm_first_alias(buf, 3, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int *tail = (int*)(ws + w.tail), *s1 = (int*)(ws + w.s1), *s2 = (int*)(ws + w.s2), *lev = (int*)(ws + w.lev), *base = (int*)(ws + w.base);
     if (hipMemsetAsync(tail, 0, 256, s) != hipSuccess) return check_launch("dsm_contour_count (clearing the counts)");
     int rc;
     if ((rc = contour_upload(levels, n_levels, lev, s))) return rc;
-    const unsigned edge_blocks = (w.n_edges + OL_THREADS - 1) / OL_THREADS, cap = (unsigned)max_cross;
-    hipLaunchKernelGGL(ct_edges, dim3(edge_blocks), dim3(OL_THREADS), 0, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges, base, tail);
-    if ((rc = check_launch("ct_edges"))) return rc;
-    if ((rc = ol_scan_exclusive(base, w.n_edges, nullptr, s1, s2, tail + CT_NC, s, "ol_scan (crossings)"))) return rc;
-    hipLaunchKernelGGL(ct_room, dim3(1), dim3(64), 0, s, cap, tail);
-    if ((rc = check_launch("ct_room"))) return rc;
+    const unsigned cap = (unsigned)max_cross;
+    DSM_LAUNCH(ct_edges, w.n_edges, OL_THREADS, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges, base, tail);
+    if ((rc = ol_scan_exclusive(base, w.n_edges, nullptr, s1, s2, tail + CH_N, s, "ol_scan (crossings)"))) return rc;
+    DSM_LAUNCH(ct_room, 1, 64, s, cap, tail);
     if (max_cross > 0) {
-        const unsigned cross_blocks = (cap + OL_THREADS - 1) / OL_THREADS;
         unsigned* pred[3] = {(unsigned*)(ws + w.pred0), (unsigned*)(ws + w.preda), (unsigned*)(ws + w.predb)};
         u64* val[2] = {(u64*)(ws + w.vala), (u64*)(ws + w.valb)};
         int* cedge = (int*)(ws + w.cedge);
         unsigned short* clev = (unsigned short*)(ws + w.clev);
         unsigned char* cflag = (unsigned char*)(ws + w.cflag);
         if (hipMemsetAsync(pred[0], 0xff, (size_t)cap * 4, s) != hipSuccess) return check_launch("dsm_contour_count (clearing the predecessors)");
-        hipLaunchKernelGGL(ct_link, dim3(edge_blocks), dim3(OL_THREADS), 0, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges,
-                           (const int*)base, cap, tail, cedge, clev, cflag, pred[0]);
-        if ((rc = check_launch("ct_link"))) return rc;
-        hipLaunchKernelGGL(ct_init, dim3(cross_blocks), dim3(OL_THREADS), 0, s, (const unsigned*)pred[0], val[0], cap, (const int*)tail);
-        if ((rc = check_launch("ct_init"))) return rc;
-        const int rounds = contour_rounds(cap);
-        for (int r = 0; r < rounds; ++r) {                   // (pred0, vala) -> (preda, valb) -> (predb, vala) -> (preda, valb) ...
-            hipLaunchKernelGGL(ct_double, dim3(cross_blocks), dim3(OL_THREADS), 0, s, (const unsigned*)pred[r == 0 ? 0 : 1 + (r + 1) % 2],
-                               (const u64*)val[r % 2], pred[1 + r % 2], val[(r + 1) % 2], 1u << r, cap, tail);
-            if ((rc = check_launch("ct_double"))) return rc;
-        }
+        DSM_LAUNCH(ct_link, w.n_edges, OL_THREADS, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges, (const int*)base, cap, tail,
+                   cedge, clev, cflag, pred[0]);
+        DSM_LAUNCH(ct_init, cap, OL_THREADS, s, (const unsigned*)pred[0], val[0], cap, (const int*)tail);
+        int at;
+        if ((rc = chain_order<true, CtLimit>(pred, val, cap, tail, s, &at))) return rc;
         // the two later predecessor arrays have done their work: the start flags and the open chains' lengths live there
         int *lscan = (int*)pred[1], *llen = (int*)pred[2];
-        hipLaunchKernelGGL(ct_starts, dim3(cross_blocks), dim3(OL_THREADS), 0, s, (const u64*)val[rounds % 2], (const unsigned*)pred[0],
-                           (const unsigned char*)cflag, lscan, llen, cap, tail);
-        if ((rc = check_launch("ct_starts"))) return rc;
-        if ((rc = ol_scan_exclusive(lscan, cap, tail + CT_NC, s1, s2, tail + CT_NL, s, "ol_scan (lines)"))) return rc;
+        DSM_LAUNCH(ct_starts, cap, OL_THREADS, s, (const u64*)val[at], (const unsigned*)pred[0], (const unsigned char*)cflag, lscan, llen, cap, tail);
+        if ((rc = ol_scan_exclusive(lscan, cap, tail + CH_N, s1, s2, tail + CH_LINES, s, "ol_scan (lines)"))) return rc;
     }
-    hipLaunchKernelGGL(ct_counts_out, dim3(1), dim3(64), 0, s, (const int*)tail, counts);
-    return check_launch("ct_counts_out");
+    DSM_LAUNCH(chain_counts_out, 1, 64, s, (const int*)tail, counts);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float nodata, const int* levels, int n_levels,
@@ -555,11 +449,11 @@ SMVS_EXPORT int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float n
     const ContourWorkspace w = contour_workspace(gw, gh, (size_t)n_cross);
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     const size_t m = (size_t)n_lines, nvb = (size_t)n_vertices;
-    const CtBuf buf[] = {{dsm, (size_t)gw * gh * 4, "dsm"}, {workspace, w.bytes, "workspace"}, {line_level, m * 4, "line_level"},
+    const DsmBuf buf[] = {{dsm, (size_t)gw * gh * 4, "dsm"}, {workspace, w.bytes, "workspace"}, {line_level, m * 4, "line_level"},
                          {line_closed, m, "line_closed"}, {offset, (m + 1) * 4, "offset"}, {first_line, ((size_t)n_levels + 1) * 4, "first_line"},
                          {vertices, nvb * 16, "vertices"}, {vertex_edge, nvb * 4, "vertex_edge"}};
     const char* other = nullptr;
-    if (const char* name = contour_overlap(buf, 8, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    if (const char* name = dsm_first_alias(buf, 8, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     hipStream_t s = (hipStream_t)stream;
     if (n_lines == 0) {                                      // no line: the two tables that still have entries
         if (hipMemsetAsync(first_line, 0, ((size_t)n_levels + 1) * 4, s) != hipSuccess || hipMemsetAsync(offset, 0, 4, s) != hipSuccess)
@@ -568,7 +462,7 @@ SMVS_EXPORT int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float n
     }
     char* ws = (char*)workspace;
     int *tail = (int*)(ws + w.tail), *s1 = (int*)(ws + w.s1), *s2 = (int*)(ws + w.s2), *lev = (int*)(ws + w.lev);
-    const int rounds = contour_rounds((unsigned)n_cross);
+    const int rounds = chain_rounds((unsigned)n_cross);
     const u64* val = (const u64*)(ws + (rounds % 2 ? w.valb : w.vala));
     int* lline = (int*)(ws + (rounds % 2 ? w.vala : w.valb));                // the doubling word that does not hold the result
     const unsigned* pred0 = (const unsigned*)(ws + w.pred0);
@@ -578,35 +472,21 @@ SMVS_EXPORT int smvs_dsm_contour_write(const float* dsm, int gw, int gh, float n
     int *skey[2] = {(int*)(ws + w.skeya), (int*)(ws + w.skeyb)}, *sval[2] = {(int*)(ws + w.svala), (int*)(ws + w.svalb)};
     int *spos = (int*)(ws + w.spos), *ebase = (int*)(ws + w.ebase);
     const unsigned nc = (unsigned)n_cross, nl = (unsigned)n_lines, nv = (unsigned)n_vertices;
-    const unsigned cross_blocks = (nc + OL_THREADS - 1) / OL_THREADS, line_blocks = (nl + OL_THREADS - 1) / OL_THREADS;
     int rc;
     if ((rc = contour_upload(levels, n_levels, lev, s))) return rc;
-    hipLaunchKernelGGL(ct_line_init, dim3(cross_blocks), dim3(OL_THREADS), 0, s, val, pred0, cflag, clev, lscan, nc, nl, nv, n_levels, tail, skey[0], sval[0]);
-    if ((rc = check_launch("ct_line_init"))) return rc;
-    int bits = 0;
+    DSM_LAUNCH(ct_line_init, nc, OL_THREADS, s, val, pred0, cflag, clev, lscan, nc, nl, nv, n_levels, tail, skey[0], sval[0]);
+    int bits = 0, at;
     while (bits < 12 && ((unsigned)(n_levels - 1) >> bits)) ++bits;
-    for (int b = 0; b < bits; ++b) {
-        hipLaunchKernelGGL(ct_sort_flag, dim3(line_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], spos, nl, b);
-        if ((rc = check_launch("ct_sort_flag"))) return rc;
-        if ((rc = ol_scan_exclusive(spos, nl, nullptr, s1, s2, tail + CT_TOTAL, s, "ol_scan (sort)"))) return rc;
-        hipLaunchKernelGGL(ct_sort_scatter, dim3(line_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], (const int*)sval[b % 2],
-                           (const int*)spos, tail, skey[(b + 1) % 2], sval[(b + 1) % 2], nl, b);
-        if ((rc = check_launch("ct_sort_scatter"))) return rc;
-    }
-    const int *keys = skey[bits % 2], *starts = sval[bits % 2];
-    hipLaunchKernelGGL(ct_line_table, dim3(line_blocks), dim3(OL_THREADS), 0, s, keys, starts, val, pred0, llen, lline, ebase, nc, nl, nv, tail,
-                       line_level, line_closed);
-    if ((rc = check_launch("ct_line_table"))) return rc;
-    hipLaunchKernelGGL(ct_first_line, dim3(((unsigned)n_levels + 1u + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, keys, nl, n_levels, first_line);
-    if ((rc = check_launch("ct_first_line"))) return rc;
-    if ((rc = ol_scan_exclusive(ebase, nl, nullptr, s1, s2, tail + CT_TOTAL, s, "ol_scan (line lengths)"))) return rc;
-    hipLaunchKernelGGL(ct_vertices, dim3(cross_blocks), dim3(OL_THREADS), 0, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges, val, pred0,
-                       cflag, cedge, clev, (const int*)lline, (const int*)ebase, nc, nl, nv, tail, vertices, vertex_edge);
-    if ((rc = check_launch("ct_vertices"))) return rc;
-    hipLaunchKernelGGL(ct_offsets, dim3(line_blocks), dim3(OL_THREADS), 0, s, (const int*)ebase, nl, nv, tail, offset);
-    if ((rc = check_launch("ct_offsets"))) return rc;
-    hipLaunchKernelGGL(ct_finish, dim3(1), dim3(64), 0, s, (const int*)tail, nl, nv, offset);
-    return check_launch("ct_finish");
+    if ((rc = chain_sort(skey, sval, spos, nl, bits, s1, s2, tail, s, &at))) return rc;
+    const int *keys = skey[at], *starts = sval[at];
+    DSM_LAUNCH(ct_line_table, nl, OL_THREADS, s, keys, starts, val, pred0, llen, lline, ebase, nc, nl, nv, tail, line_level, line_closed);
+    DSM_LAUNCH(chain_first, (size_t)n_levels + 1, OL_THREADS, s, keys, nl, n_levels, 0u, first_line);    // entry n_levels is n_lines
+    if ((rc = ol_scan_exclusive(ebase, nl, nullptr, s1, s2, tail + CH_TOTAL, s, "ol_scan (line lengths)"))) return rc;
+    DSM_LAUNCH(ct_vertices, nc, OL_THREADS, s, dsm, gw, gh, nodata, (const int*)lev, n_levels, w.n_edges, val, pred0, cflag, cedge, clev,
+               (const int*)lline, (const int*)ebase, nc, nl, nv, tail, vertices, vertex_edge);
+    DSM_LAUNCH(ct_offsets, nl, OL_THREADS, s, (const int*)ebase, nl, nv, tail, offset);
+    DSM_LAUNCH(ct_finish, 1, 64, s, (const int*)tail, nl, nv, offset);
+    return SMVS_OK;
 }
 
 }  // extern "C"

@@ -36,7 +36,6 @@ constexpr int HZ_PF = 4;                                 // rows of q a lane loa
 constexpr int HZ_MAX_DIRS = 64;                          // directions of one call: they walk side by side in one launch
 constexpr int HZ_VOID = INT32_MIN;                       // q of an invalid cell
 constexpr int HZ_OFF = INT32_MIN + 1;                    // a row of the walk at which the line is off the grid
-constexpr float HZ_MAX_Z = 32768.0f;
 constexpr double HZ_MIN_ALONG = 4.0, HZ_MAX_SPAN = 0x1p37;
 
 // One direction on its working grid (H rows along the scan, W columns): wa the term per column, wb per row.
@@ -71,8 +70,8 @@ void dsm_horizon_quantise(const float* __restrict__ z, int gw, int gh, float nod
     for (int y = y0; y < HZ_TILE; y += HZ_THREADS / HZ_TILE)
         if (r0 + y < gh && c0 + x < gw) {
             const size_t cell = (size_t)(r0 + y) * gw + (size_t)(c0 + x);
-            const float v = z[cell];
-            const int k = dsm_cell_valid(v, nodata) && fabsf(v) <= HZ_MAX_Z ? (int)__double2ll_rn(__dmul_rn((double)v, 256.0)) : HZ_VOID;
+            int k;
+            if (!dsm_quantum(z[cell], nodata, k)) k = HZ_VOID;
             q[cell] = k;
             tile[y * HZ_PITCH + x] = k;
         }

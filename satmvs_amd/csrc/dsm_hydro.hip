@@ -17,10 +17,8 @@
 // A round in which no tile moved has read final halos only: the grid is at the fixed point, which is unique.
 // Every launch has one counter of the tiles that moved, cleared by the entry before its first launch.
 //
-// The forest.  recv[c] is the cell c drains into, FL_ROOT or FL_INVALID.  up[c] starts as recv[c] (a root as itself) and is
-// squared ceil(log2(cells)) + 1 times IN PLACE: a lane that reads a word another lane has squared already only jumps further
-// along the same path, so after the fixed number of rounds up[c] is the root of every cell that has one, and a cell whose
-// up[c] is not a root is on a cycle or drains into one, whatever the order of the lanes.  The tour: cell c has the elements
+// The forest.  recv[c] is the cell c drains into, D8_ROOT or D8_INVALID, and up[c] the root of every cell that has one; a cell
+// whose up[c] is not a root is on a cycle or drains into one (dsm_flow.h has both and says why).  The tour: cell c has the elements
 // 2 c (down) and 2 c + 1 (up); the successors follow from recv of the cell's and its receiver's neighbours alone; the weight
 // sits on down.  A Wyllie doubling between two copies of (successor, suffix sum) runs ceil(log2(2 cells)) rounds, and
 // acc(c) = S(down) - S(up).  The sums are unsigned 64-bit words (they wrap like the int64 they stand for); no atomics but an
@@ -32,6 +30,7 @@
 #include <stdint.h>
 
 #include "dsm_common.h"
+#include "dsm_flow.h"
 #include "dsm_scan.h"
 #include "smvs_host.h"
 
@@ -39,28 +38,12 @@ namespace smvs {
 
 typedef unsigned long long u64;
 
-constexpr int HY_THREADS = 256;
+constexpr int HY_THREADS = D8_THREADS;
 constexpr int HY_TILE = 32, HY_SPAN = HY_TILE + 2, HY_PITCH = HY_SPAN + 1;         // interior, with halo, LDS row in keys
 constexpr int HY_ROWS = HY_THREADS / HY_TILE, HY_PER_THREAD = HY_TILE / HY_ROWS;  // 8 rows of lanes, 4 cells a lane
 constexpr int HY_MAX_ROUNDS = 4096;
-constexpr float HY_MAX_Z = 32768.0f;
 constexpr u64 HY_INVALID = ~0ull, HY_INF = 0xfffffffeull << 32;
-constexpr long long HY_MAX_CELLS = 1ll << 30;
-constexpr int FL_ROOT = -1, FL_INVALID = -2, FL_END = -1;
-
-// Neighbour k = 0 .. 7 is E, SE, S, SW, W, NW, N, NE, columns east and rows south: dc = 1, 1, 0, -1, -1, -1, 0, 1 and
-// dr = 0, 1, 1, 1, 0, -1, -1, -1, two bits each (+ 1) in one word, so that a direction read from memory indexes no table.
-__host__ __device__ constexpr int hy_dc(int k) { return (int)((0x901au >> (2 * k)) & 3u) - 1; }
-__host__ __device__ constexpr int hy_dr(int k) { return (int)((0x01a9u >> (2 * k)) & 3u) - 1; }
-static_assert(hy_dc(0) == 1 && hy_dc(1) == 1 && hy_dc(2) == 0 && hy_dc(3) == -1 && hy_dc(4) == -1 && hy_dc(5) == -1 && hy_dc(6) == 0 && hy_dc(7) == 1, "dc");
-static_assert(hy_dr(0) == 0 && hy_dr(1) == 1 && hy_dr(2) == 1 && hy_dr(3) == 1 && hy_dr(4) == 0 && hy_dr(5) == -1 && hy_dr(6) == -1 && hy_dr(7) == -1, "dr");
-
-__device__ __forceinline__ bool hy_quantum(float z, float nodata, int& q)
-{
-    if (!(dsm_cell_valid(z, nodata) && fabsf(z) <= HY_MAX_Z)) return false;
-    q = (int)__double2ll_rn(__dmul_rn((double)z, 256.0));
-    return true;
-}
+constexpr int FL_END = -1;
 
 __device__ __forceinline__ u64 hy_key(int w, unsigned d) { return (u64)((unsigned)w + 0x80000000u) << 32 | d; }
 __device__ __forceinline__ int hy_w(u64 key) { return (int)((unsigned)(key >> 32) - 0x80000000u); }
@@ -73,13 +56,13 @@ void hy_begin(const float* __restrict__ dsm, int gw, int gh, float nodata, u64* 
     if (i >= n) return;
     const int r = (int)(i / (unsigned)gw), c = (int)(i % (unsigned)gw);
     int q, qn;
-    if (!hy_quantum(dsm[i], nodata, q)) { keys[i] = HY_INVALID; return; }
+    if (!dsm_quantum(dsm[i], nodata, q)) { keys[i] = HY_INVALID; return; }
     bool outlet = false;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int rr = r + hy_dr(k), cc = c + hy_dc(k);
+        const int rr = r + d8_dr(k), cc = c + d8_dc(k);
         if (rr < 0 || rr >= gh || cc < 0 || cc >= gw) outlet = true;
-        else if (!hy_quantum(dsm[(size_t)rr * gw + cc], nodata, qn)) outlet = true;
+        else if (!dsm_quantum(dsm[(size_t)rr * gw + cc], nodata, qn)) outlet = true;
     }
     keys[i] = outlet ? hy_key(q, 0) : HY_INF;
 }
@@ -104,9 +87,9 @@ void hy_round(const float* __restrict__ dsm, int gw, int gh, float nodata, u64* 
         own[j] = tile[at];
         bool all = own[j] != HY_INVALID;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) all = all && tile[at + hy_dr(k) * HY_PITCH + hy_dc(k)] != HY_INVALID;
+        for (int k = 0; k < 8; ++k) all = all && tile[at + d8_dr(k) * HY_PITCH + d8_dc(k)] != HY_INVALID;
         int q = 0;
-        open[j] = all && r < gh && c < gw && hy_quantum(dsm[(size_t)r * gw + c], nodata, q);
+        open[j] = all && r < gh && c < gw && dsm_quantum(dsm[(size_t)r * gw + c], nodata, q);
         floor_key[j] = hy_key(q, 0);
     }
     bool any = false;
@@ -120,7 +103,7 @@ void hy_round(const float* __restrict__ dsm, int gw, int gh, float nodata, u64* 
             u64 low = HY_INVALID;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const u64 v = tile[at + hy_dr(k) * HY_PITCH + hy_dc(k)];
+                const u64 v = tile[at + d8_dr(k) * HY_PITCH + d8_dc(k)];
                 low = v < low ? v : low;
             }
             low += 1;                                        // one step more: no neighbour of an open cell is all ones, d < 2^30
@@ -156,7 +139,7 @@ void hy_read(const float* __restrict__ dsm, int gw, int gh, float nodata, const 
     const float z = dsm[i];
     const u64 key = keys[i];
     int q;
-    const bool valid = hy_quantum(z, nodata, q) && key != HY_INVALID;
+    const bool valid = dsm_quantum(z, nodata, q) && key != HY_INVALID;
     const int w = hy_w(key);
     if (filled) filled[i] = !valid ? nodata : w == q ? z : (float)((double)w / 256.0);
     if (depth) depth[i] = !valid ? nodata : (float)((double)((long long)w - q) / 256.0);
@@ -181,7 +164,7 @@ void hy_dir(const u64* __restrict__ keys, int gw, int gh, HyDist dist, unsigned 
     int down = 0, level = 0;                                 // code of the steepest lower neighbour, of the nearest level one
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const int rr = r + hy_dr(k), cc = c + hy_dc(k);
+        const int rr = r + d8_dr(k), cc = c + d8_dc(k);
         const u64 v = (rr < 0 || rr >= gh || cc < 0 || cc >= gw) ? HY_INVALID : keys[(size_t)rr * gw + cc];
         if (v == HY_INVALID) { outlet = true; continue; }
         const int wn = hy_w(v);
@@ -196,52 +179,14 @@ void hy_dir(const u64* __restrict__ keys, int gw, int gh, HyDist dist, unsigned 
     dir[i] = outlet ? 0 : down ? down : level;               // no lower or level neighbour (not a fixed point's keys): a root
 }
 
-// ---- receivers and roots -------------------------------------------------------------------------------------------------------
-// The cell a code sends cell (r, c) to; FL_ROOT for code 0 and for a target off the grid or without a code; FL_INVALID for 9 ..
-// 255.  With a pour mask a marked cell that has a code is a root.
-__device__ __forceinline__ int fl_receiver(const unsigned char* __restrict__ dir, const unsigned char* __restrict__ pour,
-                                           int gw, int gh, int r, int c)
-{
-    const size_t i = (size_t)r * gw + c;
-    const unsigned code = dir[i];
-    if (code > 8) return FL_INVALID;
-    if (code == 0 || (pour && pour[i])) return FL_ROOT;
-    const int rr = r + hy_dr(code - 1), cc = c + hy_dc(code - 1);
-    if (rr < 0 || rr >= gh || cc < 0 || cc >= gw) return FL_ROOT;
-    const size_t t = (size_t)rr * gw + cc;
-    return dir[t] > 8 ? FL_ROOT : (int)t;
-}
-
-__global__ __launch_bounds__(HY_THREADS)
-void fl_receivers(const unsigned char* __restrict__ dir, const unsigned char* __restrict__ pour, int gw, int gh,
-                  int* __restrict__ recv, int* __restrict__ up)
-{
-    const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)HY_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const int to = fl_receiver(dir, pour, gw, gh, (int)(i / (unsigned)gw), (int)(i % (unsigned)gw));
-    recv[i] = to;
-    up[i] = to >= 0 ? to : (int)i;
-}
-
-// up <- up o up, in place (the header comment says why that is sound).  Every word is a cell index written by fl_receivers.
-__global__ __launch_bounds__(HY_THREADS)
-void fl_jump(unsigned n, int* up)
-{
-    const unsigned i = blockIdx.x * (unsigned)HY_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const unsigned a = (unsigned)up[i];
-    if (a >= n) return;
-    const unsigned b = (unsigned)up[a];
-    if (b < n && b != a) up[i] = (int)b;
-}
-
+// ---- the forest ----------------------------------------------------------------------------------------------------------------
 // Whether cell i has a code and a root; else what it is.
 enum { FL_TREE = 0, FL_VOID, FL_CYCLIC };
 __device__ __forceinline__ int fl_kind(const int* __restrict__ recv, const int* __restrict__ up, unsigned n, unsigned i, unsigned& root)
 {
-    if (recv[i] == FL_INVALID) return FL_VOID;
+    if (recv[i] == D8_INVALID) return FL_VOID;
     root = (unsigned)up[i];
-    return root < n && recv[root] == FL_ROOT ? FL_TREE : FL_CYCLIC;
+    return root < n && recv[root] == D8_ROOT ? FL_TREE : FL_CYCLIC;
 }
 
 // ---- accumulation --------------------------------------------------------------------------------------------------------------
@@ -252,7 +197,7 @@ __device__ __forceinline__ int fl_child_from(const int* __restrict__ recv, int g
     int found = FL_END;
 #pragma unroll
     for (int k = 7; k >= 0; --k) {
-        const int rr = r + hy_dr(k), cc = c + hy_dc(k);
+        const int rr = r + d8_dr(k), cc = c + d8_dc(k);
         if (k < k0 || rr < 0 || rr >= gh || cc < 0 || cc >= gw) continue;
         const int child = rr * gw + cc;
         if (recv[child] == p) found = 2 * child;
@@ -315,7 +260,7 @@ __global__ __launch_bounds__(HY_THREADS)
 void fl_numbered(unsigned n, const unsigned char* __restrict__ pour, const int* __restrict__ recv, int* __restrict__ number)
 {
     const unsigned i = blockIdx.x * (unsigned)HY_THREADS + threadIdx.x;
-    if (i < n) number[i] = recv[i] == FL_ROOT && (!pour || pour[i]);
+    if (i < n) number[i] = recv[i] == D8_ROOT && (!pour || pour[i]);
 }
 
 __global__ __launch_bounds__(HY_THREADS)
@@ -350,49 +295,17 @@ static FlowWorkspace flow_workspace(size_t n)
     return w;
 }
 
-struct HyBuf { const void* p; size_t bytes; const char* name; };
-
-static const char* hydro_grid_check(int gw, int gh)
+// What the entries check alike: the grid, and that no two of the buffers given (null ones skipped; past the grid check none is
+// empty) share a byte.
+static int hydro_check(int gw, int gh, const DsmBuf* buf, int n_buf)
 {
-    if (gw < 1 || gh < 1) return "non-positive grid size";
-    if ((long long)gw * gh >= HY_MAX_CELLS) return "grid too large: gw * gh must be below 2^30 cells";
-    return nullptr;
-}
-
-// What the entries check alike: the grid, and that no two of the buffers given (null ones skipped) share a byte.
-static int hydro_check(int gw, int gh, const HyBuf* buf, int n_buf)
-{
-    if (const char* msg = hydro_grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s (got %d x %d)", msg, gw, gh);
-    for (int i = 1; i < n_buf; ++i)
-        for (int j = 0; j < i; ++j)
-            if (buf[i].p && buf[j].p && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[i].name, buf[j].name);
+    if (const char* msg = d8_grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s (got %d x %d)", msg, gw, gh);
+    const char* other = nullptr;
+    if (const char* name = dsm_first_alias(buf, n_buf, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     return SMVS_OK;
 }
 
 static size_t flood_workspace(void) { return align256((size_t)HY_MAX_ROUNDS * 4); }
-static unsigned hy_blocks(size_t n) { return (unsigned)((n + HY_THREADS - 1) / HY_THREADS); }
-
-static int ceil_log2(size_t n)
-{
-    int r = 0;
-    while (((size_t)1 << r) < n) ++r;
-    return r;
-}
-
-// recv and up of a direction grid (and a pour mask), then the roots: what accumulate and basins start with.
-static int flow_roots(const unsigned char* dir, const unsigned char* pour, int gw, int gh, int* recv, int* up, hipStream_t s)
-{
-    const size_t n = (size_t)gw * gh;
-    int rc;
-    hipLaunchKernelGGL(fl_receivers, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, dir, pour, gw, gh, recv, up);
-    if ((rc = check_launch("fl_receivers"))) return rc;
-    for (int k = 0, rounds = ceil_log2(n) + 1; k < rounds; ++k) {
-        hipLaunchKernelGGL(fl_jump, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, (unsigned)n, up);
-        if ((rc = check_launch("fl_jump"))) return rc;
-    }
-    return SMVS_OK;
-}
 
 }  // namespace smvs
 
@@ -401,7 +314,7 @@ extern "C" {
 SMVS_EXPORT size_t smvs_dsm_flood_workspace_bytes(int gw, int gh)
 {
     using namespace smvs;
-    return hydro_grid_check(gw, gh) ? 0 : flood_workspace();
+    return d8_grid_check(gw, gh) ? 0 : flood_workspace();
 }
 
 SMVS_EXPORT int smvs_dsm_flood_begin(const float* dsm, int gw, int gh, float nodata, unsigned long long* keys,
@@ -410,12 +323,12 @@ SMVS_EXPORT int smvs_dsm_flood_begin(const float* dsm, int gw, int gh, float nod
     using namespace smvs;
     if (!dsm || !keys || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
-    const HyBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {workspace, flood_workspace(), "workspace"}};
+    const DsmBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {workspace, flood_workspace(), "workspace"}};
     if (int rc = hydro_check(gw, gh, buf, 3)) return rc;
     if (workspace_bytes < flood_workspace()) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, flood_workspace());
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(hy_begin, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, dsm, gw, gh, nodata, keys);
-    return check_launch("hy_begin");
+    DSM_LAUNCH(hy_begin, n, HY_THREADS, s, dsm, gw, gh, nodata, keys);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_flood_rounds(const float* dsm, int gw, int gh, float nodata, unsigned long long* keys, int rounds,
@@ -425,20 +338,16 @@ SMVS_EXPORT int smvs_dsm_flood_rounds(const float* dsm, int gw, int gh, float no
     if (!dsm || !keys || !status || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     if (rounds < 1 || rounds > HY_MAX_ROUNDS) return fail(SMVS_ERR_ARG, "rounds must be in 1 .. %d, got %d", HY_MAX_ROUNDS, rounds);
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
-    const HyBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {status, 4, "status"}, {workspace, flood_workspace(), "workspace"}};
+    const DsmBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {status, 4, "status"}, {workspace, flood_workspace(), "workspace"}};
     if (int rc = hydro_check(gw, gh, buf, 4)) return rc;
     if (workspace_bytes < flood_workspace()) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, flood_workspace());
     hipStream_t s = (hipStream_t)stream;
     int* moved = (int*)workspace;
     if (hipMemsetAsync(moved, 0, (size_t)rounds * 4, s) != hipSuccess) return check_launch("dsm_flood_rounds (clearing the counters)");
-    const dim3 tiles((unsigned)((gw + HY_TILE - 1) / HY_TILE) * (unsigned)((gh + HY_TILE - 1) / HY_TILE));
-    int rc;
-    for (int k = 0; k < rounds; ++k) {
-        hipLaunchKernelGGL(hy_round, tiles, dim3(HY_THREADS), 0, s, dsm, gw, gh, nodata, keys, moved + k);
-        if ((rc = check_launch("hy_round"))) return rc;
-    }
-    hipLaunchKernelGGL(hy_status, dim3(1), dim3(64), 0, s, (const int*)(moved + rounds - 1), status);
-    return check_launch("hy_status");
+    const size_t tiles = (size_t)((gw + HY_TILE - 1) / HY_TILE) * (size_t)((gh + HY_TILE - 1) / HY_TILE);     // a workgroup each
+    for (int k = 0; k < rounds; ++k) DSM_LAUNCH(hy_round, tiles * HY_THREADS, HY_THREADS, s, dsm, gw, gh, nodata, keys, moved + k);
+    DSM_LAUNCH(hy_status, 1, 64, s, (const int*)(moved + rounds - 1), status);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_flood_read(const float* dsm, int gw, int gh, float nodata, const unsigned long long* keys,
@@ -447,10 +356,10 @@ SMVS_EXPORT int smvs_dsm_flood_read(const float* dsm, int gw, int gh, float noda
     using namespace smvs;
     if (!dsm || !keys) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
-    const HyBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {filled, n * 4, "filled"}, {depth, n * 4, "depth"}, {flat_dist, n * 4, "flat_dist"}};
+    const DsmBuf buf[] = {{dsm, n * 4, "dsm"}, {keys, n * 8, "keys"}, {filled, n * 4, "filled"}, {depth, n * 4, "depth"}, {flat_dist, n * 4, "flat_dist"}};
     if (int rc = hydro_check(gw, gh, buf, 5)) return rc;
-    hipLaunchKernelGGL(hy_read, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, (hipStream_t)stream, dsm, gw, gh, nodata, keys, filled, depth, flat_dist);
-    return check_launch("hy_read");
+    DSM_LAUNCH(hy_read, n, HY_THREADS, (hipStream_t)stream, dsm, gw, gh, nodata, keys, filled, depth, flat_dist);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_flow_dir(const unsigned long long* keys, int gw, int gh, const double* dist, unsigned char* dir, void* stream)
@@ -463,16 +372,16 @@ SMVS_EXPORT int smvs_dsm_flow_dir(const unsigned long long* keys, int gw, int gh
         d.d[k] = dist[k];
     }
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
-    const HyBuf buf[] = {{keys, n * 8, "keys"}, {dir, n, "dir"}};
+    const DsmBuf buf[] = {{keys, n * 8, "keys"}, {dir, n, "dir"}};
     if (int rc = hydro_check(gw, gh, buf, 2)) return rc;
-    hipLaunchKernelGGL(hy_dir, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, (hipStream_t)stream, keys, gw, gh, d, dir);
-    return check_launch("hy_dir");
+    DSM_LAUNCH(hy_dir, n, HY_THREADS, (hipStream_t)stream, keys, gw, gh, d, dir);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT size_t smvs_dsm_flow_workspace_bytes(int gw, int gh)
 {
     using namespace smvs;
-    return hydro_grid_check(gw, gh) ? 0 : flow_workspace((size_t)gw * gh).bytes;
+    return d8_grid_check(gw, gh) ? 0 : flow_workspace((size_t)gw * gh).bytes;
 }
 
 SMVS_EXPORT int smvs_dsm_flow_accumulate(const unsigned char* dir, const int* weight, int gw, int gh, long long* acc, int* flag,
@@ -482,7 +391,7 @@ SMVS_EXPORT int smvs_dsm_flow_accumulate(const unsigned char* dir, const int* we
     if (!dir || !acc || !flag || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
     const FlowWorkspace w = flow_workspace(n);
-    const HyBuf buf[] = {{dir, n, "dir"}, {weight, n * 4, "weight"}, {acc, n * 8, "acc"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
+    const DsmBuf buf[] = {{dir, n, "dir"}, {weight, n * 4, "weight"}, {acc, n * 8, "acc"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
     if (int rc = hydro_check(gw, gh, buf, 5)) return rc;
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = (hipStream_t)stream;
@@ -492,16 +401,13 @@ SMVS_EXPORT int smvs_dsm_flow_accumulate(const unsigned char* dir, const int* we
     u64* sum[2] = {(u64*)(base + w.sum), (u64*)(base + w.sum) + 2 * n};
     if (hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return check_launch("dsm_flow_accumulate (clearing the flag)");
     int rc;
-    if ((rc = flow_roots(dir, nullptr, gw, gh, recv, up, s))) return rc;
-    hipLaunchKernelGGL(fl_tour, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, dir, weight, gw, gh, (const int*)recv, (const int*)up, succ[0], sum[0]);
-    if ((rc = check_launch("fl_tour"))) return rc;
+    if ((rc = d8_roots(dir, nullptr, gw, gh, recv, up, s))) return rc;
+    DSM_LAUNCH(fl_tour, n, HY_THREADS, s, dir, weight, gw, gh, (const int*)recv, (const int*)up, succ[0], sum[0]);
     int at = 0;
-    for (int k = 0, rounds = ceil_log2(2 * n); k < rounds; ++k, at ^= 1) {
-        hipLaunchKernelGGL(fl_double, dim3(hy_blocks(2 * n)), dim3(HY_THREADS), 0, s, (unsigned)(2 * n), (const int*)succ[at], (const u64*)sum[at], succ[at ^ 1], sum[at ^ 1]);
-        if ((rc = check_launch("fl_double"))) return rc;
-    }
-    hipLaunchKernelGGL(fl_acc, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, (unsigned)n, (const int*)recv, (const int*)up, (const u64*)sum[at], acc, flag);
-    return check_launch("fl_acc");
+    for (int k = 0, rounds = dsm_ceil_log2(2 * n); k < rounds; ++k, at ^= 1)
+        DSM_LAUNCH(fl_double, 2 * n, HY_THREADS, s, (unsigned)(2 * n), (const int*)succ[at], (const u64*)sum[at], succ[at ^ 1], sum[at ^ 1]);
+    DSM_LAUNCH(fl_acc, n, HY_THREADS, s, (unsigned)n, (const int*)recv, (const int*)up, (const u64*)sum[at], acc, flag);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_flow_basins(const unsigned char* dir, const unsigned char* pour, int gw, int gh, int* basin, int* n_out,
@@ -511,7 +417,7 @@ SMVS_EXPORT int smvs_dsm_flow_basins(const unsigned char* dir, const unsigned ch
     if (!dir || !basin || !n_out || !flag || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
     const FlowWorkspace w = flow_workspace(n);
-    const HyBuf buf[] = {{dir, n, "dir"}, {pour, n, "pour"}, {basin, n * 4, "basin"}, {n_out, 4, "n_out"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
+    const DsmBuf buf[] = {{dir, n, "dir"}, {pour, n, "pour"}, {basin, n * 4, "basin"}, {n_out, 4, "n_out"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
     if (int rc = hydro_check(gw, gh, buf, 6)) return rc;
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = (hipStream_t)stream;
@@ -519,12 +425,11 @@ SMVS_EXPORT int smvs_dsm_flow_basins(const unsigned char* dir, const unsigned ch
     int *recv = (int*)(base + w.recv), *up = (int*)(base + w.up), *number = (int*)(base + w.number);
     if (hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return check_launch("dsm_flow_basins (clearing the flag)");
     int rc;
-    if ((rc = flow_roots(dir, pour, gw, gh, recv, up, s))) return rc;
-    hipLaunchKernelGGL(fl_numbered, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, (unsigned)n, pour, (const int*)recv, number);
-    if ((rc = check_launch("fl_numbered"))) return rc;
+    if ((rc = d8_roots(dir, pour, gw, gh, recv, up, s))) return rc;
+    DSM_LAUNCH(fl_numbered, n, HY_THREADS, s, (unsigned)n, pour, (const int*)recv, number);
     if ((rc = ol_scan_exclusive(number, (unsigned)n, nullptr, (int*)(base + w.s1), (int*)(base + w.s2), n_out, s, "ol_scan (roots)"))) return rc;
-    hipLaunchKernelGGL(fl_basin, dim3(hy_blocks(n)), dim3(HY_THREADS), 0, s, (unsigned)n, pour, (const int*)recv, (const int*)up, (const int*)number, basin, flag);
-    return check_launch("fl_basin");
+    DSM_LAUNCH(fl_basin, n, HY_THREADS, s, (unsigned)n, pour, (const int*)recv, (const int*)up, (const int*)number, basin, flag);
+    return SMVS_OK;
 }
 
 }  // extern "C"

@@ -28,15 +28,11 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "dsm_chain.h"
 #include "dsm_common.h"
-#include "dsm_scan.h"
 #include "smvs_host.h"
 
 namespace smvs {
-
-enum { OL_NE = 0, OL_NR = 1, OL_NV = 2, OL_ERR = 3, OL_TOTAL = 4 };                          // the workspace's tail words
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ int ol_label(const int* __restrict__ L, int gw, int gh, int n, int x, int y)
 {
@@ -52,11 +48,14 @@ __device__ __forceinline__ void ol_cell_of(int x, int y, int s, int& cx, int& cy
     cy = (s == 2 || s == 3) ? y : y - 1;
 }
 
-__device__ __forceinline__ int ol_limit(const int* tail, unsigned cap, int which)
-{
-    const int v = tail[which];
-    return v < 0 ? 0 : (unsigned)v > cap ? (int)cap : v;
-}
+// The number of edges the kernels past the count work on: no more than the caller made room for.
+struct OlLimit {
+    __device__ __forceinline__ int operator()(const int* tail, unsigned cap) const
+    {
+        const int v = tail[CH_N];
+        return v < 0 ? 0 : (unsigned)v > cap ? (int)cap : v;
+    }
+};
 
 // ---- count -------------------------------------------------------------------------------------------------------------------
 // One lane per corner: the mask of the edges that leave it and their number.
@@ -77,15 +76,15 @@ void ol_corners(const int* __restrict__ L, int gw, int gh, int n, unsigned nc, u
 __global__ __launch_bounds__(OL_THREADS)
 void ol_edges(const int* __restrict__ L, int gw, int gh, int n, unsigned nc, const unsigned char* __restrict__ cmask,
               const int* __restrict__ cbase, unsigned cap, int* tail, int* __restrict__ ecorner, u64* __restrict__ val,
-              int* __restrict__ pred, unsigned char* __restrict__ eside)
+              unsigned* __restrict__ pred, unsigned char* __restrict__ eside)
 {
     const unsigned t = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
     if (t >= nc) return;
-    if (tail[OL_NE] < 0 || (unsigned)tail[OL_NE] > cap) {    // more edges than the caller made room for
-        if (t == 0) atomicOr(tail + OL_ERR, 1);
+    if (tail[CH_N] < 0 || (unsigned)tail[CH_N] > cap) {    // more edges than the caller made room for
+        if (t == 0) atomicOr(tail + CH_ERR, 1);
         return;
     }
-    const unsigned ne = (unsigned)tail[OL_NE];
+    const unsigned ne = (unsigned)tail[CH_N];
     const int m = cmask[t];
     if (!m) return;
     const int x = (int)(t % (unsigned)(gw + 1)), y = (int)(t / (unsigned)(gw + 1));
@@ -105,32 +104,15 @@ void ol_edges(const int* __restrict__ L, int gw, int gh, int n, unsigned nc, con
         const int hm = cmask[h];
         const unsigned j2 = (unsigned)cbase[h] + (unsigned)__popc(hm & ((1 << s2) - 1));
         if (j >= ne || j2 >= ne || !((hm >> s2) & 1)) {
-            atomicOr(tail + OL_ERR, 1);
+            atomicOr(tail + CH_ERR, 1);
         } else {
             ecorner[j] = (int)t;
             val[j] = (u64)(2u * t + (s == 0 ? 1u : 0u)) << 32;
-            pred[j2] = (int)j;
+            pred[j2] = j;
             eside[j2] = (unsigned char)(s2 | (s2 != s ? 4 : 0));
         }
         ++j;
     }
-}
-
-// One round of the doubling: the window of an edge grows by the window of the edge `add` places back.
-__global__ __launch_bounds__(OL_THREADS)
-void ol_double(const int* __restrict__ pin, const u64* __restrict__ vin, int* __restrict__ pout, u64* __restrict__ vout,
-               unsigned add, unsigned cap, int* tail)
-{
-    const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    const unsigned ne = (unsigned)ol_limit(tail, cap, OL_NE);
-    if (j >= ne) return;
-    unsigned p = (unsigned)pin[j];
-    if (p >= ne) { atomicOr(tail + OL_ERR, 1); p = j; }
-    unsigned q = (unsigned)pin[p];
-    if (q >= ne) { atomicOr(tail + OL_ERR, 1); q = j; }
-    const u64 a = vin[j], b = vin[p] + add;
-    vout[j] = a < b ? a : b;
-    pout[j] = (int)q;
 }
 
 // Start edges flagged for the scan that numbers the rings; the vertices counted.
@@ -138,19 +120,14 @@ __global__ __launch_bounds__(OL_THREADS)
 void ol_starts(const u64* __restrict__ val, const unsigned char* __restrict__ eside, int* __restrict__ rscan, unsigned cap, int* tail)
 {
     const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    const unsigned ne = (unsigned)ol_limit(tail, cap, OL_NE);
+    const unsigned ne = (unsigned)OlLimit()(tail, cap);
     bool turn = false;
     if (j < ne) {
         rscan[j] = (unsigned)val[j] == 0u;
         turn = (eside[j] & 4) != 0;
     }
     const int cnt = __popcll(__ballot(turn));
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(tail + OL_NV, cnt);
-}
-
-__global__ void ol_counts_out(const int* __restrict__ tail, int* __restrict__ counts)
-{
-    if (threadIdx.x < 3) counts[threadIdx.x] = tail[OL_ERR] ? -1 : tail[threadIdx.x];
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(tail + CH_VERTICES, cnt);
 }
 
 // ---- write -------------------------------------------------------------------------------------------------------------------
@@ -164,42 +141,20 @@ void ol_ring_init(const int* __restrict__ L, int gw, int gh, int n, const u64* _
                   unsigned nc, int* tail, int* __restrict__ skey, int* __restrict__ sval)
 {
     const unsigned j = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (j == 0 && ((unsigned)tail[OL_NE] != ne || (unsigned)tail[OL_NR] != nr || (unsigned)tail[OL_NV] != nv)) atomicOr(tail + OL_ERR, 1);
+    if (j == 0 && ((unsigned)tail[CH_N] != ne || (unsigned)tail[CH_LINES] != nr || (unsigned)tail[CH_VERTICES] != nv)) atomicOr(tail + CH_ERR, 1);
     if (j >= ne || (unsigned)val[j] != 0u) return;
     const unsigned q = (unsigned)rscan[j], t = (unsigned)ecorner[j];
-    if (q >= nr || t >= nc) { atomicOr(tail + OL_ERR, 1); return; }
+    if (q >= nr || t >= nc) { atomicOr(tail + CH_ERR, 1); return; }
     int ax, ay;
     ol_cell_of((int)(t % (unsigned)(gw + 1)), (int)(t / (unsigned)(gw + 1)), eside[j] & 3, ax, ay);
     skey[q] = ol_label(L, gw, gh, n, ax, ay);
     sval[q] = (int)j;
 }
 
-__global__ __launch_bounds__(OL_THREADS)
-void ol_sort_flag(const int* __restrict__ skey, int* __restrict__ spos, unsigned nr, int bit)
-{
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (i < nr) spos[i] = !(((unsigned)skey[i] >> bit) & 1u);
-}
-
-// The stable split on one bit: the keys without the bit keep their order in front, the others theirs behind.
-__global__ __launch_bounds__(OL_THREADS)
-void ol_sort_scatter(const int* __restrict__ kin, const int* __restrict__ vin, const int* __restrict__ spos, int* tail,
-                     int* __restrict__ kout, int* __restrict__ vout, unsigned nr, int bit)
-{
-    const unsigned i = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (i >= nr) return;
-    const int k = kin[i];
-    const unsigned before = (unsigned)spos[i], zeros = (unsigned)tail[OL_TOTAL];
-    unsigned d = (((unsigned)k >> bit) & 1u) ? zeros + (i - before) : before;
-    if (d >= nr) { atomicOr(tail + OL_ERR, 1); d = i; }
-    kout[d] = k;
-    vout[d] = vin[i];
-}
-
 // One lane per ring in its final place: its label, its length (the rank of the start edge's predecessor + 1), zeroed sums,
 // and its place written where the edges find it: at its start edge.
 __global__ __launch_bounds__(OL_THREADS)
-void ol_ring_table(const int* __restrict__ skey, const int* __restrict__ sval, const u64* __restrict__ val, const int* __restrict__ pred,
+void ol_ring_table(const int* __restrict__ skey, const int* __restrict__ sval, const u64* __restrict__ val, const unsigned* __restrict__ pred,
                    int* __restrict__ rscan, int* __restrict__ ebase, unsigned ne, unsigned nr, int* tail, OlRings o)
 {
     const unsigned r = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
@@ -210,30 +165,15 @@ void ol_ring_table(const int* __restrict__ skey, const int* __restrict__ sval, c
     o.edges[2 * r + 1] = 0;
     const unsigned j0 = (unsigned)sval[r];
     unsigned len = 1;
-    if (j0 >= ne) atomicOr(tail + OL_ERR, 1);
+    if (j0 >= ne) atomicOr(tail + CH_ERR, 1);
     else {
         rscan[j0] = (int)r;
-        const unsigned p = (unsigned)pred[j0];
-        if (p >= ne) atomicOr(tail + OL_ERR, 1);
+        const unsigned p = pred[j0];
+        if (p >= ne) atomicOr(tail + CH_ERR, 1);
         else len = (unsigned)val[p] + 1u;
-        if (len > ne) { atomicOr(tail + OL_ERR, 1); len = 1; }
+        if (len > ne) { atomicOr(tail + CH_ERR, 1); len = 1; }
     }
     ebase[r] = (int)len;
-}
-
-// first_ring[k], k = 0 .. n: the first ring of label k + 1 = the first whose label is above k; entry n is n_rings.
-__global__ __launch_bounds__(OL_THREADS)
-void ol_first_ring(const int* __restrict__ skey, unsigned nr, int n, int* __restrict__ first_ring)
-{
-    const unsigned k = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (k > (unsigned)n) return;
-    unsigned lo = 0, hi = nr;
-    for (int step = 0; step < 32 && lo < hi; ++step) {
-        const unsigned mid = lo + (hi - lo) / 2;
-        if ((unsigned)skey[mid] <= k) lo = mid + 1;
-        else hi = mid;
-    }
-    first_ring[k] = (int)lo;
 }
 
 // Every edge to its place in (ring, rank) order, and its share of the ring's sums.  The lanes of a wave that belong to one
@@ -253,13 +193,13 @@ void ol_place(int gw, const u64* __restrict__ val, const int* __restrict__ ecorn
         const u64 v = val[j];
         const unsigned key = (unsigned)(v >> 32), rank = (unsigned)v, t0 = key >> 1;
         live = false;
-        if (t0 >= nc) atomicOr(tail + OL_ERR, 1);
+        if (t0 >= nc) atomicOr(tail + CH_ERR, 1);
         else {
             const unsigned j0 = (unsigned)cbase[t0] + (unsigned)__popc(cmask[t0] & ((key & 1u) ? 0 : 7));
             r = j0 < ne ? (unsigned)rscan[j0] : nr;
             const unsigned g = r < nr ? (unsigned)ebase[r] + rank : ne;
             const unsigned t = (unsigned)ecorner[j];
-            if (r >= nr || g >= ne || g < rank || t >= nc) atomicOr(tail + OL_ERR, 1);
+            if (r >= nr || g >= ne || g < rank || t >= nc) atomicOr(tail + CH_ERR, 1);
             else {
                 const int e = eside[j], s = e & 3;
                 const int x = (int)(t % (unsigned)(gw + 1)), y = (int)(t / (unsigned)(gw + 1));
@@ -302,7 +242,7 @@ void ol_vertices(int gw, const int* __restrict__ ocorner, const int* __restrict_
     const int t = ocorner[g];
     if (t < 0) return;
     const unsigned v = (unsigned)vpos[g];
-    if (v >= nv || (unsigned)t >= nc) { atomicOr(tail + OL_ERR, 1); return; }
+    if (v >= nv || (unsigned)t >= nc) { atomicOr(tail + CH_ERR, 1); return; }
     vertices[2 * v] = (int)((unsigned)t % (unsigned)(gw + 1));
     vertices[2 * v + 1] = (int)((unsigned)t / (unsigned)(gw + 1));
 }
@@ -311,16 +251,16 @@ __global__ __launch_bounds__(OL_THREADS)
 void ol_offsets(const int* __restrict__ ebase, const int* __restrict__ vpos, unsigned ne, unsigned nr, unsigned nv, int* tail, int* __restrict__ offset)
 {
     const unsigned r = blockIdx.x * (unsigned)OL_THREADS + threadIdx.x;
-    if (r == 0 && (unsigned)tail[OL_TOTAL] != nv) atomicOr(tail + OL_ERR, 1);
+    if (r == 0 && (unsigned)tail[CH_TOTAL] != nv) atomicOr(tail + CH_ERR, 1);
     if (r >= nr) return;
     const unsigned g = (unsigned)ebase[r];
-    if (g >= ne) { atomicOr(tail + OL_ERR, 1); offset[r] = 0; return; }
+    if (g >= ne) { atomicOr(tail + CH_ERR, 1); offset[r] = 0; return; }
     offset[r] = vpos[g];
 }
 
 __global__ void ol_finish(const int* __restrict__ tail, unsigned nr, unsigned nv, int* __restrict__ offset)
 {
-    if (threadIdx.x == 0) offset[nr] = tail[OL_ERR] ? -1 : (int)nv;
+    if (threadIdx.x == 0) offset[nr] = tail[CH_ERR] ? -1 : (int)nv;
 }
 
 // ---- burn --------------------------------------------------------------------------------------------------------------------
@@ -452,26 +392,6 @@ static const char* outline_check(int gw, int gh, int n, long long max_edges)
     return nullptr;
 }
 
-static int outline_rounds(unsigned max_edges)
-{
-    int rounds = 0;
-    while (rounds < 31 && (1u << rounds) < max_edges) ++rounds;
-    return rounds;
-}
-
-struct OlBuf { const void* p; size_t bytes; const char* name; };
-
-static const char* first_overlap(const OlBuf* buf, int nbuf, const char*& other)
-{
-    for (int i = 1; i < nbuf; ++i)
-        for (int j = 0; j < i; ++j)
-            if (buf[i].bytes && buf[j].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes)) {
-                other = buf[j].name;
-                return buf[i].name;
-            }
-    return nullptr;
-}
-
 static int burn_entry(bool lattice, const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,
                       int gw, int gh, int* out, int* flag, void* stream)
 {
@@ -481,10 +401,10 @@ static int burn_entry(bool lattice, const int* vertices, const int* offset, cons
     const bool some = n_rings > 0 && n_vertices > 0;
     if (some && (!vertices || !offset || !ring_label)) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t ncells = (size_t)gw * gh;
-    const OlBuf buf[] = {{out, ncells * 4, "out"}, {flag, 4, "flag"}, {vertices, some ? (size_t)n_vertices * 8 : 0, "vertices"},
+    const DsmBuf buf[] = {{out, ncells * 4, "out"}, {flag, 4, "flag"}, {vertices, some ? (size_t)n_vertices * 8 : 0, "vertices"},
                          {offset, some ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {ring_label, some ? (size_t)n_rings * 4 : 0, "ring_label"}};
     const char* other = nullptr;
-    if (const char* name = first_overlap(buf, 2, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    if (const char* name = dsm_first_alias(buf, 2, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     for (int i = 2; i < 5; ++i)
         for (int j = 0; j < 2; ++j)
             if (buf[i].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
@@ -493,13 +413,12 @@ static int burn_entry(bool lattice, const int* vertices, const int* offset, cons
     if (hipMemsetAsync(out, 0, ncells * 4, s) != hipSuccess || hipMemsetAsync(flag, 0, 4, s) != hipSuccess)
         return check_launch("dsm_burn (clearing the grid)");
     if (!some) return SMVS_OK;
-    int rc;
     const unsigned lanes = (unsigned)(n_vertices > n_rings ? n_vertices : n_rings);     // a lane per vertex, and one per entry of the offset table
-    hipLaunchKernelGGL(lattice ? ol_burn_edges : ol_burn_polygon_edges, dim3((lanes + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s,
-                       vertices, offset, ring_label, (unsigned)n_rings, (unsigned)n_vertices, gw, gh, out, flag);
-    if ((rc = check_launch(lattice ? "ol_burn_edges" : "ol_burn_polygon_edges"))) return rc;
-    hipLaunchKernelGGL(ol_burn_rows, dim3(((unsigned)gh + OL_THREADS / 64 - 1) / (OL_THREADS / 64)), dim3(OL_THREADS), 0, s, out, gw, gh);
-    return check_launch("ol_burn_rows");
+    const unsigned nr = (unsigned)n_rings, nv = (unsigned)n_vertices;
+    if (lattice) DSM_LAUNCH(ol_burn_edges, lanes, OL_THREADS, s, vertices, offset, ring_label, nr, nv, gw, gh, out, flag);
+    else DSM_LAUNCH(ol_burn_polygon_edges, lanes, OL_THREADS, s, vertices, offset, ring_label, nr, nv, gw, gh, out, flag);
+    DSM_LAUNCH(ol_burn_rows, (size_t)gh * 64, OL_THREADS, s, out, gw, gh);            // a wave per row
+    return SMVS_OK;
 }
 
 }  // namespace smvs
@@ -521,9 +440,9 @@ SMVS_EXPORT int smvs_dsm_outline_count(const int* labels, int gw, int gh, int n,
     if (const char* msg = outline_check(gw, gh, n, max_edges)) return fail(SMVS_ERR_ARG, "%s", msg);
     const OutlineWorkspace w = outline_workspace(gw, gh, (size_t)max_edges);
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-    const OlBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {counts, 12, "counts"}, {workspace, w.bytes, "workspace"}};
+    const DsmBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {counts, 12, "counts"}, {workspace, w.bytes, "workspace"}};
     const char* other = nullptr;
-    if (const char* name = first_overlap(buf, 3, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    if (const char* name = dsm_first_alias(buf, 3, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)workspace;
     int* tail = (int*)(base + w.tail);
@@ -534,32 +453,24 @@ SMVS_EXPORT int smvs_dsm_outline_count(const int* labels, int gw, int gh, int n,
     }
     int *s1 = (int*)(base + w.s1), *s2 = (int*)(base + w.s2), *cbase = (int*)(base + w.cbase);
     unsigned char* cmask = (unsigned char*)(base + w.cmask);
-    const unsigned corner_blocks = (w.nc + OL_THREADS - 1) / OL_THREADS;
     int rc;
-    hipLaunchKernelGGL(ol_corners, dim3(corner_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, w.nc, cmask, cbase);
-    if ((rc = check_launch("ol_corners"))) return rc;
-    if ((rc = ol_scan_exclusive(cbase, w.nc, nullptr, s1, s2, tail + OL_NE, s, "ol_scan (edges)"))) return rc;
+    DSM_LAUNCH(ol_corners, w.nc, OL_THREADS, s, labels, gw, gh, n, w.nc, cmask, cbase);
+    if ((rc = ol_scan_exclusive(cbase, w.nc, nullptr, s1, s2, tail + CH_N, s, "ol_scan (edges)"))) return rc;
     if (max_edges > 0) {
-        const unsigned cap = (unsigned)max_edges, edge_blocks = (cap + OL_THREADS - 1) / OL_THREADS;
-        int *pred[3] = {(int*)(base + w.pred0), (int*)(base + w.preda), (int*)(base + w.predb)};
+        const unsigned cap = (unsigned)max_edges;
+        unsigned* pred[3] = {(unsigned*)(base + w.pred0), (unsigned*)(base + w.preda), (unsigned*)(base + w.predb)};
         u64* val[2] = {(u64*)(base + w.vala), (u64*)(base + w.valb)};
         int *ecorner = (int*)(base + w.ecorner), *rscan = (int*)(base + w.rscan);
         unsigned char* eside = (unsigned char*)(base + w.eside);
-        hipLaunchKernelGGL(ol_edges, dim3(corner_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, w.nc, (const unsigned char*)cmask,
-                           (const int*)cbase, cap, tail, ecorner, val[0], pred[0], eside);
-        if ((rc = check_launch("ol_edges"))) return rc;
-        const int rounds = outline_rounds(cap);
-        for (int r = 0; r < rounds; ++r) {                   // (pred0, vala) -> (preda, valb) -> (predb, vala) -> (preda, valb) ...
-            hipLaunchKernelGGL(ol_double, dim3(edge_blocks), dim3(OL_THREADS), 0, s, (const int*)pred[r == 0 ? 0 : 1 + (r + 1) % 2],
-                               (const u64*)val[r % 2], pred[1 + r % 2], val[(r + 1) % 2], 1u << r, cap, tail);
-            if ((rc = check_launch("ol_double"))) return rc;
-        }
-        hipLaunchKernelGGL(ol_starts, dim3(edge_blocks), dim3(OL_THREADS), 0, s, (const u64*)val[rounds % 2], (const unsigned char*)eside, rscan, cap, tail);
-        if ((rc = check_launch("ol_starts"))) return rc;
-        if ((rc = ol_scan_exclusive(rscan, cap, tail + OL_NE, s1, s2, tail + OL_NR, s, "ol_scan (rings)"))) return rc;
+        DSM_LAUNCH(ol_edges, w.nc, OL_THREADS, s, labels, gw, gh, n, w.nc, (const unsigned char*)cmask, (const int*)cbase, cap, tail,
+                   ecorner, val[0], pred[0], eside);
+        int at;
+        if ((rc = chain_order<false, OlLimit>(pred, val, cap, tail, s, &at))) return rc;
+        DSM_LAUNCH(ol_starts, cap, OL_THREADS, s, (const u64*)val[at], (const unsigned char*)eside, rscan, cap, tail);
+        if ((rc = ol_scan_exclusive(rscan, cap, tail + CH_N, s1, s2, tail + CH_LINES, s, "ol_scan (rings)"))) return rc;
     }
-    hipLaunchKernelGGL(ol_counts_out, dim3(1), dim3(64), 0, s, (const int*)tail, counts);
-    return check_launch("ol_counts_out");
+    DSM_LAUNCH(chain_counts_out, 1, 64, s, (const int*)tail, counts);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n, int n_edges, int n_rings, int n_vertices,
@@ -576,11 +487,11 @@ SMVS_EXPORT int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n,
     const OutlineWorkspace w = outline_workspace(gw, gh, (size_t)n_edges);
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     const size_t m = (size_t)n_rings;
-    const OlBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {workspace, w.bytes, "workspace"}, {ring_label, m * 4, "ring_label"},
+    const DsmBuf buf[] = {{labels, (size_t)gw * gh * 4, "labels"}, {workspace, w.bytes, "workspace"}, {ring_label, m * 4, "ring_label"},
                          {area2, m * 8, "area2"}, {edges, m * 8, "edges"}, {offset, (m + 1) * 4, "offset"},
                          {first_ring, ((size_t)n + 1) * 4, "first_ring"}, {vertices, (size_t)n_vertices * 8, "vertices"}};
     const char* other = nullptr;
-    if (const char* name = first_overlap(buf, 8, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
+    if (const char* name = dsm_first_alias(buf, 8, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     hipStream_t s = (hipStream_t)stream;
     if (n_edges == 0) {                                      // no ring: the two tables that still have entries
         if (hipMemsetAsync(first_ring, 0, ((size_t)n + 1) * 4, s) != hipSuccess || hipMemsetAsync(offset, 0, 4, s) != hipSuccess)
@@ -590,45 +501,30 @@ SMVS_EXPORT int smvs_dsm_outline_write(const int* labels, int gw, int gh, int n,
     char* base = (char*)workspace;
     int *tail = (int*)(base + w.tail), *s1 = (int*)(base + w.s1), *s2 = (int*)(base + w.s2), *cbase = (int*)(base + w.cbase);
     const unsigned char *cmask = (const unsigned char*)(base + w.cmask), *eside = (const unsigned char*)(base + w.eside);
-    const int rounds = outline_rounds((unsigned)n_edges);
-    const u64* val = (const u64*)(base + (rounds % 2 ? w.valb : w.vala));
-    const int *pred0 = (const int*)(base + w.pred0), *ecorner = (const int*)(base + w.ecorner);
+    const u64* val = (const u64*)(base + (chain_rounds((unsigned)n_edges) % 2 ? w.valb : w.vala));
+    const unsigned* pred0 = (const unsigned*)(base + w.pred0);
+    const int* ecorner = (const int*)(base + w.ecorner);
     int *rscan = (int*)(base + w.rscan), *skey[2] = {(int*)(base + w.skeya), (int*)(base + w.skeyb)};
     int *sval[2] = {(int*)(base + w.svala), (int*)(base + w.svalb)}, *spos = (int*)(base + w.spos);
     int *ebase = (int*)(base + w.ebase), *ocorner = (int*)(base + w.ocorner), *vpos = (int*)(base + w.vpos);
     const unsigned ne = (unsigned)n_edges, nr = (unsigned)n_rings, nv = (unsigned)n_vertices;
-    const unsigned edge_blocks = (ne + OL_THREADS - 1) / OL_THREADS, ring_blocks = (nr + OL_THREADS - 1) / OL_THREADS;
     const OlRings o = {ring_label, edges, area2};
     int rc;
-    hipLaunchKernelGGL(ol_ring_init, dim3(edge_blocks), dim3(OL_THREADS), 0, s, labels, gw, gh, n, val, (const int*)rscan, ecorner, eside,
-                       ne, nr, nv, w.nc, tail, skey[0], sval[0]);
-    if ((rc = check_launch("ol_ring_init"))) return rc;
-    int bits = 0;
+    DSM_LAUNCH(ol_ring_init, ne, OL_THREADS, s, labels, gw, gh, n, val, (const int*)rscan, ecorner, eside, ne, nr, nv, w.nc, tail, skey[0], sval[0]);
+    int bits = 0, at;
     while (bits < 31 && ((unsigned)n >> bits)) ++bits;
-    for (int b = 0; b < bits; ++b) {
-        hipLaunchKernelGGL(ol_sort_flag, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], spos, nr, b);
-        if ((rc = check_launch("ol_sort_flag"))) return rc;
-        if ((rc = ol_scan_exclusive(spos, nr, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (sort)"))) return rc;
-        hipLaunchKernelGGL(ol_sort_scatter, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)skey[b % 2], (const int*)sval[b % 2],
-                           (const int*)spos, tail, skey[(b + 1) % 2], sval[(b + 1) % 2], nr, b);
-        if ((rc = check_launch("ol_sort_scatter"))) return rc;
-    }
-    const int *keys = skey[bits % 2], *starts = sval[bits % 2];
-    hipLaunchKernelGGL(ol_ring_table, dim3(ring_blocks), dim3(OL_THREADS), 0, s, keys, starts, val, pred0, rscan, ebase, ne, nr, tail, o);
-    if ((rc = check_launch("ol_ring_table"))) return rc;
-    hipLaunchKernelGGL(ol_first_ring, dim3(((unsigned)n + 1u + OL_THREADS - 1) / OL_THREADS), dim3(OL_THREADS), 0, s, keys, nr, n, first_ring);
-    if ((rc = check_launch("ol_first_ring"))) return rc;
-    if ((rc = ol_scan_exclusive(ebase, nr, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (ring lengths)"))) return rc;
-    hipLaunchKernelGGL(ol_place, dim3(edge_blocks), dim3(OL_THREADS), 0, s, gw, val, ecorner, eside, cmask, (const int*)cbase, (const int*)rscan,
-                       (const int*)ebase, ne, nr, w.nc, tail, ocorner, vpos, o);
-    if ((rc = check_launch("ol_place"))) return rc;
-    if ((rc = ol_scan_exclusive(vpos, ne, nullptr, s1, s2, tail + OL_TOTAL, s, "ol_scan (vertices)"))) return rc;
-    hipLaunchKernelGGL(ol_vertices, dim3(edge_blocks), dim3(OL_THREADS), 0, s, gw, (const int*)ocorner, (const int*)vpos, ne, nv, w.nc, tail, vertices);
-    if ((rc = check_launch("ol_vertices"))) return rc;
-    hipLaunchKernelGGL(ol_offsets, dim3(ring_blocks), dim3(OL_THREADS), 0, s, (const int*)ebase, (const int*)vpos, ne, nr, nv, tail, offset);
-    if ((rc = check_launch("ol_offsets"))) return rc;
-    hipLaunchKernelGGL(ol_finish, dim3(1), dim3(64), 0, s, (const int*)tail, nr, nv, offset);
-    return check_launch("ol_finish");
+    if ((rc = chain_sort(skey, sval, spos, nr, bits, s1, s2, tail, s, &at))) return rc;
+    const int *keys = skey[at], *starts = sval[at];
+    DSM_LAUNCH(ol_ring_table, nr, OL_THREADS, s, keys, starts, val, pred0, rscan, ebase, ne, nr, tail, o);
+    DSM_LAUNCH(chain_first, (size_t)n + 1, OL_THREADS, s, keys, nr, n, 1u, first_ring);       // the first ring of label k + 1; entry n is n_rings
+    if ((rc = ol_scan_exclusive(ebase, nr, nullptr, s1, s2, tail + CH_TOTAL, s, "ol_scan (ring lengths)"))) return rc;
+    DSM_LAUNCH(ol_place, ne, OL_THREADS, s, gw, val, ecorner, eside, cmask, (const int*)cbase, (const int*)rscan, (const int*)ebase, ne, nr, w.nc,
+               tail, ocorner, vpos, o);
+    if ((rc = ol_scan_exclusive(vpos, ne, nullptr, s1, s2, tail + CH_TOTAL, s, "ol_scan (vertices)"))) return rc;
+    DSM_LAUNCH(ol_vertices, ne, OL_THREADS, s, gw, (const int*)ocorner, (const int*)vpos, ne, nv, w.nc, tail, vertices);
+    DSM_LAUNCH(ol_offsets, nr, OL_THREADS, s, (const int*)ebase, (const int*)vpos, ne, nr, nv, tail, offset);
+    DSM_LAUNCH(ol_finish, 1, 64, s, (const int*)tail, nr, nv, offset);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_burn(const int* vertices, const int* offset, const int* ring_label, int n_rings, int n_vertices,

@@ -412,30 +412,24 @@ static SpState simplify_state(void* workspace, const SimplifyWorkspace& w)
     return st;
 }
 
-struct SpBuf { const void* p; size_t bytes; const char* name; };
-
 // What the four entries check alike: the counts, the ring table, the workspace, and that no two buffers share a byte.
 static int simplify_check(const int* vertices, const int* offset, int n_rings, int n_vertices, const void* workspace, size_t workspace_bytes,
-                          const SpBuf* extra, int n_extra)
+                          const DsmBuf* extra, int n_extra)
 {
     if (n_rings < 0 || n_vertices < 0) return fail(SMVS_ERR_ARG, "n_rings and n_vertices must be in 0 .. 2^31 - 1, got %d and %d", n_rings, n_vertices);
     if (n_vertices > 0 && n_rings == 0) return fail(SMVS_ERR_ARG, "vertices without rings (n_rings == 0)");
     if (!workspace || (n_rings > 0 && !offset) || (n_vertices > 0 && !vertices)) return fail(SMVS_ERR_ARG, "null pointer argument");
     const SimplifyWorkspace w = simplify_workspace((size_t)n_rings, (size_t)n_vertices);
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-    SpBuf buf[9] = {{vertices, (size_t)n_vertices * 8, "vertices"}, {offset, n_rings ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {workspace, w.bytes, "workspace"}};
+    DsmBuf buf[9] = {{vertices, (size_t)n_vertices * 8, "vertices"}, {offset, n_rings ? ((size_t)n_rings + 1) * 4 : 0, "offset"}, {workspace, w.bytes, "workspace"}};
     for (int k = 0; k < n_extra; ++k) {
         if (extra[k].bytes && !extra[k].p) return fail(SMVS_ERR_ARG, "null pointer argument");
         buf[3 + k] = extra[k];
     }
-    for (int i = 1; i < 3 + n_extra; ++i)
-        for (int j = 0; j < i; ++j)
-            if (buf[i].bytes && buf[j].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[i].name, buf[j].name);
+    const char* other = nullptr;
+    if (const char* name = dsm_first_alias(buf, 3 + n_extra, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     return SMVS_OK;
 }
-
-static unsigned sp_blocks(unsigned n) { return (n + SP_THREADS - 1) / SP_THREADS; }
 
 }  // namespace smvs
 
@@ -452,7 +446,7 @@ SMVS_EXPORT int smvs_dsm_simplify_begin(const int* vertices, const int* offset, 
                                         void* workspace, size_t workspace_bytes, void* stream)
 {
     using namespace smvs;
-    const SpBuf extra[] = {{flag, 4, "flag"}};
+    const DsmBuf extra[] = {{flag, 4, "flag"}};
     if (!flag) return fail(SMVS_ERR_ARG, "null pointer argument");
     if (int rc = simplify_check(vertices, offset, n_rings, n_vertices, workspace, workspace_bytes, extra, 1)) return rc;
     const SimplifyWorkspace w = simplify_workspace((size_t)n_rings, (size_t)n_vertices);
@@ -468,20 +462,18 @@ SMVS_EXPORT int smvs_dsm_simplify_begin(const int* vertices, const int* offset, 
     }
     if (!ok) return check_launch("dsm_simplify_begin (clearing the workspace)");
     if (!nr) return SMVS_OK;
-    int rc;
     const unsigned lanes = (unsigned)(nv > nr ? nv : nr);
-    hipLaunchKernelGGL(sp_init, dim3(sp_blocks(lanes)), dim3(SP_THREADS), 0, s, vertices, offset, (unsigned)nr, (unsigned)nv, st, flag);
-    if ((rc = check_launch("sp_init"))) return rc;
+    DSM_LAUNCH(sp_init, lanes, SP_THREADS, s, vertices, offset, (unsigned)nr, (unsigned)nv, st, flag);
     if (!nv) return SMVS_OK;
-    hipLaunchKernelGGL(sp_segments, dim3(sp_blocks((unsigned)nv)), dim3(SP_THREADS), 0, s, offset, (unsigned)nr, (unsigned)nv, st);
-    return check_launch("sp_segments");
+    DSM_LAUNCH(sp_segments, nv, SP_THREADS, s, offset, (unsigned)nr, (unsigned)nv, st);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_simplify_rounds(const int* vertices, const int* offset, int n_rings, int n_vertices, int tol16, int rounds,
                                          int* status, void* workspace, size_t workspace_bytes, void* stream)
 {
     using namespace smvs;
-    const SpBuf extra[] = {{status, 8, "status"}};
+    const DsmBuf extra[] = {{status, 8, "status"}};
     if (!status) return fail(SMVS_ERR_ARG, "null pointer argument");
     if (tol16 < 0 || tol16 > SP_MAX_TOL16) return fail(SMVS_ERR_ARG, "tol16 must be in 0 .. %d, got %d", SP_MAX_TOL16, tol16);
     if (rounds < 0 || rounds > SP_MAX_ROUNDS) return fail(SMVS_ERR_ARG, "rounds must be in 0 .. %d, got %d", SP_MAX_ROUNDS, rounds);
@@ -490,24 +482,20 @@ SMVS_EXPORT int smvs_dsm_simplify_rounds(const int* vertices, const int* offset,
     const SpState st = simplify_state(workspace, w);
     hipStream_t s = (hipStream_t)stream;
     const unsigned nr = (unsigned)n_rings, nv = (unsigned)n_vertices;
-    int rc;
     for (int k = 0; k < rounds && nv; ++k) {
-        hipLaunchKernelGGL(sp_keys, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, vertices, offset, nr, nv, st);
-        if ((rc = check_launch("sp_keys"))) return rc;
-        hipLaunchKernelGGL(sp_pick, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, offset, nr, nv, st);
-        if ((rc = check_launch("sp_pick"))) return rc;
-        hipLaunchKernelGGL(sp_decide, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, vertices, offset, nr, nv, (unsigned)tol16, st);
-        if ((rc = check_launch("sp_decide"))) return rc;
+        DSM_LAUNCH(sp_keys, nv, SP_THREADS, s, vertices, offset, nr, nv, st);
+        DSM_LAUNCH(sp_pick, nv, SP_THREADS, s, offset, nr, nv, st);
+        DSM_LAUNCH(sp_decide, nv, SP_THREADS, s, vertices, offset, nr, nv, (unsigned)tol16, st);
     }
-    hipLaunchKernelGGL(sp_status, dim3(1), dim3(64), 0, s, st, status);
-    return check_launch("sp_status");
+    DSM_LAUNCH(sp_status, 1, 64, s, st, status);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_simplify_count(const int* vertices, const int* offset, int n_rings, int n_vertices, int* n_out,
                                         void* workspace, size_t workspace_bytes, void* stream)
 {
     using namespace smvs;
-    const SpBuf extra[] = {{n_out, 4, "n_out"}};
+    const DsmBuf extra[] = {{n_out, 4, "n_out"}};
     if (!n_out) return fail(SMVS_ERR_ARG, "null pointer argument");
     if (int rc = simplify_check(vertices, offset, n_rings, n_vertices, workspace, workspace_bytes, extra, 1)) return rc;
     const SimplifyWorkspace w = simplify_workspace((size_t)n_rings, (size_t)n_vertices);
@@ -522,19 +510,15 @@ SMVS_EXPORT int smvs_dsm_simplify_count(const int* vertices, const int* offset, 
     char* base = (char*)workspace;
     int *s1 = (int*)(base + w.s1), *s2 = (int*)(base + w.s2);
     int rc;
-    hipLaunchKernelGGL(sp_flags, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, nv, st);
-    if ((rc = check_launch("sp_flags"))) return rc;
+    DSM_LAUNCH(sp_flags, nv, SP_THREADS, s, nv, st);
     if ((rc = ol_scan_exclusive(st.pos, nv, nullptr, s1, s2, st.tail + SP_NKEPT, s, "ol_scan (kept vertices)"))) return rc;
-    hipLaunchKernelGGL(sp_list, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, nv, st);
-    if ((rc = check_launch("sp_list"))) return rc;
+    DSM_LAUNCH(sp_list, nv, SP_THREADS, s, nv, st);
     if (hipMemsetAsync(st.a2in, 0, w.rcount - w.a2in, s) != hipSuccess) return check_launch("dsm_simplify_count (clearing the sums)");
-    hipLaunchKernelGGL(sp_areas, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, vertices, offset, nr, nv, st);
-    if ((rc = check_launch("sp_areas"))) return rc;
-    hipLaunchKernelGGL(sp_rings, dim3(sp_blocks(nr)), dim3(SP_THREADS), 0, s, offset, nr, nv, st);
-    if ((rc = check_launch("sp_rings"))) return rc;
+    DSM_LAUNCH(sp_areas, nv, SP_THREADS, s, vertices, offset, nr, nv, st);
+    DSM_LAUNCH(sp_rings, nr, SP_THREADS, s, offset, nr, nv, st);
     if ((rc = ol_scan_exclusive(st.rcount, nr, nullptr, s1, s2, st.tail + SP_NOUT, s, "ol_scan (rings)"))) return rc;
-    hipLaunchKernelGGL(sp_count_out, dim3(1), dim3(64), 0, s, st, n_out);
-    return check_launch("sp_count_out");
+    DSM_LAUNCH(sp_count_out, 1, 64, s, st, n_out);
+    return SMVS_OK;
 }
 
 SMVS_EXPORT int smvs_dsm_simplify_write(const int* vertices, const int* offset, int n_rings, int n_vertices, int n_out,
@@ -545,7 +529,7 @@ SMVS_EXPORT int smvs_dsm_simplify_write(const int* vertices, const int* offset, 
     if (n_out < 0 || n_out > n_vertices) return fail(SMVS_ERR_ARG, "n_out must be in 0 .. n_vertices = %d, got %d", n_vertices, n_out);
     if (!out_offset) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t m = n_rings > 0 ? (size_t)n_rings : 0, k = (size_t)n_out;
-    const SpBuf extra[] = {{out_offset, (m + 1) * 4, "out_offset"}, {out_vertices, k * 8, "out_vertices"}, {area2, m * 8, "area2"},
+    const DsmBuf extra[] = {{out_offset, (m + 1) * 4, "out_offset"}, {out_vertices, k * 8, "out_vertices"}, {area2, m * 8, "area2"},
                            {kept, k * 4, "kept"}, {simplified, m, "simplified"}};
     if (int rc = simplify_check(vertices, offset, n_rings, n_vertices, workspace, workspace_bytes, extra, 5)) return rc;
     const SimplifyWorkspace w = simplify_workspace((size_t)n_rings, (size_t)n_vertices);
@@ -559,13 +543,10 @@ SMVS_EXPORT int smvs_dsm_simplify_write(const int* vertices, const int* offset, 
         return SMVS_OK;
     }
     const SpOut o = {out_offset, out_vertices, kept, area2, simplified};
-    int rc;
-    hipLaunchKernelGGL(sp_write_vertices, dim3(sp_blocks(nv)), dim3(SP_THREADS), 0, s, vertices, offset, nr, nv, (unsigned)n_out, st, o);
-    if ((rc = check_launch("sp_write_vertices"))) return rc;
-    hipLaunchKernelGGL(sp_write_rings, dim3(sp_blocks(nr)), dim3(SP_THREADS), 0, s, nr, st, o);
-    if ((rc = check_launch("sp_write_rings"))) return rc;
-    hipLaunchKernelGGL(sp_finish, dim3(1), dim3(64), 0, s, st, nr, (unsigned)n_out, out_offset);
-    return check_launch("sp_finish");
+    DSM_LAUNCH(sp_write_vertices, nv, SP_THREADS, s, vertices, offset, nr, nv, (unsigned)n_out, st, o);
+    DSM_LAUNCH(sp_write_rings, nr, SP_THREADS, s, nr, st, o);
+    DSM_LAUNCH(sp_finish, 1, 64, s, st, nr, (unsigned)n_out, out_offset);
+    return SMVS_OK;
 }
 
 }  // extern "C"

@@ -6,8 +6,8 @@
 //   smvs_dsm_flow_length    step counts to the root by one pointer doubling with sums over the forest itself
 //
 // The network pass, every step one lane per cell or per tour element, 256 lanes a workgroup:
-//   1. receivers and roots of the whole grid as dsm_hydro.hip finds them (up <- up o up in place, ceil(log2 n) + 1 rounds), so
-//      that S = masked cells that reach a root; srecv = the receiver if it is in S, ST_ROOT at a mouth, ST_INVALID outside S.
+//   1. receivers and roots of the whole grid (dsm_flow.h: up <- up o up in place, ceil(log2 n) + 1 rounds), so
+//      that S = masked cells that reach a root; srecv = the receiver if it is in S, D8_ROOT at a mouth, D8_INVALID outside S.
 //   2. the mouths numbered in row-major order by a scan and listed; the Euler tour of the induced forest (elements 2 c down and
 //      2 c + 1 up, as fl_tour builds it) with the up element of a mouth leading to the down element of the next mouth: one list
 //      of 2 |S| elements.  One Wyllie doubling of ceil(log2(2 n)) rounds between two copies ranks it; an element is one 64-bit
@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "dsm_common.h"
+#include "dsm_flow.h"
 #include "dsm_scan.h"
 #include "smvs_host.h"
 
@@ -36,75 +37,33 @@ namespace smvs {
 
 typedef unsigned long long u64;
 
-constexpr int ST_THREADS = 256;
-constexpr long long ST_MAX_CELLS = 1ll << 30;
-constexpr int ST_ROOT = -1, ST_INVALID = -2;
+constexpr int ST_THREADS = D8_THREADS;
 constexpr unsigned ST_END = 0xffffffffu;
 constexpr int ST_MAX_ROUNDS = 30;
 // the counters at the end of the workspace, ints: the four counts, the mouths, the length of the offsets' scan, then per order
 // round the length of its scan and its total
 enum { ST_CELLS = 0, ST_LINKS, ST_VERTICES, ST_TOP, ST_MOUTHS, ST_WLEN, ST_LEN, ST_TOT = ST_LEN + ST_MAX_ROUNDS + 2, ST_WORDS = 128 };
 
-// Neighbour k = 0 .. 7 is E, SE, S, SW, W, NW, N, NE (include/satmvs.h, "Hydrology"), two bits each (+ 1) in one word.
-__host__ __device__ constexpr int st_dc(int k) { return (int)((0x901au >> (2 * k)) & 3u) - 1; }
-__host__ __device__ constexpr int st_dr(int k) { return (int)((0x01a9u >> (2 * k)) & 3u) - 1; }
-static_assert(st_dc(0) == 1 && st_dc(1) == 1 && st_dc(2) == 0 && st_dc(3) == -1 && st_dc(4) == -1 && st_dc(5) == -1 && st_dc(6) == 0 && st_dc(7) == 1, "dc");
-static_assert(st_dr(0) == 0 && st_dr(1) == 1 && st_dr(2) == 1 && st_dr(3) == 1 && st_dr(4) == 0 && st_dr(5) == -1 && st_dr(6) == -1 && st_dr(7) == -1, "dr");
-
 __device__ __forceinline__ u64 st_pair(unsigned low, u64 high) { return (u64)low | high << 32; }
-
-// The cell a code sends cell (r, c) to; ST_ROOT for code 0 and for a target off the grid or without a code; ST_INVALID for 9 .. 255.
-__device__ __forceinline__ int st_receiver(const unsigned char* __restrict__ dir, int gw, int gh, int r, int c)
-{
-    const unsigned code = dir[(size_t)r * gw + c];
-    if (code > 8) return ST_INVALID;
-    if (code == 0) return ST_ROOT;
-    const int rr = r + st_dr(code - 1), cc = c + st_dc(code - 1);
-    if (rr < 0 || rr >= gh || cc < 0 || cc >= gw) return ST_ROOT;
-    const size_t t = (size_t)rr * gw + cc;
-    return dir[t] > 8 ? ST_ROOT : (int)t;
-}
 
 // 0 E-W, 1 N-S, 2 diagonal: the kind of the step a code 1 .. 8 takes.
 __device__ __forceinline__ int st_step_kind(unsigned code) { return (code & 1u) ? (int)(((code - 1) >> 1) & 1u) : 2; }
 
-// ---- 1. the whole grid's forest, then the induced one ---------------------------------------------------------------------------
-__global__ __launch_bounds__(ST_THREADS)
-void st_receivers(const unsigned char* __restrict__ dir, int gw, int gh, int* __restrict__ recv, int* __restrict__ up)
-{
-    const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const int to = st_receiver(dir, gw, gh, (int)(i / (unsigned)gw), (int)(i % (unsigned)gw));
-    recv[i] = to;
-    up[i] = to >= 0 ? to : (int)i;
-}
-
-// up <- up o up, in place, as fl_jump of dsm_hydro.hip.  Every word is a cell index written by st_receivers.
-__global__ __launch_bounds__(ST_THREADS)
-void st_jump(unsigned n, int* up)
-{
-    const unsigned i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const unsigned a = (unsigned)up[i];
-    if (a >= n) return;
-    const unsigned b = (unsigned)up[a];
-    if (b < n && b != a) up[i] = (int)b;
-}
-
+// ---- 1. the whole grid's forest (dsm_flow.h), then the induced one --------------------------------------------------------------
 __global__ __launch_bounds__(ST_THREADS)
 void st_induced(const unsigned char* __restrict__ mask, unsigned n, const int* __restrict__ recv, const int* __restrict__ up,
                 int* __restrict__ srecv, int* __restrict__ mouth, int* words, int* flag)
 {
     const unsigned i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     bool cyclic = false, in_s = false;
-    int to = ST_INVALID;
-    if (i < n && recv[i] != ST_INVALID) {
+    int to = D8_INVALID;
+    if (i < n && recv[i] != D8_INVALID) {
         const unsigned root = (unsigned)up[i];
-        cyclic = !(root < n && recv[root] == ST_ROOT);
+        cyclic = !(root < n && recv[root] == D8_ROOT);
         in_s = !cyclic && mask[i] != 0;
         if (in_s) {
             const int down = recv[i];                        // a tree cell's receiver is a tree cell: the mask decides
-            to = down >= 0 && mask[down] != 0 ? down : ST_ROOT;
+            to = down >= 0 && mask[down] != 0 ? down : D8_ROOT;
         }
     }
     if (__any(cyclic) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
@@ -115,7 +74,7 @@ void st_induced(const unsigned char* __restrict__ mask, unsigned n, const int* _
     }
     if (i >= n) return;
     srecv[i] = to;
-    mouth[i] = to == ST_ROOT;
+    mouth[i] = to == D8_ROOT;
 }
 
 // ---- 2. the tour ---------------------------------------------------------------------------------------------------------------
@@ -123,7 +82,7 @@ __global__ __launch_bounds__(ST_THREADS)
 void st_mouth_list(unsigned n, const int* __restrict__ srecv, const int* __restrict__ mouth_at, int* __restrict__ list)
 {
     const unsigned i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
-    if (i < n && srecv[i] == ST_ROOT) list[mouth_at[i]] = (int)i;
+    if (i < n && srecv[i] == D8_ROOT) list[mouth_at[i]] = (int)i;
 }
 
 // The first neighbour of cell p from direction k0 on that flows into p, as its down element; ST_END if there is none.
@@ -133,7 +92,7 @@ __device__ __forceinline__ unsigned st_child_from(const int* __restrict__ srecv,
     unsigned found = ST_END;
 #pragma unroll
     for (int k = 7; k >= 0; --k) {
-        const int rr = r + st_dr(k), cc = c + st_dc(k);
+        const int rr = r + d8_dr(k), cc = c + d8_dc(k);
         if (k < k0 || rr < 0 || rr >= gh || cc < 0 || cc >= gw) continue;
         const int child = rr * gw + cc;
         if (srecv[child] == p) found = 2u * (unsigned)child;
@@ -148,7 +107,7 @@ void st_tour(const unsigned char* __restrict__ dir, int gw, int gh, const int* _
     const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     if (i >= n) return;
     const int p = srecv[i];
-    if (p == ST_INVALID) {
+    if (p == D8_INVALID) {
         tour[2 * (size_t)i] = tour[2 * (size_t)i + 1] = st_pair(ST_END, 0);
         return;
     }
@@ -188,7 +147,7 @@ void st_positions(unsigned n, const int* __restrict__ srecv, const u64* __restri
 {
     const unsigned i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     if (i >= n) return;
-    const bool in_s = srecv[i] != ST_INVALID;
+    const bool in_s = srecv[i] != D8_INVALID;
     const int total = 2 * words[ST_CELLS], last = (int)(2 * n) - 1;
     const int down = total - (int)(tour[2 * (size_t)i] >> 32), up = total - (int)(tour[2 * (size_t)i + 1] >> 32);
     // a list of 2 |S| elements ranks to 0 .. 2 |S| - 1; the clamp keeps every later index on the marks whatever happens
@@ -204,12 +163,12 @@ void st_mark(int gw, int gh, int k, const int* __restrict__ srecv, const unsigne
     const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     const bool active = k == 1 || words[ST_TOT + k - 1] > 0;
     if (i == 0) words[ST_LEN + k] = active ? 2 * words[ST_CELLS] : 0;
-    if (!active || i >= n || srecv[i] == ST_INVALID) return;
+    if (!active || i >= n || srecv[i] == D8_INVALID) return;
     const int r = (int)(i / (unsigned)gw), c = (int)(i % (unsigned)gw);
     int inflow = 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int rr = r + st_dr(j), cc = c + st_dc(j);
+        const int rr = r + d8_dr(j), cc = c + d8_dc(j);
         if (rr < 0 || rr >= gh || cc < 0 || cc >= gw) continue;
         const int u = rr * gw + cc;
         inflow += srecv[u] == (int)i && ord[u] == k;
@@ -235,7 +194,7 @@ void st_heads(int gw, int gh, const int* __restrict__ srecv, unsigned char* __re
 {
     const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     if (i >= n) return;
-    if (srecv[i] == ST_INVALID) {
+    if (srecv[i] == D8_INVALID) {
         inflow[i] = 255;
         lp[i] = st_pair(i, 0);
         head_at[i] = 0;
@@ -246,7 +205,7 @@ void st_heads(int gw, int gh, const int* __restrict__ srecv, unsigned char* __re
     unsigned from = i;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int rr = r + st_dr(j), cc = c + st_dc(j);
+        const int rr = r + d8_dr(j), cc = c + d8_dc(j);
         if (rr < 0 || rr >= gh || cc < 0 || cc >= gw) continue;
         const int u = rr * gw + cc;
         if (srecv[u] == (int)i) { ++count; from = (unsigned)u; }
@@ -279,12 +238,12 @@ void st_maps(unsigned n, const int* __restrict__ srecv, const unsigned char* __r
              int* __restrict__ link_map, int* words)
 {
     const unsigned i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
-    const int down = i < n ? srecv[i] : ST_INVALID;
+    const int down = i < n ? srecv[i] : D8_INVALID;
     const int junctions = __popcll(__ballot(down >= 0 && st_link_ends(inflow, down)));    // a link's closing vertex
     if (junctions && (threadIdx.x & 63) == 0) atomicAdd(words + ST_VERTICES, junctions);
     if (i >= n) return;
     if (order) order[i] = ord[i];
-    if (link_map) link_map[i] = down != ST_INVALID ? head_at[(unsigned)lp[i]] + 1 : 0;
+    if (link_map) link_map[i] = down != D8_INVALID ? head_at[(unsigned)lp[i]] + 1 : 0;
 }
 
 // The highest order = 1 + the rounds that promoted a cell; then the counts to the caller.
@@ -314,7 +273,7 @@ void st_tables(const unsigned char* __restrict__ dir, unsigned n, const int* __r
     if (i == 0) words[ST_WLEN] = match ? n_links : 0;
     if (!match || i >= n) return;
     const int down = srecv[i];
-    if (down == ST_INVALID) return;
+    if (down == D8_INVALID) return;
     const u64 a = lp[i];
     const unsigned h = (unsigned)a;
     const int link = head_at[h];
@@ -342,7 +301,7 @@ void st_vertices(int gw, unsigned n, const int* __restrict__ srecv, const unsign
     }
     if (i >= n) return;
     const int down = srecv[i];
-    if (down == ST_INVALID) return;
+    if (down == D8_INVALID) return;
     const u64 a = lp[i];
     const int link = head_at[(unsigned)a];
     if (link < 0 || link >= n_links) return;
@@ -365,7 +324,7 @@ void st_length_begin(const unsigned char* __restrict__ dir, int gw, int gh, u64*
 {
     const unsigned n = (unsigned)gw * (unsigned)gh, i = blockIdx.x * (unsigned)ST_THREADS + threadIdx.x;
     if (i >= n) return;
-    const int down = st_receiver(dir, gw, gh, (int)(i / (unsigned)gw), (int)(i % (unsigned)gw));
+    const int down = d8_receiver(dir, nullptr, gw, gh, (int)(i / (unsigned)gw), (int)(i % (unsigned)gw));
     const int kind = down >= 0 ? st_step_kind(dir[i]) : -1;
     to[i] = st_pair(down >= 0 ? (unsigned)down : ST_END, kind == 2);
     steps[i] = st_pair(kind == 0, kind == 1);
@@ -424,33 +383,13 @@ static StreamWorkspace stream_workspace(size_t n)
     return w;
 }
 
-struct StBuf { const void* p; size_t bytes; const char* name; };
-
-static const char* stream_grid_check(int gw, int gh)
-{
-    if (gw < 1 || gh < 1) return "non-positive grid size";
-    if ((long long)gw * gh >= ST_MAX_CELLS) return "grid too large: gw * gh must be below 2^30 cells";
-    return nullptr;
-}
-
 // What the entries check alike: the grid, and that no two of the buffers given (null or empty ones skipped) share a byte.
-static int stream_check(int gw, int gh, const StBuf* buf, int n_buf)
+static int stream_check(int gw, int gh, const DsmBuf* buf, int n_buf)
 {
-    if (const char* msg = stream_grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s (got %d x %d)", msg, gw, gh);
-    for (int i = 1; i < n_buf; ++i)
-        for (int j = 0; j < i; ++j)
-            if (buf[i].p && buf[j].p && buf[i].bytes && buf[j].bytes && dsm_overlap(buf[i].p, buf[i].bytes, buf[j].p, buf[j].bytes))
-                return fail(SMVS_ERR_ARG, "%s aliases %s", buf[i].name, buf[j].name);
+    if (const char* msg = d8_grid_check(gw, gh)) return fail(SMVS_ERR_ARG, "%s (got %d x %d)", msg, gw, gh);
+    const char* other = nullptr;
+    if (const char* name = dsm_first_alias(buf, n_buf, other)) return fail(SMVS_ERR_ARG, "%s aliases %s", name, other);
     return SMVS_OK;
-}
-
-static unsigned st_blocks(size_t n) { return (unsigned)((n + ST_THREADS - 1) / ST_THREADS); }
-
-static int st_ceil_log2(size_t n)
-{
-    int r = 0;
-    while (((size_t)1 << r) < n) ++r;
-    return r;
 }
 
 static int stream_order_rounds(size_t n)                     // an order k needs 2^(k - 1) sources: k <= floor(log2 n) + 1, and 30 at 2^30 cells
@@ -459,12 +398,6 @@ static int stream_order_rounds(size_t n)                     // an order k needs
     while (((size_t)2 << r) <= n) ++r;
     return r < ST_MAX_ROUNDS ? r : ST_MAX_ROUNDS;
 }
-
-#define ST_LAUNCH(kernel, count, ...)                                                                  \
-    do {                                                                                               \
-        hipLaunchKernelGGL(kernel, dim3(st_blocks(count)), dim3(ST_THREADS), 0, s, __VA_ARGS__);       \
-        if (int rc_ = check_launch(#kernel)) return rc_;                                               \
-    } while (0)
 
 // The network pass: everything the two entries share.  order, link_map and counts may be null.
 static int stream_pass(const unsigned char* dir, const unsigned char* mask, int gw, int gh, unsigned char* order, int* link_map,
@@ -485,28 +418,27 @@ static int stream_pass(const unsigned char* dir, const unsigned char* mask, int 
     if (hipMemsetAsync(words, 0, ST_WORDS * 4, s) != hipSuccess) return check_launch("dsm_stream (clearing the counters)");
     if (flag && hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return check_launch("dsm_stream (clearing the flag)");
     int* flag_word = flag ? flag : words + ST_WORDS - 1;
-    ST_LAUNCH(st_receivers, n, dir, gw, gh, recv, up);
-    for (int k = 0, rounds = st_ceil_log2(n) + 1; k < rounds; ++k) ST_LAUNCH(st_jump, n, (unsigned)n, up);
-    ST_LAUNCH(st_induced, n, mask, (unsigned)n, (const int*)recv, (const int*)up, srecv, mouth_at, words, flag_word);
+    if ((rc = d8_roots(dir, nullptr, gw, gh, recv, up, s))) return rc;
+    DSM_LAUNCH(st_induced, n, ST_THREADS, s, mask, (unsigned)n, (const int*)recv, (const int*)up, srecv, mouth_at, words, flag_word);
     if ((rc = ol_scan_exclusive(mouth_at, (unsigned)n, nullptr, s1, s2, words + ST_MOUTHS, s, "ol_scan (mouths)"))) return rc;
-    ST_LAUNCH(st_mouth_list, n, (unsigned)n, (const int*)srecv, (const int*)mouth_at, list);
-    ST_LAUNCH(st_tour, n, dir, gw, gh, (const int*)srecv, (const int*)mouth_at, (const int*)list, (const int*)words, tour[0]);
+    DSM_LAUNCH(st_mouth_list, n, ST_THREADS, s, (unsigned)n, (const int*)srecv, (const int*)mouth_at, list);
+    DSM_LAUNCH(st_tour, n, ST_THREADS, s, dir, gw, gh, (const int*)srecv, (const int*)mouth_at, (const int*)list, (const int*)words, tour[0]);
     int at = 0;
-    for (int k = 0, rounds = st_ceil_log2(2 * n); k < rounds; ++k, at ^= 1) ST_LAUNCH(st_rank, 2 * n, (unsigned)(2 * n), (const u64*)tour[at], tour[at ^ 1]);
-    ST_LAUNCH(st_positions, n, (unsigned)n, (const int*)srecv, (const u64*)tour[at], (const int*)words, pos, ord);
+    for (int k = 0, rounds = dsm_ceil_log2(2 * n); k < rounds; ++k, at ^= 1) DSM_LAUNCH(st_rank, 2 * n, ST_THREADS, s, (unsigned)(2 * n), (const u64*)tour[at], tour[at ^ 1]);
+    DSM_LAUNCH(st_positions, n, ST_THREADS, s, (unsigned)n, (const int*)srecv, (const u64*)tour[at], (const int*)words, pos, ord);
     const int rounds = stream_order_rounds(n);
     for (int k = 1; k <= rounds; ++k) {
-        ST_LAUNCH(st_mark, n, gw, gh, k, (const int*)srecv, (const unsigned char*)ord, (const int2*)pos, marks, words);
+        DSM_LAUNCH(st_mark, n, ST_THREADS, s, gw, gh, k, (const int*)srecv, (const unsigned char*)ord, (const int2*)pos, marks, words);
         if ((rc = ol_scan_exclusive(marks, (unsigned)(2 * n), words + ST_LEN + k, s1, s2, words + ST_TOT + k, s, "ol_scan (marks)"))) return rc;
-        ST_LAUNCH(st_promote, n, (unsigned)n, k, (const int2*)pos, (const int*)marks, (const int*)words, ord);
+        DSM_LAUNCH(st_promote, n, ST_THREADS, s, (unsigned)n, k, (const int2*)pos, (const int*)marks, (const int*)words, ord);
     }
-    ST_LAUNCH(st_heads, n, gw, gh, (const int*)srecv, inflow, lp, head_at);
+    DSM_LAUNCH(st_heads, n, ST_THREADS, s, gw, gh, (const int*)srecv, inflow, lp, head_at);
     if ((rc = ol_scan_exclusive(head_at, (unsigned)n, nullptr, s1, s2, words + ST_LINKS, s, "ol_scan (heads)"))) return rc;
-    for (int k = 0, jumps = st_ceil_log2(n) + 1; k < jumps; ++k) ST_LAUNCH(st_link_jump, n, (unsigned)n, lp);
-    ST_LAUNCH(st_maps, n, (unsigned)n, (const int*)srecv, (const unsigned char*)inflow, (const u64*)lp, (const int*)head_at,
+    for (int k = 0, jumps = dsm_ceil_log2(n) + 1; k < jumps; ++k) DSM_LAUNCH(st_link_jump, n, ST_THREADS, s, (unsigned)n, lp);
+    DSM_LAUNCH(st_maps, n, ST_THREADS, s, (unsigned)n, (const int*)srecv, (const unsigned char*)inflow, (const u64*)lp, (const int*)head_at,
               (const unsigned char*)ord, order, link_map, words);
-    hipLaunchKernelGGL(st_counts, dim3(1), dim3(64), 0, s, rounds, words, counts);
-    return check_launch("st_counts");
+    DSM_LAUNCH(st_counts, 1, 64, s, rounds, words, counts);
+    return SMVS_OK;
 }
 
 }  // namespace smvs
@@ -516,7 +448,7 @@ extern "C" {
 SMVS_EXPORT size_t smvs_dsm_stream_workspace_bytes(int gw, int gh)
 {
     using namespace smvs;
-    return stream_grid_check(gw, gh) ? 0 : stream_workspace((size_t)gw * gh).bytes;
+    return d8_grid_check(gw, gh) ? 0 : stream_workspace((size_t)gw * gh).bytes;
 }
 
 SMVS_EXPORT int smvs_dsm_stream_order(const unsigned char* dir, const unsigned char* mask, int gw, int gh, unsigned char* order,
@@ -526,7 +458,7 @@ SMVS_EXPORT int smvs_dsm_stream_order(const unsigned char* dir, const unsigned c
     if (!dir || !mask || !order || !counts || !flag || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
     const StreamWorkspace w = stream_workspace(n);
-    const StBuf buf[] = {{dir, n, "dir"}, {mask, n, "mask"}, {order, n, "order"}, {link_map, n * 4, "link_map"}, {counts, 16, "counts"},
+    const DsmBuf buf[] = {{dir, n, "dir"}, {mask, n, "mask"}, {order, n, "order"}, {link_map, n * 4, "link_map"}, {counts, 16, "counts"},
                          {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
     if (int rc = stream_check(gw, gh, buf, 7)) return rc;
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
@@ -543,7 +475,7 @@ SMVS_EXPORT int smvs_dsm_stream_write(const unsigned char* dir, const unsigned c
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0, nl = (size_t)n_links, nv = (size_t)n_vertices;
     if (n && (nl > n || nv > 2 * n)) return fail(SMVS_ERR_ARG, "more links (%d) than cells or more vertices (%d) than twice the cells (%zu)", n_links, n_vertices, n);
     const StreamWorkspace w = stream_workspace(n);
-    const StBuf buf[] = {{dir, n, "dir"}, {mask, n, "mask"}, {head, nl * 4, "head"}, {link_order, nl * 4, "link_order"}, {next_link, nl * 4, "next_link"},
+    const DsmBuf buf[] = {{dir, n, "dir"}, {mask, n, "mask"}, {head, nl * 4, "head"}, {link_order, nl * 4, "link_order"}, {next_link, nl * 4, "next_link"},
                          {offset, (nl + 1) * 4, "offset"}, {vertices, nv * 8, "vertices"}, {steps, nl * 12, "steps"}, {workspace, w.bytes, "workspace"}};
     if (int rc = stream_check(gw, gh, buf, 9)) return rc;
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
@@ -552,17 +484,17 @@ SMVS_EXPORT int smvs_dsm_stream_write(const unsigned char* dir, const unsigned c
     if (int rc = stream_pass(dir, mask, gw, gh, nullptr, nullptr, nullptr, nullptr, base, w, s)) return rc;
     int* words = (int*)(base + w.words);
     if (n_links == 0) {
-        hipLaunchKernelGGL(st_no_links, dim3(1), dim3(64), 0, s, (const int*)words, n_vertices, offset);
-        return check_launch("st_no_links");
+        DSM_LAUNCH(st_no_links, 1, 64, s, (const int*)words, n_vertices, offset);
+        return SMVS_OK;
     }
     const int* srecv = (const int*)(base + w.srecv);
     const unsigned char *ord = (const unsigned char*)(base + w.ord), *inflow = (const unsigned char*)(base + w.inflow);
     const u64* lp = (const u64*)(base + w.tour) + n;
     const int* head_at = (const int*)((const u64*)(base + w.tour) + 2 * n);
     if (hipMemsetAsync(steps, 0, nl * 12, s) != hipSuccess) return check_launch("dsm_stream_write (clearing the step counts)");
-    ST_LAUNCH(st_tables, n, dir, (unsigned)n, srecv, inflow, lp, head_at, ord, words, n_links, n_vertices, head, link_order, next_link, offset, steps);
+    DSM_LAUNCH(st_tables, n, ST_THREADS, s, dir, (unsigned)n, srecv, inflow, lp, head_at, ord, words, n_links, n_vertices, head, link_order, next_link, offset, steps);
     if (int rc = ol_scan_exclusive(offset, (unsigned)n_links, words + ST_WLEN, (int*)(base + w.s1), (int*)(base + w.s2), offset + n_links, s, "ol_scan (offsets)")) return rc;
-    ST_LAUNCH(st_vertices, n, gw, (unsigned)n, srecv, inflow, lp, head_at, (const int*)words, n_links, n_vertices, offset, (int2*)vertices);
+    DSM_LAUNCH(st_vertices, n, ST_THREADS, s, gw, (unsigned)n, srecv, inflow, lp, head_at, (const int*)words, n_links, n_vertices, offset, (int2*)vertices);
     return SMVS_OK;
 }
 
@@ -573,18 +505,18 @@ SMVS_EXPORT int smvs_dsm_flow_length(const unsigned char* dir, int gw, int gh, i
     if (!dir || !steps || !flag || !workspace) return fail(SMVS_ERR_ARG, "null pointer argument");
     const size_t n = gw > 0 && gh > 0 ? (size_t)gw * gh : 0;
     const StreamWorkspace w = stream_workspace(n);
-    const StBuf buf[] = {{dir, n, "dir"}, {steps, n * 12, "steps"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
+    const DsmBuf buf[] = {{dir, n, "dir"}, {steps, n * 12, "steps"}, {flag, 4, "flag"}, {workspace, w.bytes, "workspace"}};
     if (int rc = stream_check(gw, gh, buf, 4)) return rc;
     if (workspace_bytes < w.bytes) return fail(SMVS_ERR_ARG, "workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t s = (hipStream_t)stream;
     u64* to[2] = {(u64*)workspace, (u64*)workspace + 2 * n};
     u64* sum[2] = {to[0] + n, to[1] + n};
     if (hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return check_launch("dsm_flow_length (clearing the flag)");
-    ST_LAUNCH(st_length_begin, n, dir, gw, gh, to[0], sum[0]);
+    DSM_LAUNCH(st_length_begin, n, ST_THREADS, s, dir, gw, gh, to[0], sum[0]);
     int at = 0;
-    for (int k = 0, rounds = st_ceil_log2(n); k < rounds; ++k, at ^= 1)
-        ST_LAUNCH(st_length_double, n, (unsigned)n, (const u64*)to[at], (const u64*)sum[at], to[at ^ 1], sum[at ^ 1]);
-    ST_LAUNCH(st_length_end, n, dir, (unsigned)n, (const u64*)to[at], (const u64*)sum[at], steps, flag);
+    for (int k = 0, rounds = dsm_ceil_log2(n); k < rounds; ++k, at ^= 1)
+        DSM_LAUNCH(st_length_double, n, ST_THREADS, s, (unsigned)n, (const u64*)to[at], (const u64*)sum[at], to[at ^ 1], sum[at ^ 1]);
+    DSM_LAUNCH(st_length_end, n, ST_THREADS, s, dir, (unsigned)n, (const u64*)to[at], (const u64*)sum[at], steps, flag);
     return SMVS_OK;
 }
 

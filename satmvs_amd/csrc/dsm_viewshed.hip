@@ -32,7 +32,6 @@ constexpr int VS_TILE_W = 64 / VS_TILE_H;
 static_assert(VS_TILE_H * VS_TILE_W == 64, "a wave holds 64 targets");
 constexpr int VS_MAX_OBS = 64;                           // observers of one call: they walk side by side in one launch
 constexpr int VS_VOID = INT32_MIN;                       // q of an invalid cell
-constexpr float VS_MAX_Z = 32768.0f;
 constexpr int VS_MAX_SIDE = 65536;                       // n < 2^16, so (q' - E) n and (q' - E) i stay below 2^47
 constexpr int VS_MAX_HEIGHT = 1 << 23;                   // |eye| and tgt, in units of 2^-8 m
 constexpr double VS_MAX_DROP = 0x1p30;
@@ -43,7 +42,8 @@ struct VsTerms { double xres, yres, c256, r2max; };
 
 __device__ __forceinline__ int vs_quantise(float v, float nodata)
 {
-    return dsm_cell_valid(v, nodata) && fabsf(v) <= VS_MAX_Z ? __double2int_rn(__dmul_rn((double)v, 256.0)) : VS_VOID;
+    int q;
+    return dsm_quantum(v, nodata, q) ? q : VS_VOID;
 }
 
 // Where a line reads its heights: the quantised grid of the workspace, or the floats themselves.

@@ -37,13 +37,13 @@ THRESHOLDS = (1, 100, 1000)
 
 
 def kernel_resources():
-    """{kernel: {vgpr, scratch}} of the st_ kernels, from the code objects inside the built library (tools/kernel_regs.py;
-    dsm_bench_common.scratch_sizes looks at the kernels named dsm_ only)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), _lib.LIB_PATH, "st_"], capture_output=True, text=True).stdout
+    """{kernel: {vgpr, scratch}} of the st_ kernels and the d8_ ones of csrc/dsm_flow.h, from the code objects inside the built
+    library (tools/kernel_regs.py; dsm_bench_common.scratch_sizes looks at the kernels named dsm_ only)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), _lib.LIB_PATH], capture_output=True, text=True).stdout
     table = {}
     for line in out.splitlines()[1:]:
         f = line.split()
-        if len(f) >= 8 and f[0].startswith("st_"):
+        if len(f) >= 8 and f[0].startswith(("st_", "d8_")):
             table[f[0]] = {"vgpr": int(f[1]), "scratch": int(f[-3])}
     return table
 
