@@ -1199,6 +1199,57 @@ int smvs_dsm_stream_write(const unsigned char* dir, const unsigned char* mask, i
 int smvs_dsm_flow_length(const unsigned char* dir, int gw, int gh, int* steps, int* flag,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- heights without a network: census plane sweep and semi-global matching (sgm.hip) ----------------
+ * Three entries over plane-minor uint16 volumes (B, H, W, D): the D planes of a pixel are contiguous.  1 <= D <= 256 and
+ * B H W D < 2^31.  Everything is integer arithmetic but the census comparisons (float32 `<`) and the sub-plane height (float64,
+ * every operation rounded by itself), so every output is equal bits from run to run, on any stream, and to the numpy statement
+ * of tests/sgm_oracle.py.  No atomics, no host synchronisation.
+ *
+ * smvs_sgm_census_cost: the matching cost of planes d_begin .. d_begin + Dc - 1 of `cost`; the other planes are left alone.
+ *   ref (B, H, W) float32; warped: HOST array of n_src DEVICE pointers, each (B, 2, Dc, H, W) float32 -- what smvs_rpc_warp_fwd /
+ *   smvs_homo_warp_fwd write for the 2-channel feature [grey image, ones]: channel 0 the warped image, channel 1 its coverage.
+ *   The window is (2 radius + 1)^2 without its centre: 8, 24 or 48 bits.  The bit of image I at (y, x) for the offset (dy, dx)
+ *   is I(y + dy, x + dx) < I(y, x) in float32 (strict, false with a NaN); an offset that leaves the H x W grid gives 0 in every
+ *   image, which is the mask M of the rule.  Source s is valid at (d, y, x) iff its coverage is >= cov_min at the centre and at
+ *   every window position on the grid.  ham_s = popcount(census_ref ^ census_s); with n valid sources
+ *   cost = floor(16 sum_valid ham_s / n) (<= 768), and 0xFFFF ("void") with n = 0.  The census of ref is computed once per call,
+ *   into the workspace (8 bytes per pixel: smvs_sgm_census_workspace_bytes(B, H, W), 0 = unsupported sizes).
+ *   Limits (SMVS_ERR_ARG with a message, before any HIP call; nothing is written): non-null pointers; 1 <= n_src <= 7;
+ *   radius 1, 2 or 3; cov_min not NaN; B, H, W >= 1; 1 <= D <= 256; 0 <= d_begin, 1 <= Dc, d_begin + Dc <= D; B H W D < 2^31;
+ *   the workspace large enough; ref, cost, workspace and every warped volume do not overlap.
+ *
+ * smvs_sgm_aggregate: sum = sum over the directions r of L_r.  C'(p, d) = void_cost where cost == 0xFFFF, else
+ *   min(cost, cost_max).  Directions, each with q = p - r: paths 4: (0, +-1), (+-1, 0); paths 8: those and (+-1, +-1).
+ *   q off the grid: L_r(p, d) = C'(p, d).  Otherwise, with m = min_k L_r(q, k) and the d +- 1 terms only where those planes exist,
+ *     L_r(p, d) = C'(p, d) + min(L_r(q, d), L_r(q, d - 1) + P1, L_r(q, d + 1) + P1, m + P2') - m
+ *   P2' = P2 without a guide; with guide (B, H, W) uint8: P2' = max(p2_min, P2 - alpha |G(p) - G(q)|).
+ *   The bound: by induction L_r(p, .) >= C'(p, .) >= 0 (every term of the min is >= m), and the min is <= m + P2', so
+ *   L_r <= C' + P2' <= cost_max + P2.  With paths (cost_max + P2) <= 65535 neither an L_r nor the sum of all of them leaves
+ *   uint16: nothing wraps and nothing saturates.
+ *   Limits (SMVS_ERR_ARG): non-null cost and sum, which do not overlap each other or the guide; sizes as above; paths 4 or 8;
+ *   0 <= P1 <= p2_min <= P2; 0 <= alpha <= 65535; 0 <= void_cost <= cost_max; paths (cost_max + P2) <= 65535.
+ *
+ * smvs_sgm_select: per pixel the winner d0 = the smallest index of the minimum of sum, a uniqueness test and a sub-plane height.
+ *   depth: (B, D) or, with depth_is_4d, (B, D, H, W) float32.  support = the number of planes whose cost is not 0xFFFF.
+ *   Rejected (index -1, height NaN): cost given and support < min_support; or some d with |d - d0| > 1 has
+ *   sum[d] (100 - uniqueness) < sum[d0] 100 (int32).  Otherwise a, b, c = sum[d0 - 1], sum[d0], sum[d0 + 1], den = a + c - 2 b;
+ *   t = 0 at an end plane or with den = 0, else t = (double)(a - c) / (double)(2 den), one IEEE division (|t| <= 1/2);
+ *   height = (float)(h0 + t (h+ - h0)) for t >= 0, (float)(h0 + t (h0 - h-)) for t < 0, the operands widened to double, a
+ *   difference, a product and a sum each rounded once.  A NaN height is written as the quiet NaN 0x7FC00000.
+ *   min_sum = sum[d0] and support are written for every pixel, rejected or not.
+ *   Limits (SMVS_ERR_ARG): non-null sum, depth, index, height; sizes as above; 0 <= uniqueness <= 99; min_support >= 0;
+ *   support needs cost; no output overlaps an input or another output. */
+size_t smvs_sgm_census_workspace_bytes(int B, int H, int W);
+int smvs_sgm_census_cost(const float* ref, const float* const* warped /* HOST, n_src device pointers */, int n_src,
+                         int radius, float cov_min, unsigned short* cost, int B, int H, int W, int d_begin, int Dc, int D,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int smvs_sgm_aggregate(const unsigned short* cost, const unsigned char* guide /* may be NULL */, unsigned short* sum,
+                       int B, int H, int W, int D, int P1, int P2, int p2_min, int alpha, int cost_max, int void_cost,
+                       int paths, void* stream);
+int smvs_sgm_select(const unsigned short* sum, const unsigned short* cost /* may be NULL */, const float* depth, int depth_is_4d,
+                    int uniqueness, int min_support, int* index, float* height, unsigned short* min_sum /* may be NULL */,
+                    unsigned short* support /* may be NULL */, int B, int H, int W, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
