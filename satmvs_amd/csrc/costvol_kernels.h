@@ -457,9 +457,10 @@ void costvol_dma_kernel(const CostVolParams p)
                 if (GEO == 0) {
                     double samp[PQ], line[PQ];
                     if constexpr (PC) {
-                        // planes per pass of the bivariate chain: 4 where the instance has 256 registers (8 planes per wave, 2 waves per SIMD), 2 in the
-                        // 168-register instances (9 monomial registers pairs per plane in flight: 4 planes spilled 20 registers to scratch)
-                        constexpr int PQW = DP >= 8 ? PC_PLANES : 2, PQC = PQ < PQW ? PQ : PQW;
+                        // planes per pass of the bivariate chain: 4 in every instance.  (Until the nested form the 168-register instances ran 2: the
+                        // monomial form kept 9 register pairs per plane in flight, and 4 planes spilled 20 registers to scratch.  Nested, a plane
+                        // holds P, L and three partial sums; no instance has scratch, profiles/plane_coef_horner.txt.)
+                        constexpr int PQC = PQ < PC_PLANES ? PQ : PC_PLANES;
 #pragma unroll
                         for (int v = 0; v < PQ; v += PQC)
                             o2p_pc_xn<PQC>(geo_d + (size_t)(s + 1) * RPC_LEN, src_n[s], lat + pq + v, lon + pq + v,

@@ -237,6 +237,15 @@ __device__ __forceinline__ double to_vgpr(double s)
     return v;
 }
 
+// x * y + k with the addend k in SGPRs (src2 of a VOP3 v_fma_f64).  Written out: given fma(x, y, k) with a k that has
+// no other use, the compiler selects the two-address v_fmac_f64 and copies k to VGPRs first (two v_mov_b32 per coefficient).
+__device__ __forceinline__ double fma_sgpr_addend(double x, double y, double k)
+{
+    double d;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "s"(k));
+    return d;
+}
+
 // A(P,L), B(P,L), C(P,L) of one cubic at N points
 template <int N>
 __device__ __forceinline__ void cubic_abc_xn(cgeo_t kp, const double* P, const double* L, double* A, double* B, double* C)
@@ -368,10 +377,14 @@ __device__ __forceinline__ void o2p_xn(cgeo_t r, const RpcInv& n, const double* 
 // (monomial order 1,L,P,H,LP,LH,PH,LL,PP,HH,PLH,LLL,LPP,LHH,LLP,PPP,PHH,LLH,PPH,HHH, warping.py:183-207).  A tiny
 // pre-kernel (rpc_plane_coef_kernel, costvol.hip) folds k0..k5 once per (batch item, plane, source, cubic) into a
 // caller-owned workspace, and a wave whose 64 x DP heights all equal their planes' heights (checked, wave-uniform
-// branch) evaluates 7 monomial products + 4 x (1 move + 9 FMAs) per source and plane instead of 6/4 moves + 76 FMAs +
-// the height normalisation.  Same polynomial, re-associated: coordinates move by float64 rounding only (~1e-13 px, like
-// the Horner form vs the reference's order).  Per-voxel heights (stages 2-3, jittered planes) fail the check and take
-// the trivariate chain above.
+// branch) evaluates each cubic in the nested form of A(P,L) above,
+//   (k0 + L (k1 + L (k4 + L c11))) + P ((k2 + L (k3 + L c14)) + P ((k5 + L c12) + P c15)):
+// 9 FMAs and no monomial product.  The three innermost L-steps pair an invariant coefficient with a folded one; the
+// invariant one is the VGPR copy (shared by the N planes of the pass), the folded one stays the SGPR operand.  That is
+// 4 x (9 FMAs + 3/N moves) per source and plane instead of 6/4 moves + 76 FMAs + the height normalisation (until the
+// nesting: 7 monomial products + 4 x (1 move + 9 FMAs), and seven more register pairs per plane in flight).  Same
+// polynomial, re-associated: coordinates move by float64 rounding only (~1e-13 px, like the Horner form vs the
+// reference's order).  Per-voxel heights (stages 2-3, jittered planes) fail the check and take the trivariate chain above.
 // Workspace layout (doubles): [0, pc_heights_doubles(B D)) the planes' heights, (b, d) at b D + d; the views' reciprocal scales (below);
 // then, from pc_header_doubles(B D, B) on, the folded
 // coefficients as [b][source][cubic: SNUM, SDEN, LNUM, LDEN][d][6]: for one (source, cubic) the planes are contiguous,
@@ -463,17 +476,16 @@ __device__ __forceinline__ void o2p_pc_xn(cgeo_t r, const RpcInv& n, const doubl
                                           cgeo_t pc, size_t cubic_stride, double* samp, double* line)
 {
     double q[4][N];
-    double P[N], L[N], LL[N], LP[N], PP[N], LLL[N], LPP[N], LLP[N], PPP[N];
+    double P[N], L[N];
 #pragma unroll
     for (int u = 0; u < N; ++u) {
         P[u] = (lat[u] - r[I_LAT_OFF]) * n.a;
         L[u] = (lon[u] - r[I_LON_OFF]) * n.b;
-        LL[u] = L[u] * L[u]; LP[u] = L[u] * P[u]; PP[u] = P[u] * P[u];
-        LLL[u] = L[u] * LL[u]; LPP[u] = L[u] * PP[u]; LLP[u] = L[u] * LP[u]; PPP[u] = P[u] * PP[u];
     }
     constexpr int base[4] = {I_SNUM, I_SDEN, I_LNUM, I_LDEN};
     // one cubic at a time for all N planes: 6 N folded (one contiguous run) + 4 invariant coefficients in SGPRs (56 at
-    // N = 4), then N independent chains of 1 move + 9 FMAs
+    // N = 4), 3 moves for the cubic (c11, c12, c14: each meets a folded coefficient in its step, and a VALU instruction
+    // reads one SGPR), then N independent nests of 9 FMAs
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         __builtin_amdgcn_sched_barrier(0);
@@ -488,27 +500,30 @@ __device__ __forceinline__ void o2p_pc_xn(cgeo_t r, const RpcInv& n, const doubl
             for (int j = 0; j < PC_PER_CUBIC; ++j) kk[u][j] = k[PC_PER_CUBIC * u + j];
         const double c11 = c[11], c12 = c[12], c14 = c[14], c15 = c[15];
         __builtin_amdgcn_sched_barrier(0);
-        double a[N];
+        const double v11 = to_vgpr(c11), v12 = to_vgpr(c12), v14 = to_vgpr(c14);     // one copy each for the N planes
+        double a[N], b[N], t[N];
+        // a = k0 + L (kL + L (kLL + L c11))
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = to_vgpr(kk[u][0]);
+        for (int u = 0; u < N; ++u) a[u] = fma_sgpr_addend(L[u], v11, kk[u][4]);
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(L[u], kk[u][1], a[u]);
+        for (int u = 0; u < N; ++u) a[u] = fma_sgpr_addend(L[u], a[u], kk[u][1]);
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(P[u], kk[u][2], a[u]);
+        for (int u = 0; u < N; ++u) a[u] = fma_sgpr_addend(L[u], a[u], kk[u][0]);
+        // b = kP + L (kLP + L c14)
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(LP[u], kk[u][3], a[u]);
+        for (int u = 0; u < N; ++u) b[u] = fma_sgpr_addend(L[u], v14, kk[u][3]);
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(LL[u], kk[u][4], a[u]);
+        for (int u = 0; u < N; ++u) b[u] = fma_sgpr_addend(L[u], b[u], kk[u][2]);
+        // t = (kPP + L c12) + P c15
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(PP[u], kk[u][5], a[u]);
+        for (int u = 0; u < N; ++u) t[u] = fma_sgpr_addend(L[u], v12, kk[u][5]);
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(LLL[u], c11, a[u]);
+        for (int u = 0; u < N; ++u) t[u] = fma(P[u], c15, t[u]);
+        // a + P (b + P t)
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(LPP[u], c12, a[u]);
+        for (int u = 0; u < N; ++u) b[u] = fma(P[u], t[u], b[u]);
 #pragma unroll
-        for (int u = 0; u < N; ++u) a[u] = fma(LLP[u], c14, a[u]);
-#pragma unroll
-        for (int u = 0; u < N; ++u) { q[i][u] = fma(PPP[u], c15, a[u]); pin(q[i][u]); }
+        for (int u = 0; u < N; ++u) { q[i][u] = fma(P[u], b[u], a[u]); pin(q[i][u]); }
     }
     __builtin_amdgcn_sched_barrier(0);
     const cgeo_t rr = launder(r);
