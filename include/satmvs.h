@@ -1080,6 +1080,44 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   0 <= n_links <= gw gh, 0 <= n_vertices <= 2 gw gh; inputs, outputs and workspace do not overlap; workspace:
  *   smvs_dsm_stream_workspace_bytes(gw, gh) for all three (0 = unsupported arguments): 54 bytes per cell, the scans' block
  *   sums and 512 bytes of counters; flow length uses the first 32 per cell.  No kernel uses scratch. */
+/* Cost distance ("Cost distance"): the accumulated cost of the cheapest trip from every cell to a source
+ * over a grid that is not uniformly passable, and its back-links as a D8 direction grid.  Integer arithmetic throughout.
+ *   Inputs.  friction (gh, gw) uint16, device: 0 a barrier, 1 .. 65535 the cost per metre in units of 2^-8; null = 256
+ *   everywhere.  sources (gh, gw) uint8, non-zero = a source; a source on a barrier is no source.  dsm (gh, gw) float32 with
+ *   nodata, or null; table a HOST int32[256] with entries 0 .. 65535 in units of 2^-8, or null; dsm and table come together or
+ *   not at all.  With a DSM a cell without a height (the test and q of "Hydrology": finite, != nodata, |z| <= 32768, q =
+ *   llrint(256 z)) is a barrier.  L a HOST int32[8], 1 <= L[k] <= 32767: the step lengths towards the neighbours k = 0 .. 7 (E,
+ *   SE, S, SW, W, NW, N, NE, as in "Hydrology") in units of 2^-8 m; the library takes no square root.  reverse is 0 or 1.
+ *   Step cost.  For a passable cell c and its passable neighbour n in direction k: x = (f_c + f_n) L[k] T in int64.  Without a
+ *   table T = 256.  With one, delta = q_n - q_c (with reverse q_c - q_n: travel FROM the sources), bin = clamp(floor(32 delta /
+ *   L[k]), -128, 127) + 128 with the floor towards -infinity (tan(slope) in steps of 1/32 out to +-4), T = table[bin], and T = 0
+ *   forbids the step.  w = max(1, floor(x / 2^10)) in units of 2^-15 cost metre.  Every step costs at least 1.  A diagonal
+ *   step does not look at the two cells beside it.
+ *   Keys.  D(c) = 0 at a passable source, else the minimum over the allowed steps c -> n of D(n) + w: because w >= 1 the
+ *   solution is unique and is the cost of the cheapest path.  A key is the uint64 D; a barrier is all ones; a cell not
+ *   reached yet, or not reachable, is all ones - 1.  gw gh <= 2^24 and w < 2^38 keep D below 2^62.
+ *   Back-link.  uint8 in the direction codes of "Hydrology": 0 at a source, 255 at barriers and unreachable cells, else k + 1
+ *   for the k that attains the minimum, ties to the lowest k.  D falls strictly along a back-link, so the grid is a forest
+ *   rooted at the sources, and smvs_dsm_flow_basins (the allocation), smvs_dsm_flow_length, smvs_dsm_flow_accumulate and
+ *   smvs_dsm_stream_* (the least-cost paths as links) take it as it is.
+ *   Reading.  raw int64 = D, -1 at barriers and unreachable cells.  cost float64 = (double)D / 32768.0, one conversion and one
+ *   IEEE division; +Inf where unreachable, NaN (0x7ff8000000000000) on barriers.  With max_cost (all ones for none) a cell
+ *   with D > max_cost reads as unreachable, back-link 255; everything upstream of it costs more, so the forest stays closed.
+ * smvs_dsm_cost_begin writes the keys the relaxation starts from (sources 0, barriers all ones, the rest all ones - 1) and the
+ *   number of passable sources to n_sources, a device int (block counts summed in a fixed order, no atomics).
+ *   smvs_dsm_cost_rounds runs `rounds` (1 .. 4096) global rounds and leaves in status (a device int) how many tiles changed
+ *   in the last one: 0 means the keys are the solution.  A round is one workgroup per tile of 32 x 32 cells, which lowers the
+ *   tile's cells in LDS against a halo of one cell until the tile is at its own fixed point and writes the interior back if
+ *   anything moved.  Keys only fall and never below the solution, so a round reads its neighbours' keys as they are; gw gh + 2
+ *   rounds bound any grid.  smvs_dsm_cost_read turns keys into raw, cost and backlink (each may be null).  All three take
+ *   the same friction and dsm; rounds and read the same L, table and reverse.  No host synchronisation in any entry.  Every
+ *   workspace word a kernel reads was written by a kernel of the same call; the only atomic is the per-launch counter of moved
+ *   tiles: equal bits from run to run, for any batching of the rounds, on any stream, and equal to the Python statement of
+ *   this rule (tests/dsm_cost_oracle.py).
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null sources, keys, n_sources, status, L and workspace; dsm and
+ *   table both or neither; gw, gh >= 1, gw * gh <= 2^24; 1 <= rounds <= 4096; L and table in range; reverse 0 or 1; inputs,
+ *   outputs and workspace do not overlap; workspace: smvs_dsm_cost_workspace_bytes(gw, gh) (0 = unsupported arguments): 16 KB
+ *   of round counters, 1 KB for the table and 4 bytes per 256 cells.  No kernel uses scratch. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -1198,6 +1236,19 @@ int smvs_dsm_stream_write(const unsigned char* dir, const unsigned char* mask, i
                           void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_flow_length(const unsigned char* dir, int gw, int gh, int* steps, int* flag,
                          void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_cost_workspace_bytes(int gw, int gh);
+int smvs_dsm_cost_begin(const unsigned short* friction /* may be null */, const unsigned char* sources,
+                        const float* dsm /* may be null */, int gw, int gh, float nodata, unsigned long long* keys,
+                        int* n_sources, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_cost_rounds(const unsigned short* friction /* may be null */, const float* dsm /* may be null */, int gw, int gh,
+                         float nodata, const int* L /* HOST, 8 */, const int* table /* HOST, 256; null iff dsm is */,
+                         int reverse, unsigned long long* keys, int rounds, int* status,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_cost_read(const unsigned short* friction /* may be null */, const float* dsm /* may be null */, int gw, int gh,
+                       float nodata, const int* L /* HOST, 8 */, const int* table /* HOST, 256; null iff dsm is */,
+                       int reverse, const unsigned long long* keys, unsigned long long max_cost,
+                       long long* raw /* may be null */, double* cost /* may be null */, unsigned char* backlink /* may be null */,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- heights without a network: census plane sweep and semi-global matching (sgm.hip) ----------------
  * Three entries over plane-minor uint16 volumes (B, H, W, D): the D planes of a pixel are contiguous.  1 <= D <= 256 and

@@ -1,6 +1,7 @@
 // dsm_flow.h -- the forest of a D8 direction grid, which dsm_hydro.hip (accumulation, basins) and dsm_stream.hip (stream
 // networks) share: the neighbour tables, the receiver of a cell, and the root of every cell by pointer doubling.  Every kernel
-// is static, as in dsm_scan.h: each source that includes this header has its own copy.
+// is static, as in dsm_scan.h: each source that includes this header has its own copy.  dsm_cost.hip takes the neighbour tables
+// alone: its back-links are codes in this numbering, so the forest below is what reads them.
 //
 // recv[c] is the cell c drains into, D8_ROOT or D8_INVALID.  up[c] starts as recv[c] (a root as itself) and is squared
 // ceil(log2(cells)) + 1 times IN PLACE: a lane that reads a word another lane has squared already only jumps further along the

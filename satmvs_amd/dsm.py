@@ -44,6 +44,14 @@ and water over the terrain: depressions filled, D8 directions, accumulation, cat
     write_streams("streams.geojson", links, grid, proj)        # or extract_streams(dtm, grid) for the whole chain
     metres = flow_length(direction, grid=grid)                 # every cell's way to its root (step counts without a grid)
 
+and distance over ground that is not uniformly passable: accumulated cost, the source that serves each cell, least-cost paths:
+
+    friction = quantise_friction(1.0 + slope(dtm, grid) / 10.0)      # cost per metre as uint16 in units of 2^-8; 0 = a barrier
+    cost, backlink = cost_distance(sources, grid, friction)    # float64 cost metre (+Inf unreachable, NaN barrier); a D8 forest
+    cost, backlink = cost_distance(sources, grid, dsm=dtm, vertical=tobler_table())   # walking effort: the slope along each step
+    served_by, n = cost_allocation(backlink)                   # = basins(backlink): the source each cell's cheapest trip ends at
+    paths = least_cost_paths(backlink, targets, grid)          # the trips of the targets as merged links, into write_streams()
+
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
     reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
@@ -114,6 +122,8 @@ and smvs_dsm_flow_basins numbers the roots by a scan: launches follow log(cells)
 smvs_dsm_stream_order / _write rank an Euler tour of the forest induced on the stream cells, raise the Strahler order by one
 per round through a scan of junction marks at their tour positions, and find every cell's link head by an in-place pointer
 doubling; smvs_dsm_flow_length is one doubling over the forest with the three step counts as sums.
+smvs_dsm_cost_begin / _rounds / _read are the flood's relaxation with another step rule: uint64 accumulated costs over the same
+tiles, the eight integer step costs of a lane's cells in registers, the back-links read off the final keys one lane per cell.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1306,14 +1316,25 @@ def _flood(z, nodata, batch=None):
     keys = torch.empty((gh, gw), dtype=torch.int64, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     _call(dev, "smvs_dsm_flood_begin", z, gw, gh, nodata, keys, ws, nbytes)
+
+    def rounds(step):
+        _call(dev, "smvs_dsm_flood_rounds", z, gw, gh, nodata, keys, step, status, ws, nbytes)
+        return int(status.item())
+    return keys, _relax(rounds, gw * gh, "smvs_dsm_flood_rounds", batch)
+
+
+def _relax(rounds, cells, name, batch=None):
+    """The batch loop of the tile relaxations (flood, cost distance): rounds(k) runs k global rounds and returns the device's
+    status, read once; 8 rounds, then doubling (batch=k fixes it), until a batch ends with no tile changed -> the rounds run.
+    More than cells + 2 rounds cannot be: SatMVSNativeError."""
     run, step, grow = 0, batch or FLOOD_BATCH, batch is None
     while True:
-        _call(dev, "smvs_dsm_flood_rounds", z, gw, gh, nodata, keys, step, status, ws, nbytes)
+        status = rounds(step)
         run += step
-        if int(status.item()) == 0:
-            return keys, run
-        if run > gw * gh + 2:
-            raise _lib.SatMVSNativeError("smvs_dsm_flood_rounds: tiles still change after %d rounds, more than the grid has cells (%d)" % (run, gw * gh))
+        if status == 0:
+            return run
+        if run > cells + 2:
+            raise _lib.SatMVSNativeError("%s: tiles still change after %d rounds, more than the grid has cells (%d)" % (name, run, cells))
         if grow:
             step = min(2 * step, MAX_FLOOD_BATCH)
 
@@ -1714,6 +1735,217 @@ def extract_streams(dtm, grid, min_area_m2=25000.0, nodata=-999.0):
     acc = flow_accumulation(code, grid=grid)
     links = stream_links(code, streams(acc, min_area_m2), grid=grid)
     return {k: _back(as_numpy, t) for k, t in links.items()}
+
+
+# ---- cost distance: accumulated cost, back-links as a D8 forest, least-cost paths -----------------------------------------------
+MAX_COST_CELLS = 2 ** 24                                          # w < 2^38 and fewer steps than cells keep D below 2^62
+MAX_COST_LENGTH = 32767                                           # a step length in units of 2^-8 m
+MAX_COST_FACTOR = 65535                                           # a friction or a table entry in units of 2^-8
+COST_UNIT = 32768.0                                               # D counts 2^-15 cost metre
+NO_MAX_COST = 2 ** 64 - 1
+
+
+def cost_terms(grid):
+    """The eight step lengths of cost_distance() on `grid`, int32 in units of 2^-8 m: rint(256 flow_distances(grid)[k]) for
+    k = E, SE, S, SW, W, NW, N, NE.  ValueError if one leaves 1 .. 32767 (cells below 2^-8 m, or a diagonal above 127 m)."""
+    L = np.rint(256.0 * flow_distances(grid))
+    if not (np.isfinite(L).all() and L.min() >= 1 and L.max() <= MAX_COST_LENGTH):
+        raise ValueError("the step lengths of the grid must lie in 2^-8 m .. 127.99 m, got %s m" % (flow_distances(grid).tolist(),))
+    return L.astype(np.int32)
+
+
+def slope_table(fn):
+    """The vertical factor of cost_distance() as its int32[256] table: bin b holds the steps with floor(32 tan(slope)) = b - 128
+    (the two end bins take everything beyond -4 and +4); fn, a Python callable of tan(slope), is evaluated at the bin centres
+    (b - 127.5) / 32 and stored as rint(256 value).  A value that is not finite or is <= 0 gives 0, which forbids the step (so
+    does a positive value below 1 / 512); a value above 65535 / 256 is a ValueError.  Floats on the host only: the device
+    sees the integers."""
+    table = np.zeros(256, np.int32)
+    for b in range(256):
+        v = float(fn((b - 127.5) / 32.0))
+        if not math.isfinite(v) or v <= 0.0:
+            continue
+        if v > MAX_COST_FACTOR / 256.0:
+            raise ValueError("the vertical factor at tan(slope) = %g is %g, above 65535 / 256" % ((b - 127.5) / 32.0, v))
+        table[b] = int(np.rint(256.0 * v))
+    return table
+
+
+def tobler_table():
+    """slope_table() of walking: the pace relative to level ground from Tobler's hiking function, v = 6 exp(-3.5 |tan + 0.05|)
+    km/h, so exp(3.5 (|tan + 0.05| - 0.05)), times the surface length of the step, sqrt(1 + tan^2) = 1 / cos(slope).  Where the
+    product passes 65535 / 256 (beyond about 56 degrees either way) the step is forbidden.  tan is the rise in the direction of
+    travel: cost_distance() reads it towards the sources, and away from them with reverse=True."""
+    def factor(t):
+        v = math.exp(3.5 * (abs(t + 0.05) - 0.05)) * math.sqrt(1.0 + t * t)
+        return v if v <= MAX_COST_FACTOR / 256.0 else float("nan")
+    return slope_table(factor)
+
+
+def quantise_friction(friction, nodata=-999.0):
+    """A float friction grid [cost per metre] as the uint16 grid cost_distance() takes: rint(256 f) computed in float64, 0 (a
+    barrier) where f is not finite, equals nodata (compared in the grid's own dtype) or is <= 0.  A value above 65535 / 256 is
+    a ValueError; a positive one below 1 / 512 becomes a barrier.  numpy in, numpy out; a tensor stays on its device."""
+    as_numpy = not isinstance(friction, torch.Tensor)
+    f = torch.from_numpy(np.ascontiguousarray(friction)) if as_numpy else friction
+    if f.ndim != 2 or not f.is_floating_point():
+        raise ValueError("a friction grid is (gh, gw) of a float dtype, got %s %s" % (f.dtype, tuple(f.shape)))
+    bad = ~torch.isfinite(f) | (f == torch.tensor(float(nodata), dtype=f.dtype).item()) | (f <= 0)
+    q = torch.where(bad, torch.zeros((), dtype=torch.float64, device=f.device), torch.round(256.0 * f.double()))
+    if q.numel() and float(q.max()) > MAX_COST_FACTOR:
+        raise ValueError("friction above 65535 / 256 = %g does not fit: rescale the grid (got %g)" % (MAX_COST_FACTOR / 256.0, float(q.max()) / 256.0))
+    q = q.to(torch.int32).to(torch.uint16)
+    return q.numpy() if as_numpy else q
+
+
+def _friction_checked(friction, shape):
+    if not isinstance(friction, torch.Tensor):
+        friction = np.asarray(friction)
+    if friction.dtype not in (np.uint16, torch.uint16) or tuple(friction.shape) != tuple(shape):
+        raise ValueError("friction is uint16 of shape %s in units of 2^-8 (quantise_friction() makes it), got %s %s"
+                         % (tuple(shape), friction.dtype, tuple(friction.shape)))
+    return friction
+
+
+def _table_checked(vertical):
+    table = np.ascontiguousarray(vertical)
+    if table.shape != (256,) or not np.issubdtype(table.dtype, np.integer) or table.min() < 0 or table.max() > MAX_COST_FACTOR:
+        raise ValueError("vertical is the int table of slope_table(): 256 entries in 0 .. 65535")
+    return table.astype(np.int32)
+
+
+def _max_cost_units(max_cost):
+    """max_cost [cost metre] in the units of D: floor(32768 max_cost); None or +inf: no limit."""
+    if max_cost is None:
+        return NO_MAX_COST
+    max_cost = float(max_cost)
+    if math.isnan(max_cost) or max_cost < 0.0:
+        raise ValueError("max_cost must be >= 0, got %r" % max_cost)
+    return NO_MAX_COST if max_cost * COST_UNIT >= 2.0 ** 63 else int(math.floor(max_cost * COST_UNIT))
+
+
+def _cost_relax(dev, f, z, gw, gh, nodata, L, table, reverse, keys, ws, nbytes, batch=None):
+    """The rounds of cost_distance() on begun keys -> the global rounds run."""
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+
+    def rounds(step):
+        _call(dev, "smvs_dsm_cost_rounds", f, z, gw, gh, nodata, L, table, reverse, keys, step, status, ws, nbytes)
+        return int(status.item())
+    return _relax(rounds, gw * gh, "smvs_dsm_cost_rounds", batch)
+
+
+def cost_distance(sources, grid, friction=None, dsm=None, vertical=None, reverse=False, max_cost=None, nodata=-999.0,
+                  return_raw=False, return_rounds=False, batch=None):
+    """Cost distance over a grid (include/satmvs.h, "Cost distance"): the accumulated cost of the cheapest
+    8-connected trip from every cell to a source, in integers.
+      sources   a (gh, gw) mask (bool or integer, non-zero = a source) or an (m, 2) integer list of (row, col), with the rules of
+                basins()' pour points; a source on a barrier is no source; no passable source at all is a ValueError
+      grid      a DSMGrid of that shape: the step lengths are cost_terms(grid)
+      friction  (gh, gw) uint16 from quantise_friction(): cost per metre in units of 2^-8, 0 = a barrier; None = 1.0 everywhere
+      dsm, vertical  a (gh, gw) float32 DSM, never converted, and the table of slope_table() / tobler_table(); both or neither.
+                Cells without a height (not finite, nodata, |z| > 32768) are barriers; a step c -> n towards the sources costs
+                table[bin of (q_n - q_c) / length] in place of 256, and 0 forbids it.  reverse=True reads the slope the other
+                way: travel away from the sources
+    A step between the neighbours c and n costs w = max(1, (f_c + f_n) L[k] T >> 10) units of 2^-15 cost metre, that is the
+    mean friction times the length times the vertical factor; D = 0 at the sources and min(D_n + w) elsewhere.
+    -> (cost, backlink): cost float64 (gh, gw) = D / 32768, +Inf where no source is reached, NaN on barriers; backlink uint8 in
+    the codes of flow_direction() ("index"): 0 at a source, k + 1 towards the neighbour the cheapest trip goes to (ties to the
+    lowest k), 255 at barriers and unreachable cells.  It is a flow forest rooted at the sources: cost_allocation(),
+    flow_length(), flow_accumulation() and least_cost_paths() take it as it is.  With max_cost [cost metre] cells with
+    D > floor(32768 max_cost) read as unreachable.  With return_raw also D as int64 (-1 at barriers and unreachable cells), with
+    return_rounds also the global rounds run.  The host reads the device's status once per batch of rounds (8, then doubling;
+    batch=k fixes it).  Every bit depends on the inputs alone.  numpy if the sources came as numpy, device tensors otherwise."""
+    _grid_checked(grid, "grid")
+    gh, gw = int(grid.height), int(grid.width)
+    if gh * gw > MAX_COST_CELLS:
+        raise ValueError("cost distance takes at most 2^24 cells, got %d x %d" % (gh, gw))
+    L = cost_terms(grid)
+    src = _pour_checked(sources, (gh, gw))
+    if friction is not None:
+        friction = _friction_checked(friction, (gh, gw))
+    if (dsm is None) != (vertical is None):
+        raise ValueError("dsm and vertical go together: a DSM needs the table of slope_table(), and the table a DSM")
+    table = None
+    if dsm is not None:
+        dsm = _on_grid(_dsm_bits(dsm), grid)
+        table = _table_checked(vertical)
+    units = _max_cost_units(max_cost)
+    if batch is not None:
+        batch = _int_checked(batch, "batch", 1, MAX_FLOOD_BATCH)
+    as_numpy = not isinstance(sources, torch.Tensor)
+    given = [t for t in (sources, friction, dsm) if isinstance(t, torch.Tensor) and t.is_cuda]
+    dev = given[0].device if given else _dev()
+    s = _pour_mask(*src, (gh, gw), dev)
+    f = None if friction is None else _to_device(friction, dev=dev)[0]
+    z = None if dsm is None else _to_device(dsm, dev=dev)[0]
+    nodata, reverse = float(nodata), int(bool(reverse))
+    nbytes = _lib.load().smvs_dsm_cost_workspace_bytes(gw, gh)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keys = torch.empty((gh, gw), dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_cost_begin", f, s, z, gw, gh, nodata, keys, count, ws, nbytes)
+    if int(count.item()) == 0:
+        raise ValueError("no passable source: every source lies on a barrier, or there is none")
+    rounds = _cost_relax(dev, f, z, gw, gh, nodata, L, table, reverse, keys, ws, nbytes, batch)
+    cost = torch.empty((gh, gw), dtype=torch.float64, device=dev)
+    backlink = torch.empty((gh, gw), dtype=torch.uint8, device=dev)
+    raw = torch.empty((gh, gw), dtype=torch.int64, device=dev) if return_raw else None
+    _call(dev, "smvs_dsm_cost_read", f, z, gw, gh, nodata, L, table, reverse, keys, ctypes.c_ulonglong(units), raw, cost, backlink, ws, nbytes)
+    out = _back(as_numpy, *((cost, backlink) + ((raw,) if return_raw else ())))
+    return out + (rounds,) if return_rounds else out
+
+
+def cost_allocation(backlink):
+    """The cost allocation of cost_distance(): which source serves each cell.  It is basins(backlink), nothing else: the
+    back-links are a direction grid whose roots are the sources, so a cell's basin is the source its cheapest trip ends at.
+    The sources are numbered 1 .. n in row-major order of their cells (a source on a barrier has no number); barriers and
+    unreachable cells get 0.  -> (labels (gh, gw) int32, n), as basins()."""
+    return basins(backlink)
+
+
+def least_cost_paths(backlink, targets, grid=None, raw=None):
+    """The least-cost paths from a set of targets to their sources as a connected network: the forest tools on the back-links
+    of cost_distance(), no kernel of their own.  targets: a (gh, gw) mask or an (m, 2) integer list of (row, col), with the
+    rules of basins()' pour points.  A target on a barrier or an unreachable cell (back-link 255) is reported, not followed.
+    The corridor is flow_accumulation(backlink, weights=targets) > 0, every cell some target's path passes, and the result is
+    stream_links(backlink, corridor, grid): paths that meet merge into one link from there on, and a link's `order` is the
+    Strahler order of the merged network.  -> that dict, which write_streams() takes as it is, and per target, in the order of
+    the list (row-major for a mask):
+      target_cell int32 (m, 2) row, col; target_link int32 (m), the link the target lies on (following next_link from it
+        leads to the source), -1 for a target that is not followed
+      target_steps int32 (m, 3), the E-W, N-S and diagonal steps of its path (flow_length(); -1 where not followed), and with
+        grid target_length_m float64 (m) = (n_ew xres + n_ns yres) + n_diag hypot(xres, yres), NaN where not followed
+      with raw (cost_distance(return_raw=True)) target_cost float64 (m) = raw / 32768, +Inf where raw is -1.
+    numpy if the back-links came as numpy, device tensors otherwise."""
+    backlink = _codes_checked(backlink)
+    shape = tuple(int(v) for v in backlink.shape)
+    is_mask, p = _pour_checked(targets, shape)
+    if grid is not None:
+        _on_grid(backlink, _grid_checked(grid, "grid"))
+    if raw is not None:
+        if not isinstance(raw, torch.Tensor):
+            raw = np.asarray(raw)
+        if raw.dtype not in (np.int64, torch.int64) or tuple(raw.shape) != shape:
+            raise ValueError("raw is int64 of the back-links' shape, got %s %s" % (raw.dtype, tuple(raw.shape)))
+    d, as_numpy = _to_device(backlink)
+    dev = d.device
+    mask = _pour_mask(is_mask, p, shape, dev)
+    rc = torch.nonzero(mask) if is_mask else torch.as_tensor(p).to(dev).long().reshape(-1, 2)
+    followed = (mask != 0) & (d <= 8)
+    acc = flow_accumulation(d, weights=followed.to(torch.int32))
+    out = stream_links(d, acc > 0, grid=grid)
+    r, c = rc[:, 0], rc[:, 1]
+    on = followed[r, c]
+    out["target_cell"] = rc.to(torch.int32)
+    out["target_link"] = torch.where(on, out["link"][r, c] - 1, torch.full_like(out["link"][r, c], -1))
+    steps = flow_length(d)[r, c]
+    out["target_steps"] = steps
+    if grid is not None:
+        out["target_length_m"] = torch.where(on, _steps_length(steps, grid), torch.full((), float("nan"), dtype=torch.float64, device=dev))
+    if raw is not None:
+        at = _to_device(raw, dev=dev)[0][r, c]
+        out["target_cost"] = torch.where(at < 0, torch.full((), float("inf"), dtype=torch.float64, device=dev), at.double() / COST_UNIT)
+    return {k: _back(as_numpy, t) for k, t in out.items()}
 
 
 # ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
