@@ -1118,6 +1118,63 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   table both or neither; gw, gh >= 1, gw * gh <= 2^24; 1 <= rounds <= 4096; L and table in range; reverse 0 or 1; inputs,
  *   outputs and workspace do not overlap; workspace: smvs_dsm_cost_workspace_bytes(gw, gh) (0 = unsupported arguments): 16 KB
  *   of round counters, 1 KB for the table and 4 bytes per 256 cells.  No kernel uses scratch. */
+/* Meshes ("Meshes"): an error-bounded triangle mesh of a DSM, the adaptive right-triangulated irregular
+ *   network (RTIN: longest-side bisection) over the lattice of cell centres, in integers throughout.
+ *   Lattice.  The vertices are the cell centres (row r, col c) of a (gh, gw) float32 DSM with the heights of the exact tools:
+ *   q = rn(256 z), valid iff finite, != (float)nodata and |z| <= 32768.  Root squares of side S = tile = 2^k cells (1 <= k <= 10)
+ *   cover the lattice from (0, 0): max(1, ceil((gh - 1) / S)) by max(1, ceil((gw - 1) / S)) of them.  Vertices beyond the grid
+ *   are invalid; there is no triangle beyond the cover.
+ *   Hierarchy.  A triangle is (a, b, c): hypotenuse a -> b, right angle at its apex c.  The root square at (r0, c0) holds
+ *   ((r0, c0), (r0 + S, c0 + S), (r0 + S, c0)) and ((r0 + S, c0 + S), (r0, c0), (r0, c0 + S)).  With m = (a + b) / 2, the split
+ *   vertex, the children of (a, b, c) are (c, a, m) and (b, c, m).  Levels 0 .. 2 k; the triangles of level 2 k have legs of one
+ *   cell and are not split.  Every vertex that is no root corner splits the triangles of exactly one level, one or two of them.
+ *   Exact error.  E(T) = +infinity if a lattice vertex in the closed triangle T is invalid, else the maximum over the lattice
+ *   vertices p in closed T of |q_p - plane_T(p)|.  Every barycentric weight has a denominator that divides S (a leg of T is h
+ *   or h / 2 lattice steps long, straight or diagonal, h = S / 2^j), so errors are exact integers in units of 2^-8 m / S, below
+ *   2^37; +infinity is 2^63 - 1.  This is the error of the whole triangle, not of its hypotenuse's midpoint alone.
+ *   Vertex error.  e(m) = max E(T) over the triangles that m splits.  Saturation: from the finest split level to the coarsest,
+ *   e(apex of T) <- max(e(apex of T), e(m(T))), an m beyond the grid counting as +infinity; the root triangles' apexes are root
+ *   corners, which hold 0.
+ *   Active.  A vertex is active iff e > threshold = floor(256 tol) S (strict); every root corner and every vertex beyond the
+ *   grid is active.  Emission.  A triangle of a level below 2 k is emitted iff its apex is active and its split vertex is not; a
+ *   triangle of level 2 k iff its apex is active and its three corners are valid.  It follows that the mesh is conforming (no
+ *   vertex strictly inside an edge), that it covers exactly the half-cells of level 2 k with three valid corners (voids and
+ *   the grid's outside are holes, refined down to single cells along their rim), and that every lattice vertex in an emitted
+ *   triangle deviates from its plane by at most floor(256 tol) quanta; tol = 0 is lossless in the quantised heights.
+ *   Order.  Vertices: the lattice vertices of the emitted triangles in row-major order.  Triangles: sorted by (row of a + b,
+ *   col of a + b, side), a unique key: a + b is twice the split vertex, for level 2 k twice a cell's middle; side is 0 for the
+ *   triangle whose apex is the lexicographically smaller (row, col) of the two that can share the hypotenuse, 1 for the other
+ *   (also where only one of them lies in the cover).  Each is written a, b, c with a and b swapped where needed so that it is
+ *   counter-clockwise seen from above, east right and north up (x = col, y = -row).
+ * smvs_dsm_mesh_errors: errors[r gw + c] int64 <- the saturated e of every vertex of the grid.  One launch clears, one finds the
+ *   deviations of all levels (a lane per vertex, 64-bit integer max atomics, the lanes of a wave that share a split vertex
+ *   combined first), 2 k - 1 gather passes saturate.  No workspace.  The maximum is order-free: equal bits from run to run.
+ * smvs_dsm_mesh_count: with errors, the same dsm, nodata and tile and threshold = floor(256 tol) S in the errors' units:
+ *   counts (device, 2 ints) <- n_triangles, n_vertices; the workspace keeps, per slot pair of the order (gh rows of gw vertices
+ *   and gw - 1 cells), the two sides' emission and the exclusive scan of their number, and the scan of the used vertices.  No host
+ *   synchronisation; the caller reads counts.
+ * smvs_dsm_mesh_write: with the workspace as smvs_dsm_mesh_count left it and its two counts: triangles int32 (3 per triangle,
+ *   indices into the vertex list), tri_level uint8, vertices int32 (col, row per vertex), z float32, the DSM's own bits.  status
+ *   (device, 1 int) <- n_triangles, or -1 with nothing else written if n_triangles or n_vertices differ from the workspace's
+ *   counts (arrays one too small, say).  The workspace is left as found: the call may be repeated.
+ * smvs_dsm_mesh_heights: heights[r gw + c] float32 <- the mesh's height at every vertex, nodata where the vertex is invalid or in
+ *   no emitted triangle; dev (may be null) int64 <- S q_p - S plane(p) in the errors' units, 2^63 - 1 where uncovered.  A lane per
+ *   vertex walks down from its root triangle (the one under the root's diagonal if p lies on it; the root square to the right
+ *   and below if p lies on a rim between two) into the child (c, a, m) if p lies on a's side of the line c - m or on it, else
+ *   into (b, c, m), while the split vertex is active: at most 2 k steps.  height = fl32(fl64(S plane) / fl64(256 S)), one IEEE
+ *   division of two exact doubles.  A walk that ends in a triangle of level 2 k with an invalid corner gives the vertex its own
+ *   q if an emitted triangle uses the vertex, else nodata.  All triangles that hold p agree on its height: a mesh vertex is
+ *   exact in each; p strictly inside an edge shared by two emitted triangles is interpolated along the edge's two ends by
+ *   both; and if a walk runs past an emitted triangle T that holds p, p is the split vertex of a descendant of T and active, so
+ *   by saturation T's split vertex is active and T is not emitted -- so a walk that reaches level 2 k without stopping has
+ *   passed no emitted triangle with p inside it or inside an edge, and only triangles with p as a corner are left.
+ *   Every workspace word a kernel reads was written by a kernel of the same call or, for write, of the count call (a
+ *   workspace full of anything will do).  No kernel uses scratch.
+ * Limits (SMVS_ERR_ARG with a message, before any HIP call; nothing is written): non-null pointers (dev may be null; the
+ *   outputs of write may be null where their count is 0); gw, gh >= 1, gw * gh < 2^29; tile a power of two in 2 .. 1024;
+ *   threshold >= 0; 0 <= n_triangles <= 2 gw gh, 0 <= n_vertices <= gw gh; inputs, outputs and workspace do not overlap;
+ *   workspace: smvs_dsm_mesh_workspace_bytes(gw, gh, tile) bytes (0 = unsupported arguments): 14 bytes per cell (two slot pairs
+ *   of 4 + 1 bytes and a 4-byte vertex mark) and the scans' block sums. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -1249,6 +1306,16 @@ int smvs_dsm_cost_read(const unsigned short* friction /* may be null */, const f
                        int reverse, const unsigned long long* keys, unsigned long long max_cost,
                        long long* raw /* may be null */, double* cost /* may be null */, unsigned char* backlink /* may be null */,
                        void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_mesh_workspace_bytes(int gw, int gh, int tile);
+int smvs_dsm_mesh_errors(const float* dsm, int gw, int gh, float nodata, int tile, long long* errors, void* stream);
+int smvs_dsm_mesh_count(const long long* errors, const float* dsm, int gw, int gh, float nodata, int tile, long long threshold,
+                        int* counts /* device, 2 */, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_mesh_write(const float* dsm, int gw, int gh, int tile, int n_triangles, int n_vertices, int* triangles,
+                        unsigned char* tri_level, int* vertices, float* z, int* status /* device, 1 */,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_mesh_heights(const long long* errors, const float* dsm, int gw, int gh, float nodata, int tile,
+                          long long threshold, float* heights, long long* dev /* may be null */,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- heights without a network: census plane sweep and semi-global matching (sgm.hip) ----------------
  * Three entries over plane-minor uint16 volumes (B, H, W, D): the D planes of a pixel are contiguous.  1 <= D <= 256 and

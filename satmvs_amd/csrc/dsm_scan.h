@@ -1,5 +1,5 @@
 // dsm_scan.h -- the exclusive scan of an int array on the device that dsm_outline.hip and dsm_contour.hip (through dsm_chain.h, whose
-// sort is a scan per bit), dsm_simplify.hip, dsm_hydro.hip and dsm_stream.hip share: three levels of
+// sort is a scan per bit), dsm_simplify.hip, dsm_hydro.hip, dsm_stream.hip and dsm_mesh.hip share: three levels of
 // 2048-element blocks (256 lanes of 8 elements), so any length below 2^31.  Every kernel is static: each source that includes
 // this header has its own copy.
 #pragma once

@@ -52,6 +52,13 @@ and distance over ground that is not uniformly passable: accumulated cost, the s
     served_by, n = cost_allocation(backlink)                   # = basins(backlink): the source each cell's cheapest trip ends at
     paths = least_cost_paths(backlink, targets, grid)          # the trips of the targets as merged links, into write_streams()
 
+and the surface itself as a triangle mesh with a guaranteed error (adaptive RTIN), for viewers, engines, printing, texturing:
+
+    errors = mesh_errors(dtm, tile=256)                        # once per DSM: the exact error of every hierarchy triangle, saturated
+    m = mesh(dtm, grid, tol=0.5, errors=errors)                # vertices, z, triangles, tri_level, xyz: every height within tol of it
+    h, dev = mesh_heights(dtm, 0.5, errors=errors, return_dev=True)   # the mesh's height at every cell, and its deviation
+    write_ply("dtm.ply", m, grid, colors=ortho_u8)             # binary PLY with the orthophoto's colours; write_obj() with vt
+
 and the comparison with another DSM (a ground truth, a LiDAR DSM, an earlier epoch), after removing the offset between them:
 
     reg = coregister(dsm, grid, gt, gt_grid)                   # the shift with the least spread of dsm - gt: de, dn, dz, std, grid
@@ -124,6 +131,10 @@ per round through a scan of junction marks at their tour positions, and find eve
 doubling; smvs_dsm_flow_length is one doubling over the forest with the three step counts as sums.
 smvs_dsm_cost_begin / _rounds / _read are the flood's relaxation with another step rule: uint64 accumulated costs over the same
 tiles, the eight integer step costs of a lane's cells in registers, the back-links read off the final keys one lane per cell.
+smvs_dsm_mesh_errors is one lane per lattice vertex over all levels of the bisection hierarchy, the deviation from each
+triangle's plane raised into its split vertex's word by 64-bit integer max atomics (a wave an 8 x 8 block, its lanes combined per
+split vertex first), then one gather pass per level; smvs_dsm_mesh_count / _write flag the emitted triangles per slot of the
+output order and place them by scans; smvs_dsm_mesh_heights walks every vertex down its root triangle by the active flags.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1946,6 +1957,222 @@ def least_cost_paths(backlink, targets, grid=None, raw=None):
         at = _to_device(raw, dev=dev)[0][r, c]
         out["target_cost"] = torch.where(at < 0, torch.full((), float("inf"), dtype=torch.float64, device=dev), at.double() / COST_UNIT)
     return {k: _back(as_numpy, t) for k, t in out.items()}
+
+
+# ---- meshes: the error-bounded triangulation of a DSM (adaptive RTIN), PLY and OBJ -----------------------------------------------
+MAX_MESH_CELLS = 2 ** 29                                          # vertices and cells together in an int32 scan
+MAX_MESH_TILE = 1024
+MESH_INF = 2 ** 63 - 1                                            # the error of a vertex whose triangles hold a void or leave the grid
+MESH_KEYS = ("vertices", "z", "triangles", "tri_level")
+
+
+def _mesh_tile_checked(tile):
+    tile = _int_checked(tile, "tile", 2, MAX_MESH_TILE)
+    if tile & (tile - 1):
+        raise ValueError("tile must be a power of two in 2 .. %d, got %r" % (MAX_MESH_TILE, tile))
+    return tile
+
+
+def _mesh_tol_units(tol):
+    """tol [m] -> floor(256 tol), the tolerance in height quanta."""
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not math.isfinite(tol) or tol < 0:
+        raise ValueError("tol is a finite number of metres >= 0, got %r" % (tol,))
+    return int(math.floor(256.0 * float(tol)))
+
+
+def _mesh_dsm(dsm, grid=None):
+    dsm = _dsm_bits(dsm)
+    if int(dsm.shape[0]) * int(dsm.shape[1]) >= MAX_MESH_CELLS:
+        raise ValueError("meshes take fewer than 2^29 cells, got %d x %d" % (dsm.shape[0], dsm.shape[1]))
+    if grid is not None:
+        _on_grid(dsm, _grid_checked(grid, "grid"))
+    return dsm
+
+
+def _mesh_errors_checked(errors, dsm):
+    """The int64 map of mesh_errors() for this DSM, never converted."""
+    if isinstance(errors, torch.Tensor) != isinstance(dsm, torch.Tensor):
+        raise ValueError("errors and dsm must both be numpy arrays or both be tensors")
+    if not isinstance(errors, torch.Tensor):
+        errors = np.asarray(errors)
+    if errors.dtype not in (np.int64, torch.int64):
+        raise ValueError("errors is int64, got %s" % (errors.dtype,))
+    if tuple(errors.shape) != tuple(dsm.shape):
+        raise ValueError("errors shape %s differs from the DSM's %s" % (tuple(errors.shape), tuple(dsm.shape)))
+    return errors
+
+
+def _mesh_inputs(dsm, grid, tol, tile, errors):
+    """Everything checked before any device work -> z, as_numpy, the error map on the device, tol_units, the threshold."""
+    dsm = _mesh_dsm(dsm, grid)
+    tile = _mesh_tile_checked(tile)
+    units = _mesh_tol_units(tol)
+    if errors is not None:
+        errors = _mesh_errors_checked(errors, dsm)
+    z, as_numpy = _to_device(dsm)
+    return z, as_numpy, errors, tile, units, min(units * tile, 2 ** 62)        # no finite error reaches 2^62
+
+
+def _mesh_error_map(z, tile, nodata):
+    gh, gw = z.shape
+    e = torch.empty((gh, gw), dtype=torch.int64, device=z.device)
+    _call(z.device, "smvs_dsm_mesh_errors", z, gw, gh, float(nodata), tile, e)
+    return e
+
+
+def mesh_errors(dsm, tile=256, nodata=-999.0):
+    """The saturated error of every lattice vertex (include/satmvs.h smvs_dsm_mesh_errors, DESIGN.md section 9, "Meshes"): dsm
+    (gh, gw) float32, fewer than 2^29 cells; tile a power of two in 2 .. 1024, the side S of the root squares.  -> int64
+    (gh, gw) in units of 2^-8 m / S: the largest deviation of any lattice vertex from the plane of a triangle that the vertex
+    splits, or of one further down that needs it; 2^63 - 1 where such a triangle holds a void or leaves the grid; 0 at the root
+    squares' corners.  It depends on dsm, nodata and tile alone, bit for bit, and serves any number of tolerances: pass it to
+    mesh() and mesh_heights() as `errors` for a chain of levels of detail.  numpy if the DSM came as numpy."""
+    dsm = _mesh_dsm(dsm)
+    tile = _mesh_tile_checked(tile)
+    z, as_numpy = _to_device(dsm)
+    return _back(as_numpy, _mesh_error_map(z, tile, nodata))
+
+
+def _mesh_write(z, tile, nt, nv, ws, nbytes):
+    """smvs_dsm_mesh_write into arrays of nt triangles and nv vertices -> the arrays and the status word, both on the device."""
+    dev = z.device
+    gh, gw = z.shape
+    out = {"vertices": torch.empty((nv, 2), dtype=torch.int32, device=dev), "z": torch.empty(nv, dtype=torch.float32, device=dev),
+           "triangles": torch.empty((nt, 3), dtype=torch.int32, device=dev), "tri_level": torch.empty(nt, dtype=torch.uint8, device=dev)}
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_mesh_write", z, gw, gh, tile, nt, nv, out["triangles"] if nt else None, out["tri_level"] if nt else None,
+          out["vertices"] if nv else None, out["z"] if nv else None, status, ws, nbytes)
+    return out, status
+
+
+def _mesh_status_checked(status, nt, nv):
+    """One host read: the write's status is n_triangles, or -1 where the counts given were not the workspace's."""
+    if int(status.item()) != nt:
+        raise _lib.SatMVSNativeError("smvs_dsm_mesh_write gave up: %d triangles and %d vertices are not the counts of its workspace" % (nt, nv))
+
+
+def mesh(dsm, grid=None, tol=0.5, tile=256, nodata=-999.0, errors=None):
+    """A triangle mesh of a DSM with a guaranteed error (include/satmvs.h smvs_dsm_mesh_count / _write, DESIGN.md section 9,
+    "Meshes"): the right-triangulated irregular network over the lattice of cell centres, refined exactly where a triangle's
+    plane would leave some lattice height by more than tol.  dsm (gh, gw) float32; tol [m] >= 0, used as floor(256 tol) height
+    quanta of 2^-8 m (tol = 0: lossless in the quantised heights); tile as in mesh_errors(); errors: that function's result for
+    this dsm, nodata and tile, else it is computed here.  Every lattice height within a triangle lies within tol of its plane;
+    the mesh has no T-junctions and covers exactly the finest half-cells whose three corners hold a height (voids and the
+    grid's outside are holes).
+    -> dict: vertices int32 (V, 2) col, row, in row-major order; z float32 (V), the DSM's own bits; triangles int32 (T, 3)
+      indices a, b, c, hypotenuse a -> b and right angle at c, counter-clockwise seen from above (east right, north up), sorted
+      by (row, col) of a + b and the apex's side; tri_level uint8 (T), 0 the root triangles .. 2 log2(tile) the half-cells;
+      n_vertices, n_triangles, tile, tol_units as Python ints; with grid (a DSMGrid of the DSM's shape) xyz float64 (V, 3): east,
+      north of the cell centres (e0 + col xres, n0 - row yres) and z.
+    numpy if the DSM came as numpy, device tensors otherwise.  The host reads the device once, for the two counts, like
+    outlines(); the write is given those very counts, so its status (-1 for counts that are not the workspace's) can only tell
+    of a workspace damaged in between: it is read and raised for numpy, whose arrays go to the host anyway, and not for tensors."""
+    z, as_numpy, errors, tile, units, thr = _mesh_inputs(dsm, grid, tol, tile, errors)
+    dev = z.device
+    gh, gw = z.shape
+    e = _mesh_error_map(z, tile, nodata) if errors is None else _to_device(errors, dev=dev)[0]
+    nbytes = _lib.load().smvs_dsm_mesh_workspace_bytes(gw, gh, tile)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_mesh_count", e, z, gw, gh, float(nodata), tile, thr, counts, ws, nbytes)
+    nt, nv = counts.tolist()
+    out, status = _mesh_write(z, tile, nt, nv, ws, nbytes)
+    if as_numpy:                                             # everything goes to the host anyway; tensors: see the docstring
+        _mesh_status_checked(status, nt, nv)
+    if grid is not None:
+        v = out["vertices"].double()
+        out["xyz"] = torch.stack([float(grid.e0) + v[:, 0] * float(grid.xres), float(grid.n0) - v[:, 1] * float(grid.yres), out["z"].double()], dim=1)
+    out = {k: _back(as_numpy, t) for k, t in out.items()}
+    out.update(n_vertices=nv, n_triangles=nt, tile=tile, tol_units=units)
+    return out
+
+
+def mesh_heights(dsm, tol, tile=256, nodata=-999.0, errors=None, return_dev=False):
+    """The height of mesh(dsm, tol=tol, tile=tile) at every lattice vertex (include/satmvs.h smvs_dsm_mesh_heights): float32
+    (gh, gw), fl32(S plane / (256 S)) with one IEEE division, nodata where the vertex is a void or in no triangle; a mesh vertex
+    gets its own quantised height.  return_dev: also int64 S q - S plane in the errors' units (|dev| <= floor(256 tol) tile at
+    every covered vertex, 0 at the mesh's vertices, 2^63 - 1 where uncovered).  To compare a mesh with its DSM without
+    rasterising triangles."""
+    z, as_numpy, errors, tile, units, thr = _mesh_inputs(dsm, None, tol, tile, errors)
+    dev = z.device
+    gh, gw = z.shape
+    e = _mesh_error_map(z, tile, nodata) if errors is None else _to_device(errors, dev=dev)[0]
+    nbytes = _lib.load().smvs_dsm_mesh_workspace_bytes(gw, gh, tile)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    h = torch.empty((gh, gw), dtype=torch.float32, device=dev)
+    d = torch.empty((gh, gw), dtype=torch.int64, device=dev) if return_dev else None
+    _call(dev, "smvs_dsm_mesh_heights", e, z, gw, gh, float(nodata), tile, thr, h, d, ws, nbytes)
+    return _back(as_numpy, h, d) if return_dev else _back(as_numpy, h)
+
+
+def _mesh_host(mesh, grid):
+    """vertices, z, triangles of a mesh() dict as host arrays and its (V, 3) float64 east, north, z on `grid`."""
+    for key in MESH_KEYS:
+        if key not in mesh:
+            raise ValueError("mesh is the dict of mesh(): entry %r is missing" % key)
+    host = {k: (mesh[k].cpu().numpy() if hasattr(mesh[k], "cpu") else np.asarray(mesh[k])) for k in MESH_KEYS}
+    v, z, t = host["vertices"], host["z"], host["triangles"]
+    if v.ndim != 2 or v.shape[1] != 2 or z.shape != (len(v),) or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("mesh is the dict of mesh()")
+    _grid_checked(grid, "grid")
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("mesh holds a triangle index outside its vertices")
+    if len(v) and (v.min() < 0 or v[:, 0].max() >= int(grid.width) or v[:, 1].max() >= int(grid.height)):
+        raise ValueError("mesh holds a vertex outside the grid")
+    xyz = np.stack([float(grid.e0) + v[:, 0].astype(np.float64) * float(grid.xres),
+                    float(grid.n0) - v[:, 1].astype(np.float64) * float(grid.yres), z.astype(np.float64)], axis=1)
+    return v, t.astype("<i4"), xyz
+
+
+def write_ply(path, mesh, grid, colors=None):
+    """A mesh() dict as a binary little-endian PLY: vertices x (east), y (north), z as float64, faces as lists of three int32.
+    float64 rather than float32 offsets from a `comment origin`: map coordinates need 7 to 8 digits before the decimal point,
+    double properties are plain PLY that the common readers take, and a reader that ignores comments still gets the right
+    coordinates.  colors: a uint8 (gh, gw, 3) image on the DSM's grid (an orthophoto of orthorectify(), say), read at the
+    vertices into red, green, blue.  Standard library and numpy only.  -> the number of faces."""
+    v, t, xyz = _mesh_host(mesh, grid)
+    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    if colors is not None:
+        colors = np.asarray(colors.cpu() if hasattr(colors, "cpu") else colors)
+        if colors.dtype != np.uint8 or colors.shape != (int(grid.height), int(grid.width), 3):
+            raise ValueError("colors is a uint8 (%d, %d, 3) image on the grid, got %s %s" % (grid.height, grid.width, colors.dtype, colors.shape))
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    rec = np.empty(len(v), dtype=fields)
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if colors is not None:
+        at = colors[v[:, 1], v[:, 0]]
+        rec["red"], rec["green"], rec["blue"] = at[:, 0], at[:, 1], at[:, 2]
+    faces = np.empty(len(t), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    faces["n"], faces["v"] = 3, t
+    names = {"<f8": "double", "u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", "comment DSM mesh: east north height, tile %d, tol_units %d" % (
+        int(mesh.get("tile", 0)), int(mesh.get("tol_units", 0))), "element vertex %d" % len(v)]
+    header += ["property %s %s" % (names[kind], name) for name, kind in fields]
+    header += ["element face %d" % len(t), "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
+    return len(t)
+
+
+def write_obj(path, mesh, grid, texcoords=False):
+    """A mesh() dict as a Wavefront OBJ in plain text: `v east north z` with every digit of the float64, then with texcoords
+    `vt col / (gw - 1)  1 - row / (gh - 1)` (the orthophoto on the same grid as the texture image, its first row on top), then
+    `f a b c` or `f a/a b/b c/c`, indices from 1.  Standard library and numpy only.  -> the number of faces."""
+    v, t, xyz = _mesh_host(mesh, grid)
+    gw1, gh1 = max(int(grid.width) - 1, 1), max(int(grid.height) - 1, 1)
+    with open(path, "w") as f:
+        f.write("# DSM mesh: %d vertices, %d faces\n" % (len(v), len(t)))
+        for x, y, z in xyz.tolist():
+            f.write("v %r %r %r\n" % (x, y, z))
+        if texcoords:
+            for col, row in v.tolist():
+                f.write("vt %r %r\n" % (col / gw1, 1.0 - row / gh1))
+        form = "f %d/%d %d/%d %d/%d\n" if texcoords else "f %d %d %d\n"
+        for a, b, c in (t + 1).tolist():
+            f.write(form % ((a, a, b, b, c, c) if texcoords else (a, b, c)))
+    return len(t)
 
 
 # ---- registration: one DSM onto another's grid, the shift between two DSMs, scores and changes ---------------------------------
