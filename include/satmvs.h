@@ -1175,6 +1175,60 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   threshold >= 0; 0 <= n_triangles <= 2 gw gh, 0 <= n_vertices <= gw gh; inputs, outputs and workspace do not overlap;
  *   workspace: smvs_dsm_mesh_workspace_bytes(gw, gh, tile) bytes (0 = unsupported arguments): 14 bytes per cell (two slot pairs
  *   of 4 + 1 bytes and a 4-byte vertex mark) and the scans' block sums. */
+/* Facets ("Facets"): a DSM segmented into planar facets (roof faces, flat ground) and the plane of every
+ *   facet, in exact integers up to the plane's float64 coefficients.
+ *   Heights.  A cell is valid iff it is finite, != (float)nodata and |z| <= 32768; q = rn(256 z), halves to even, in units of
+ *   2^-8 m.  With a mask (uint8, non-zero = inside; may be null) a cell outside the mask is invalid everywhere below.
+ *   Local plane of a cell p: defined only if p and its eight neighbours are on the grid and valid.  Rows grow southwards.
+ *     Gx = (q[NE] + 2 q[E] + q[SE]) - (q[NW] + 2 q[W] + q[SW]),  Gy = (q[SW] + 2 q[S] + q[SE]) - (q[NW] + 2 q[N] + q[NE]),
+ *   8 x the height step per column and per row; both are written as 0 where the local plane is undefined.  p is planar iff
+ *   |8 (q[k] - q[p]) - (Gx dx_k + Gy dy_k)| <= 8 T for each of the eight neighbours k at offset (dx, dy); T = floor(256 tol).
+ *   Adjacency.  Two planar neighbours p and n, (dx, dy) the offset from p to n, are linked iff |Gx_p - Gx_n| <= Ax and
+ *   |Gy_p - Gy_n| <= Ay and |16 (q_n - q_p) - ((Gx_p + Gx_n) dx + (Gy_p + Gy_n) dy)| <= 16 T; neighbours are the 4 or the 8 of
+ *   `connectivity`; Ax = floor(2048 slope_tol xres), Ay = floor(2048 slope_tol yres), slope_tol a difference of tan(slope).
+ *   The test is symmetric in p and n.  (Between two planar cells the third condition cannot fail: its left side is the
+ *   difference of the two cells' planarity residuals towards each other, each at most 8 T.  It is part of the rule all the same.)
+ *   A facet is a class of the transitive closure of links; facets are numbered 1 .. n in
+ *   raster order of their first planar cell (smvs_dsm_label's numbering).  Widths: |q| <= 2^23, so |Gx|, |Gy| <= 2^26, the
+ *   planarity residual is below 2^28 + 2^27 and the link residual below 2^29 + 2^28; with 0 <= T, Ax, Ay <= 2^26 nothing wraps
+ *   in an int32.
+ *   Growth (grow = 1, one round).  A valid cell u that is not planar takes the label of the first of its neighbours p, in
+ *   the order k = 0 .. 7 of E, SE, S, SW, W, NW, N, NE ("Hydrology"), that is planar and has
+ *   |8 (q_u - q_p) - (Gx_p dx + Gy_p dy)| <= 8 T, (dx, dy) the offset from p to u.  Always all eight neighbours; it reads only
+ *   labels and gradients of planar cells and never renumbers.  Everything else gets 0: invalid cells, cells outside the mask,
+ *   non-planar cells that were not grown.
+ *   Known property.  Links are pairwise, so a gently curved surface (a dome, rolling terrain) chains into one facet; its rms
+ *   and max_abs say so, and callers reject by them.  A face needs at least one cell whose whole 3 x 3 window lies in it.
+ * smvs_dsm_facet_normals: Gx, Gy int32 and planar uint8 (gh, gw) of every cell.  One lane per cell, no workspace.
+ * smvs_dsm_facet_label: labels (gh, gw) int32; n_out (device, one int) <- n, or -1 if a union-find loop reached its bound
+ *   (cannot happen on an undamaged labels buffer: every find and union strictly lowers an index with each step).  The
+ *   workspace keeps q, Gx, Gy and the planar flag of every cell, the roots' ranks and the scan's block sums; every word a
+ *   kernel reads was written by a kernel of the same call.  The result depends on the inputs alone: equal bits from run to
+ *   run, on any stream, and to the numpy statement of the rule (tests/dsm_facet_oracle.py).
+ * smvs_dsm_facet_planes: per label k + 1, k = 0 .. n - 1, over the cells of `labels` that carry it and are valid (no mask):
+ *   sums int64 (n, 4): n_k, sum c, sum r, sum q; centre int32 (n, 3): cb = floor(sum c / n_k), rb = floor(sum r / n_k),
+ *   qb = floor(sum q / n_k) (zeros where n_k = 0); with dc = c - cb, dr = r - rb, dq = q - qb, moments int64 (n, 8): the sums
+ *   Sx, Sy, Sz, Sxx, Sxy, Syy, Sxz, Syz of dc, dr, dq, dc^2, dc dr, dr^2, dc dq, dr dq.
+ *   Bound: gw, gh <= 32768 and gw gh < 2^24, so |dc|, |dr| < 2^15 and |dq| <= 2^24: a term is below 2^39 and a sum of fewer
+ *   than 2^24 terms below 2^63.  Larger scenes go through tiles.
+ *   plane float64 (n, 3): a (units per column), b (units per row), h0 (the plane's height at (cb, rb), in units), every
+ *   operation an IEEE double operation by itself (the library is built with -ffp-contract=off), N and the sums converted
+ *   to double first (round to nearest):
+ *     cxx = Sxx - (Sx Sx) / N, cxy = Sxy - (Sx Sy) / N, cyy = Syy - (Sy Sy) / N, cxz = Sxz - (Sx Sz) / N, cyz = Syz - (Sy Sz) / N,
+ *     det = cxx cyy - cxy cxy, a = (cxz cyy - cyz cxy) / det, b = (cyz cxx - cxz cxy) / det,
+ *     h0 = (double)qb + ((Sz / N - a (Sx / N)) - b (Sy / N)).
+ *   !(det > 0) gives NaN for all three: fewer than three cells, or cells on one line.  An 8-connected collinear set is a row,
+ *   a column or a diagonal; for a row or a column Sy = Sxy = Syy = 0 (Sx = Sxy = Sxx = 0), for a diagonal dr = dc and for an
+ *   anti-diagonal dr = -dc or 1 - dc, for which cxx, cyy and |cxy| are the same exactly representable number: det is exactly 0.
+ *   Residuals: e = q - rn((h0 + a dc) + b dr), the sum clamped to +-2^40 before rounding and e to +-2^16; sse int64 (n) = sum
+ *   e^2 and max_abs int32 (n) = max |e|; both 0 for a NaN plane.  Integer atomics only, after a reduction along a wave's rows
+ *   and columns on chip: equal bits from run to run and to the numpy statement, float64 coefficients included.
+ *   n == 0 returns SMVS_OK without a launch.
+ * Limits (SMVS_ERR_ARG with a message, before any HIP call; nothing is written): non-null pointers (mask may be null); gw, gh
+ *   >= 1 and gw gh < 2^31 (planes: the bound above); 0 <= T, Ax, Ay <= 2^26; connectivity 4 or 8; grow 0 or 1; n >= 0; inputs,
+ *   outputs and workspace do not overlap; workspace: smvs_dsm_facet_workspace_bytes(gw, gh) bytes (0 = unsupported arguments),
+ *   17 bytes per cell and the scan's block sums.  Every entry takes a stream, does no host synchronisation and initialises
+ *   every output it owns.  No kernel uses scratch. */
 typedef struct smvs_dsm_layer {
     const float* z;              /* (gh, gw) float32, device */
     const int* d2;               /* (gh, gw) int32, device; may be null outside mode 5 */
@@ -1316,6 +1370,15 @@ int smvs_dsm_mesh_write(const float* dsm, int gw, int gh, int tile, int n_triang
 int smvs_dsm_mesh_heights(const long long* errors, const float* dsm, int gw, int gh, float nodata, int tile,
                           long long threshold, float* heights, long long* dev /* may be null */,
                           void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_facet_workspace_bytes(int gw, int gh);
+int smvs_dsm_facet_normals(const float* dsm, const unsigned char* mask /* may be null */, int gw, int gh, float nodata, int T,
+                           int* Gx, int* Gy, unsigned char* planar, void* stream);
+int smvs_dsm_facet_label(const float* dsm, const unsigned char* mask /* may be null */, int gw, int gh, float nodata,
+                         int T, int Ax, int Ay, int connectivity, int grow, int* labels, int* n_out /* device, 1 */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_facet_planes(const int* labels, const float* dsm, int gw, int gh, float nodata, int n,
+                          long long* sums, int* centre, long long* moments, double* plane, long long* sse, int* max_abs,
+                          void* stream);
 
 /* ---- heights without a network: census plane sweep and semi-global matching (sgm.hip) ----------------
  * Three entries over plane-minor uint16 volumes (B, H, W, D): the D planes of a pixel are contiguous.  1 <= D <= 256 and

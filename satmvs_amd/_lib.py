@@ -127,6 +127,9 @@ _SIGNATURES = {
     "smvs_dsm_mesh_count": [_vp, _vp, _i, _i, _f, _i, C.c_longlong, _vp, _vp, _sz, _vp],
     "smvs_dsm_mesh_write": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_mesh_heights": [_vp, _vp, _i, _i, _f, _i, C.c_longlong, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_facet_normals": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
+    "smvs_dsm_facet_label": [_vp, _vp, _i, _i, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_facet_planes": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "smvs_sgm_census_cost": [_vp, _vp, _i, _i, _f, _vp] + [_i] * 6 + [_vp, _sz, _vp],
     "smvs_sgm_aggregate": [_vp, _vp, _vp] + [_i] * 11 + [_vp],
     "smvs_sgm_select": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp] + [_i] * 4 + [_vp],
@@ -146,6 +149,7 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2,
                "smvs_dsm_stream_workspace_bytes": [_i] * 2, "smvs_dsm_cost_workspace_bytes": [_i] * 2,
                "smvs_dsm_mesh_workspace_bytes": [_i] * 3,
+               "smvs_dsm_facet_workspace_bytes": [_i] * 2,
                "smvs_sgm_census_workspace_bytes": [_i] * 3}
 # host-side queries (no HIP call, no stream) that return a code, or a status beside a plan written to an int[6]: called on load()
 # directly, never through call()

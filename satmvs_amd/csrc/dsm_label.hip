@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "dsm_common.h"
+#include "dsm_unionfind.h"
 #include "smvs_host.h"
 
 namespace smvs {
@@ -33,42 +34,7 @@ constexpr int LABEL_TW = 64, LABEL_TH = 16, LABEL_THREADS = 256;        // a til
 constexpr int SCAN_PER_THREAD = 8, SCAN_BLOCK = LABEL_THREADS * SCAN_PER_THREAD;     // 2048 cells per workgroup
 constexpr int STATS_ROWS = 16;                               // rows of the 64-column strip one wave of the statistics walks down
 
-__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_lds(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// Root of a (LDS == false: across workgroups, every load at agent scope past the CU's L1).  At most a steps.
-template <bool LDS>
-__device__ __forceinline__ int label_find(const int* P, int a, int* err)
-{
-    for (;;) {
-        const int p = LDS ? ld_lds(P + a) : ld_agent(P + a);
-        if (p == a) return a;
-        if (p < 0 || p > a) {                                // not a step down: the array is damaged
-            atomicOr(err, 1);
-            return a;
-        }
-        a = p;
-    }
-}
-
-// Unite the trees of a and b: the higher root goes under the lower.  atomicMin answers what the parent was: the root itself
-// = linked; anything else is lower than a, and the union goes on from there.  At most max(a, b) retries.
-template <bool LDS>
-__device__ __forceinline__ void label_union(int* P, int a, int b, int* err)
-{
-    a = label_find<LDS>(P, a, err);
-    b = label_find<LDS>(P, b, err);
-    while (a != b) {
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(P + a, b);
-        if (old == a) break;
-        if (old < 0 || old > a) {
-            atomicOr(err, 1);
-            break;
-        }
-        a = old;
-    }
-}
+// label_find and label_union (dsm_unionfind.h) are the loops the paragraph above argues about.
 
 // (a) One 64 x 16 tile.  Wave w labels rows w, w + 4, ... : lane = column.
 __global__ __launch_bounds__(LABEL_THREADS)

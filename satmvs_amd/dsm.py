@@ -21,6 +21,12 @@ and the objects that stand on the ground (connected components in scipy.ndimage.
     labels, n = label(above > 10.0, connectivity=4)            # the building block; label_stats(), sieve_labels()
     voids, n_voids = label(~(np.isfinite(dsm) & (dsm != -999.0)))   # the void regions fill_voids could not reach
 
+and the planar faces of those objects, roof by roof (facets in exact integers, a least-squares plane per facet):
+
+    labels, n = facets(dsm, grid, tol=0.25, slope_tol=0.1)     # cells whose 3 x 3 windows are planar, linked pairwise; the rims grown
+    table = facet_planes(labels, n, dsm, grid)                 # plane, slope_deg, aspect_deg, area_m2, surface_m2, rms_m per facet
+    roofs, table = extract_roofs(dsm, above, grid)             # extract_objects -> facets -> facet_planes -> sieve; into outlines()
+
 and their outlines as vector data, one polygon with holes per object, and polygons put back on the grid:
 
     rings = outlines(labels, len(stats["area"]), grid)         # rings of lattice corners: exterior counter-clockwise, holes clockwise
@@ -135,6 +141,9 @@ smvs_dsm_mesh_errors is one lane per lattice vertex over all levels of the bisec
 triangle's plane raised into its split vertex's word by 64-bit integer max atomics (a wave an 8 x 8 block, its lanes combined per
 split vertex first), then one gather pass per level; smvs_dsm_mesh_count / _write flag the emitted triangles per slot of the
 output order and place them by scans; smvs_dsm_mesh_heights walks every vertex down its root triangle by the active flags.
+smvs_dsm_facet_label is smvs_dsm_label's union-find with another adjacency: the 3 x 3 integer gradients of all cells once into the
+workspace, tiles of q, Gx, Gy in LDS, a pair united where its link holds; smvs_dsm_facet_planes reduces int64 moments about
+an integer centre along a wave's rows and columns before its atomics, and fits the plane in float64 in a fixed order.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -792,6 +801,186 @@ def extract_objects(above, grid, min_height=2.5, min_area_m2=50.0, connectivity=
     labels, _, kept = sieve_labels(labels, stats["area"], min_cells)
     stats = {k: t[kept] for k, t in stats.items()}
     return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in stats.items()}
+
+
+# ---- facets: planar faces of a DSM (roofs, flat ground) and their planes ------------------------------------------------------------
+MAX_FACET_TERM = 2 ** 26                                          # T, Ax, Ay: with it no term of the rule wraps an int32
+MAX_FACET_PLANE_SIDE = 32768                                      # facet_planes: gw, gh <= 2^15 and gw gh < 2^24 keep every sum below 2^63
+MAX_FACET_PLANE_CELLS = 2 ** 24
+FACET_MOMENTS = ("Sx", "Sy", "Sz", "Sxx", "Sxy", "Syy", "Sxz", "Syz")
+
+
+def _facet_term(v, name):
+    if not (math.isfinite(v) and 0.0 <= v <= MAX_FACET_TERM):
+        raise ValueError("%s must be in 0 .. 2^26, got %r" % (name, v))
+    return int(math.floor(v))
+
+
+def facet_terms(grid, tol=0.25, slope_tol=0.1):
+    """(T, Ax, Ay) of the facet rule (include/satmvs.h, "Facets"): T = floor(256 tol), tol [m] the distance a cell may lie off its
+    neighbours' plane; Ax = floor(2048 slope_tol xres), Ay = floor(2048 slope_tol yres), slope_tol the difference of tan(slope)
+    two linked cells may have per axis.  The defaults are chosen on a synthetic roof scene, not tuned on real data."""
+    _grid_checked(grid, "grid")
+    tol, slope_tol = float(tol), float(slope_tol)
+    if not (math.isfinite(tol) and tol >= 0.0) or not (math.isfinite(slope_tol) and slope_tol >= 0.0):
+        raise ValueError("tol and slope_tol must be finite and >= 0, got %r, %r" % (tol, slope_tol))
+    return (_facet_term(256.0 * tol, "256 tol"), _facet_term(2048.0 * slope_tol * float(grid.xres), "2048 slope_tol xres"),
+            _facet_term(2048.0 * slope_tol * float(grid.yres), "2048 slope_tol yres"))
+
+
+def _facet_inputs(dsm, grid, mask):
+    """The DSM (float32, never converted) and the mask (or None) on one device, checked before any device work."""
+    dsm = _dsm_bits(dsm)
+    if grid is not None:
+        _on_grid(dsm, _grid_checked(grid, "grid"))
+    if mask is not None:
+        mask = _mask_checked(mask)
+        if tuple(mask.shape) != tuple(dsm.shape):
+            raise ValueError("mask shape %s differs from the DSM's %s" % (tuple(mask.shape), tuple(dsm.shape)))
+        if not isinstance(mask, torch.Tensor):
+            mask = np.not_equal(mask, 0).view(np.uint8)
+    z, as_numpy = _to_device(dsm)
+    m = None
+    if mask is not None:
+        m = (_to_device(mask, dev=z.device)[0] != 0).to(torch.uint8).contiguous()
+    return z, m, as_numpy
+
+
+def local_planes(dsm, grid=None, tol=0.25, mask=None, nodata=-999.0):
+    """The 3 x 3 integer gradient of every cell and whether its window is planar within tol (include/satmvs.h
+    smvs_dsm_facet_normals): heights q = rn(256 z); Gx, Gy int32 = 8 x the height step per column and per row (rows grow
+    southwards) in units of 2^-8 m, 0 where a cell of the window is off the grid, invalid or outside `mask`; planar uint8.
+    -> (Gx, Gy, planar), each (gh, gw); numpy if the DSM came as numpy, device tensors otherwise."""
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol must be finite and >= 0, got %r" % tol)
+    T = _facet_term(256.0 * tol, "256 tol")
+    z, m, as_numpy = _facet_inputs(dsm, grid, mask)
+    gh, gw = z.shape
+    Gx = torch.empty((gh, gw), dtype=torch.int32, device=z.device)
+    Gy = torch.empty_like(Gx)
+    planar = torch.empty((gh, gw), dtype=torch.uint8, device=z.device)
+    _call(z.device, "smvs_dsm_facet_normals", z, m, gw, gh, float(nodata), T, Gx, Gy, planar)
+    return _back(as_numpy, Gx, Gy, planar)
+
+
+def facets(dsm, grid, tol=0.25, slope_tol=0.1, connectivity=8, grow=True, mask=None, nodata=-999.0):
+    """Planar facets of a DSM (include/satmvs.h smvs_dsm_facet_label, DESIGN.md section 9, "Facets"): a cell is planar if its 3
+    x 3 window lies within tol of the window's plane; two planar neighbours are linked if their gradients differ by at most
+    slope_tol per axis and the step between them fits both planes within tol; a facet is a class of the transitive closure of
+    links, numbered 1 .. n in raster order of its first planar cell.  With grow, one round gives a face its rim back: a valid
+    cell that is not planar joins the first neighbouring planar cell whose plane passes within tol of it.  Cells outside `mask`
+    (bool or integer, non-zero = inside) count as invalid.  Links are pairwise, so a gently curved surface chains into one
+    facet: reject by rms_m and max_abs_m of facet_planes().  A face needs a cell whose whole 3 x 3 window lies in it.  Integer
+    arithmetic throughout: the result depends on the inputs alone, bit for bit.
+    -> (labels (gh, gw) int32, n int); labels numpy if the DSM came as numpy, a device tensor otherwise.  Reading n is the one
+    synchronisation."""
+    T, Ax, Ay = facet_terms(grid, tol, slope_tol)
+    connectivity = _connectivity_checked(connectivity)
+    z, m, as_numpy = _facet_inputs(dsm, grid, mask)
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_facet_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported facet labelling: %d x %d cells" % (gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    labels = torch.empty((gh, gw), dtype=torch.int32, device=z.device)
+    n_dev = torch.empty(1, dtype=torch.int32, device=z.device)
+    _call(z.device, "smvs_dsm_facet_label", z, m, gw, gh, float(nodata), T, Ax, Ay, connectivity, int(bool(grow)), labels, n_dev, ws, nbytes)
+    n = int(n_dev.item())
+    if n < 0:
+        raise _lib.SatMVSNativeError("smvs_dsm_facet_label gave up: a union-find loop reached its bound (n = %d)" % n)
+    return _back(as_numpy, labels), n
+
+
+def facet_planes(labels, n, dsm, grid=None, nodata=-999.0):
+    """The least-squares plane of every label 1 .. n over its valid cells (include/satmvs.h smvs_dsm_facet_planes): exact int64
+    moments about an integer centre, the plane in float64 in a fixed operation order, and its residuals.  At most 32768 cells a
+    side and fewer than 2^24 cells (larger scenes go through tiles).  -> dict of arrays of length n, entry k for label k + 1:
+      n_cells int64; sums int64 (n, 3): sum col, sum row, sum q (q = rn(256 z)); centre int32 (n, 2) row, col and centre_q int32,
+      the floors of the means; moments int64 (n, 8): FACET_MOMENTS about the centre; plane float64 (n, 3): a [units per column], b
+      [units per row], h0 [units at the centre], NaN for fewer than three cells or cells on one line; sse int64 and max_abs
+      int32 of e = q - rn(plane), rms_m = sqrt(sse / n_cells) / 256 and max_abs_m (NaN with the plane)
+      with grid: dzde = a / (256 xres), dzdn = -b / (256 yres); slope_deg; aspect_deg in aspect()'s convention (downslope,
+      clockwise from north, NaN where both components are 0); area_m2; surface_m2 = area_m2 sqrt(1 + dzde^2 + dzdn^2); mean_m.
+    Equal bits from run to run.  The dict goes into outlines() / write_geojson() as it is (NaN is written as null).  numpy if the
+    labels came as numpy, device tensors otherwise."""
+    labels = _labels_checked(labels)
+    n = _label_count_checked(n)
+    dsm = _dsm_bits(dsm)
+    if tuple(dsm.shape) != tuple(labels.shape):
+        raise ValueError("dsm shape %s differs from the labels' %s" % (tuple(dsm.shape), tuple(labels.shape)))
+    gh, gw = int(labels.shape[0]), int(labels.shape[1])
+    if gw > MAX_FACET_PLANE_SIDE or gh > MAX_FACET_PLANE_SIDE or gw * gh >= MAX_FACET_PLANE_CELLS:
+        raise ValueError("facet_planes takes at most 32768 cells a side and fewer than 2^24 cells, got %d x %d" % (gh, gw))
+    if grid is not None:
+        _on_grid(labels, _grid_checked(grid, "grid"))
+    lab, as_numpy = _to_device(labels)
+    dev = lab.device
+    z, _ = _to_device(dsm, dev=dev)
+    sums = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    centre = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    moments = torch.empty((n, 8), dtype=torch.int64, device=dev)
+    plane = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    sse = torch.empty(n, dtype=torch.int64, device=dev)
+    max_abs = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        _call(dev, "smvs_dsm_facet_planes", lab, z, gw, gh, float(nodata), n, sums, centre, moments, plane, sse, max_abs)
+    cells = sums[:, 0]
+    nan = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    fitted = ~torch.isnan(plane[:, 2])
+    per_cell = cells.double().clamp(min=1.0)
+    out = {"n_cells": cells, "sums": sums[:, 1:], "centre": torch.stack([centre[:, 1], centre[:, 0]], dim=1), "centre_q": centre[:, 2],
+           "moments": moments, "plane": plane, "sse": sse, "max_abs": max_abs,
+           "rms_m": torch.where(fitted, torch.sqrt(sse.double() / per_cell) / 256.0, nan),
+           "max_abs_m": torch.where(fitted, max_abs.double() / 256.0, nan)}
+    if grid is not None:
+        # tensor divisors: a division by a Python scalar is a multiplication by its rounded reciprocal on the device
+        dzde = plane[:, 0] / torch.full_like(nan, 256.0 * float(grid.xres))
+        dzdn = -plane[:, 1] / torch.full_like(nan, 256.0 * float(grid.yres))
+        asp = torch.rad2deg(torch.atan2(-dzde, -dzdn))
+        asp = torch.where(asp < 0.0, asp + 360.0, asp)
+        asp = torch.where(asp >= 360.0, torch.zeros_like(asp), asp)
+        area = cells.double() * float(grid.xres) * float(grid.yres)
+        out.update({"dzde": dzde, "dzdn": dzdn, "slope_deg": torch.rad2deg(torch.atan(torch.sqrt(dzde * dzde + dzdn * dzdn))),
+                    "aspect_deg": torch.where((dzde == 0.0) & (dzdn == 0.0), nan, asp), "area_m2": area,
+                    "surface_m2": area * torch.sqrt(1.0 + dzde * dzde + dzdn * dzdn),
+                    "mean_m": torch.where(cells > 0, sums[:, 3].double() / per_cell / 256.0, nan)})
+    return {k: _back(as_numpy, t) for k, t in out.items()}
+
+
+def extract_roofs(dsm, above, grid, min_height=2.5, min_area_m2=50.0, facet_min_area_m2=25.0, max_rms=None, tol=0.25, slope_tol=0.1,
+                  nodata=-999.0):
+    """The roof faces of a DSM: extract_objects(above, grid, min_height, min_area_m2) -> facets(dsm, mask = objects > 0) ->
+    facet_planes() -> sieve_labels() at ceil(facet_min_area_m2 / (xres yres)) cells and, with max_rms [m], at rms_m <= max_rms (a
+    facet without a plane goes with it).  `above` is the nDSM of `dsm` (ndsm()).  The defaults are chosen on a synthetic roof
+    scene, not tuned on real data.  -> (labels (gh, gw) int32 with 1 .. n' on the facets that stay, table: the dict of
+    facet_planes(grid=grid) restricted to them, and `object` int32 = the label of extract_objects under each facet's first
+    cell); numpy if the DSM came as numpy, device tensors otherwise."""
+    dsm = _on_grid(_dsm_bits(dsm), _grid_checked(grid, "grid"))
+    facet_terms(grid, tol, slope_tol)                        # rejected here, before any device work
+    facet_min_area_m2 = float(facet_min_area_m2)
+    if not (math.isfinite(facet_min_area_m2) and facet_min_area_m2 >= 0.0):
+        raise ValueError("facet_min_area_m2 must be finite and >= 0, got %r" % facet_min_area_m2)
+    if max_rms is not None:
+        max_rms = float(max_rms)
+        if not (math.isfinite(max_rms) and max_rms >= 0.0):
+            raise ValueError("max_rms must be finite and >= 0, got %r" % max_rms)
+    min_cells = _int_checked(int(math.ceil(facet_min_area_m2 / (float(grid.xres) * float(grid.yres)))), "facet_min_area_m2 in cells", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    a, _ = _to_device(_dsm_bits(above), dev=z.device)
+    objects, _ = extract_objects(a, grid, min_height, min_area_m2, nodata=nodata)
+    labels, n = facets(z, grid, tol, slope_tol, mask=objects > 0, nodata=nodata)
+    table = facet_planes(labels, n, z, grid, nodata)
+    size = table["n_cells"].to(torch.int32)
+    if max_rms is not None:
+        size = torch.where(table["rms_m"] <= max_rms, size, torch.zeros_like(size))
+    labels, _, kept = sieve_labels(labels, size, max(min_cells, 1))
+    table = {k: t[kept] for k, t in table.items()}
+    cell = torch.arange(labels.numel(), dtype=torch.int64, device=z.device)
+    first = torch.full((len(kept) + 1,), labels.numel(), dtype=torch.int64, device=z.device)
+    first.scatter_reduce_(0, labels.reshape(-1).long(), cell, reduce="amin")
+    table["object"] = objects.reshape(-1)[first[1:]] if len(kept) else torch.zeros(0, dtype=torch.int32, device=z.device)
+    return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in table.items()}
 
 
 # ---- outlines: a label map as oriented rings of lattice corners, GeoJSON, and rings burnt back into a label map ---------------
