@@ -668,6 +668,27 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   n >= 0; labels, n_out and workspace distinct from mask and from each other; every statistics output distinct from labels,
  *   values and the other outputs; workspace: smvs_dsm_label_workspace_bytes(gw, gh) bytes (0 = unsupported arguments).
  *
+ * Zonal order statistics (csrc/dsm_zonal.hip).  labels (gh, gw) int32 and values (gh, gw) float32 (device), read only.  A cell
+ *   counts for label k + 1 iff its label is k + 1 with 0 <= k < n and its value is finite and != (float)nodata; labels need not
+ *   be connected: any zone map will do.  Values are ordered by the keys of smvs_dsm_label_stats' vmin / vmax: the
+ *   order-preserving uint32 image of the float32 bits, -0.0 below +0.0.  They are never converted: a result is one of the
+ *   input values with its own bits.
+ * smvs_dsm_label_select: with m_k the number of cells that count for label k + 1, out[k n_ranks + j] (float32) is the value
+ *   whose key is the ranks[k n_ranks + j]-th smallest, 0-based, duplicates counted, among them, and (float)nodata if that rank
+ *   is outside 0 .. m_k - 1.  ranks (n, n_ranks) int32 (device), 1 <= n_ranks <= 8; equal ranks in a row are allowed.
+ *   nvalid[k] (int32, may be null) gets m_k.  Deviation mode: with centre non-null, (n) float32 (device), the selection runs on
+ *   d = (float)fabs((double)v - (double)centre[k]) in place of v: one float64 subtraction, one fabs, one rounding to float32,
+ *   not contracted.  Whether a cell counts is still decided on v (d itself is not held against nodata, and a d that rounds to
+ *   +Inf is selected as such); a label whose centre is not finite has no cell that counts.
+ *   The result depends on the inputs alone: equal bits from run to run, on any stream, for any grouping of ranks into calls,
+ *   and with the numpy statement of this rule (integer atomics only).  The entry initialises all it writes, enqueues 66
+ *   launches for every n_ranks (2 + 2 per key bit), whatever n, the grid and the data, and never reads the device back;
+ *   n == 0 returns SMVS_OK without a launch.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null labels, values, ranks, out and workspace; gw, gh >= 1,
+ *   gw * gh < 2^31; n >= 0; 1 <= n_ranks <= 8; n * n_ranks < 2^28; out, nvalid and workspace distinct from labels, values,
+ *   centre and ranks and from each other; workspace: smvs_dsm_label_select_workspace_bytes(n, n_ranks) bytes (0 = unsupported
+ *   arguments; never 0 for supported ones, n == 0 included).
+ *
  * Registration (csrc/dsm_coreg.hip).  A cell is valid iff it is finite and != (float)nodata, as above.
  * smvs_dsm_shift_stats: a (gha, gwa), the moving grid, and b (ghb, gwb), the fixed one, float32 (device), read only, of equal
  *   cell sizes (the caller's business).  For every shift (sx, sy) in [-radius, radius]^2, cell (r, c) of b is paired with cell
@@ -1265,6 +1286,10 @@ int smvs_dsm_label(const unsigned char* mask, int gw, int gh, int connectivity, 
 int smvs_dsm_label_stats(const int* labels, const float* values, int gw, int gh, float nodata, int n,
                          int* area, int* bbox, long long* rc_sum,
                          int* nvalid, float* vmin, float* vmax, long long* qsum, void* stream);
+size_t smvs_dsm_label_select_workspace_bytes(int n, int n_ranks);
+int smvs_dsm_label_select(const int* labels, const float* values, int gw, int gh, float nodata, int n,
+                          const float* centre /* may be null */, const int* ranks /* device, n x n_ranks */, int n_ranks,
+                          float* out, int* nvalid /* may be null */, void* workspace, size_t workspace_bytes, void* stream);
 size_t smvs_dsm_shift_workspace_bytes(int gwa, int gha, int gwb, int ghb, int radius);
 int smvs_dsm_shift_stats(const float* a, int gwa, int gha, const float* b, int gwb, int ghb, float nodata,
                          int ox, int oy, int radius, double dz0, double trim,

@@ -27,6 +27,12 @@ and the planar faces of those objects, roof by roof (facets in exact integers, a
     table = facet_planes(labels, n, dsm, grid)                 # plane, slope_deg, aspect_deg, area_m2, surface_m2, rms_m per facet
     roofs, table = extract_roofs(dsm, above, grid)             # extract_objects -> facets -> facet_planes -> sieve; into outlines()
 
+and the figures of an object that survive outliers, exact order statistics per label of any zone map:
+
+    per = label_quantiles(labels, n, above, q=(0.5, 0.9))      # n_valid, lo, hi (input values, their own bits), value float64
+    spread = label_nmad(labels, n, above)                      # median, mad, nmad = 1.4826 mad per label
+    score = dsm_metrics_robust(dsm, gt)                        # n, median, nmad, le68, le90, le95; compare_dsms_robust() round a shift
+
 and their outlines as vector data, one polygon with holes per object, and polygons put back on the grid:
 
     rings = outlines(labels, len(stats["area"]), grid)         # rings of lattice corners: exterior counter-clockwise, holes clockwise
@@ -144,6 +150,9 @@ output order and place them by scans; smvs_dsm_mesh_heights walks every vertex d
 smvs_dsm_facet_label is smvs_dsm_label's union-find with another adjacency: the 3 x 3 integer gradients of all cells once into the
 workspace, tiles of q, Gx, Gy in LDS, a pair united where its link holds; smvs_dsm_facet_planes reduces int64 moments about
 an integer centre along a wave's rows and columns before its atomics, and fits the plane in float64 in a fixed order.
+smvs_dsm_label_select is a radix descent over the 32 bits of the order-preserving keys for up to 8 ranks per label at once: a
+counting pass per bit (a ballot per rank where a wave lies inside a zone, runs of lanes with one label elsewhere, the waves of a
+workgroup combined in LDS before the integer atomics) and one lane per (label, rank) that fixes the bit and lowers the rank.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -981,6 +990,196 @@ def extract_roofs(dsm, above, grid, min_height=2.5, min_area_m2=50.0, facet_min_
     first.scatter_reduce_(0, labels.reshape(-1).long(), cell, reduce="amin")
     table["object"] = objects.reshape(-1)[first[1:]] if len(kept) else torch.zeros(0, dtype=torch.int32, device=z.device)
     return _back(as_numpy, labels), {k: _back(as_numpy, t) for k, t in table.items()}
+
+
+# ---- zonal order statistics: medians, percentiles and NMAD per label -------------------------------------------------------------
+MAX_SELECT_RANKS = 8                                              # slots of one smvs_dsm_label_select call
+MAX_SELECT_SLOTS = 2 ** 28                                        # n * n_ranks stays below it
+MAX_QUANTILE_DEN = 1 << 16
+QUANTILE_METHODS = ("linear", "lower", "higher", "midpoint", "nearest")
+NMAD_FACTOR = 1.4826                                              # MAD -> the standard deviation of a normal distribution
+
+
+def _quantile_fractions(q):
+    """The quantile levels as reduced (num, den) pairs: each a Fraction, a (num, den) pair of integers, or a float taken as
+    Fraction(q).limit_denominator(2^16); 0 <= q <= 1 and den <= 2^16 after reduction."""
+    from fractions import Fraction
+    if isinstance(q, (Fraction, float, int, np.floating, np.integer)) and not isinstance(q, bool):
+        q = (q,)
+    if isinstance(q, (np.ndarray, torch.Tensor)):
+        q = [float(v) for v in q.reshape(-1).tolist()]
+    if not isinstance(q, (list, tuple)) or len(q) == 0:
+        raise ValueError("q is a non-empty sequence of quantile levels, got %r" % (q,))
+    out = []
+    for v in q:
+        if isinstance(v, Fraction):
+            f = v
+        elif isinstance(v, (tuple, list)):
+            if len(v) != 2 or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in v) or int(v[1]) <= 0:
+                raise ValueError("a quantile level given as a pair is (num, den) of integers with den > 0, got %r" % (v,))
+            f = Fraction(int(v[0]), int(v[1]))
+        elif isinstance(v, (float, int, np.floating, np.integer)) and not isinstance(v, bool):
+            if not math.isfinite(float(v)):
+                raise ValueError("a quantile level must be finite, got %r" % (v,))
+            f = Fraction(v if isinstance(v, int) else float(v)).limit_denominator(MAX_QUANTILE_DEN)
+        else:
+            raise ValueError("a quantile level is a Fraction, a (num, den) pair or a float, got %r" % (v,))
+        if not 0 <= f <= 1:
+            raise ValueError("a quantile level must be in [0, 1], got %r" % (v,))
+        if f.denominator > MAX_QUANTILE_DEN:
+            raise ValueError("a quantile level's denominator must be at most 2^16 after reduction, got %r" % (v,))
+        out.append((f.numerator, f.denominator))
+    return out
+
+
+def quantile_ranks(n_valid, q):
+    """The two ranks a quantile lies between, in integers: with m = n_valid and q = num / den, h = (m - 1) num (int64),
+    lo = h // den, rem = h % den, hi = lo + (rem > 0): the quantile is the order statistic lo, or lies rem / den of the way to
+    the order statistic hi.  m = 0 gives lo = hi = -1, rem = 0.  n_valid (n) of an integer dtype with 0 <= m < 2^31, numpy or a
+    tensor on any device (no device needed); q as in label_quantiles.
+    -> (lo int32 (n, Q), hi int32 (n, Q), rem int64 (n, Q), den int64 (Q)), of n_valid's kind."""
+    fr = _quantile_fractions(q)
+    is_tensor = isinstance(n_valid, torch.Tensor)
+    m = n_valid if is_tensor else np.asarray(n_valid)
+    integral = not (m.is_floating_point() or m.is_complex() or m.dtype == torch.bool) if is_tensor else np.issubdtype(m.dtype, np.integer)
+    if m.ndim != 1 or not integral:
+        raise ValueError("n_valid is a 1-D integer array, one entry per label, got %s %s" % (m.dtype, tuple(m.shape)))
+    if is_tensor:
+        m64 = m.to(torch.int64)[:, None]
+        num = torch.tensor([f[0] for f in fr], dtype=torch.int64, device=m.device)
+        den = torch.tensor([f[1] for f in fr], dtype=torch.int64, device=m.device)
+        some = m64 > 0
+        h = (m64 - 1).clamp(min=0) * num
+        lo = torch.div(h, den, rounding_mode="floor")
+        rem = h - lo * den
+        hi = lo + (rem > 0)
+        none = torch.full_like(lo, -1)
+        return torch.where(some, lo, none).to(torch.int32), torch.where(some, hi, none).to(torch.int32), rem, den
+    if m.size and (int(m.min()) < 0 or int(m.max()) >= 2 ** 31):
+        raise ValueError("n_valid must be in 0 .. 2^31 - 1")
+    m64 = m.astype(np.int64)[:, None]
+    num = np.array([f[0] for f in fr], dtype=np.int64)
+    den = np.array([f[1] for f in fr], dtype=np.int64)
+    some = m64 > 0
+    h = np.maximum(m64 - 1, 0) * num
+    lo = h // den
+    rem = h - lo * den
+    hi = lo + (rem > 0)
+    return np.where(some, lo, -1).astype(np.int32), np.where(some, hi, -1).astype(np.int32), rem, den
+
+
+def _quantile_value(lo, hi, lo_rank, rem, den, method):
+    """The quantile in float64 from its two order statistics (float32 tensors) by `method`; the operation order is the rule."""
+    a, b = lo.double(), hi.double()
+    if method == "lower":
+        return a
+    if method == "higher":
+        return b
+    if method == "midpoint":
+        return (a + b) * 0.5
+    if method == "nearest":
+        upper = (2 * rem > den) | ((2 * rem == den) & (lo_rank % 2 == 1))       # on a tie the one of even rank
+        return torch.where(upper, b, a)
+    return a + (b - a) * (rem.double() / den.double())                          # tensor divisor: a true division on the device
+
+
+def _label_select(lab, v, n, nodata, centre, ranks):
+    """smvs_dsm_label_select over the columns of ranks (n, S) int32 in chunks of 8 -> out (n, S) float32."""
+    dev = lab.device
+    gh, gw = lab.shape
+    S = int(ranks.shape[1])
+    out = torch.empty((n, S), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    width = min(S, MAX_SELECT_RANKS)
+    nbytes = _lib.load().smvs_dsm_label_select_workspace_bytes(n, width)
+    if nbytes == 0:
+        raise ValueError("unsupported selection: %d labels x %d ranks (n * n_ranks must be below 2^28)" % (n, width))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for s0 in range(0, S, MAX_SELECT_RANKS):
+        r = ranks[:, s0:s0 + MAX_SELECT_RANKS].contiguous()
+        o = torch.empty(r.shape, dtype=torch.float32, device=dev)
+        _call(dev, "smvs_dsm_label_select", lab, v, gw, gh, nodata, n, centre, r, int(r.shape[1]), o, None, ws, nbytes)
+        out[:, s0:s0 + MAX_SELECT_RANKS] = o
+    return out
+
+
+def label_quantiles(labels, n, values, q=(0.5,), method="linear", centre=None, nodata=-999.0):
+    """Exact quantiles of the values under every label 1 .. n (include/satmvs.h smvs_dsm_label_select, DESIGN.md section 9, "Zonal
+    order statistics"): labels (gh, gw) int32, any zone map (label(), facets(), burn_polygons(), a class grid); values (gh, gw)
+    float32, never converted; a cell counts iff its label is in 1 .. n and its value is finite and != nodata.  q: the levels,
+    each a Fraction, a (num, den) pair or a float taken as Fraction(q).limit_denominator(2^16).  With centre ((n) float32) the
+    statistics are those of |value - centre[k]| (float64 difference, rounded to float32 once); a label whose centre is not finite
+    has no cell.  -> dict, entry k for label k + 1:
+      n_valid int32 (n): the cells that count
+      lo, hi float32 (n, Q): the order statistics of quantile_ranks(), input values with their own bits (order: -0.0 below +0.0);
+        nodata where n_valid is 0
+      value float64 (n, Q), NaN where n_valid is 0, by `method`: "linear" lo + (hi - lo) (rem / den), "lower", "higher",
+        "midpoint" (lo + hi) 0.5, "nearest" (the closer rank, on a tie the even one)
+    Selection, no sums: equal bits from run to run.  numpy if the labels came as numpy, device tensors otherwise."""
+    labels = _labels_checked(labels)
+    n = _label_count_checked(n)
+    values = _dsm_bits(values)
+    if tuple(values.shape) != tuple(labels.shape):
+        raise ValueError("values shape %s differs from the labels' %s" % (tuple(values.shape), tuple(labels.shape)))
+    fr = _quantile_fractions(q)
+    if method not in QUANTILE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (QUANTILE_METHODS, method))
+    if centre is not None:
+        if not isinstance(centre, torch.Tensor):
+            centre = np.asarray(centre)
+        if centre.ndim != 1 or int(centre.shape[0]) != n or centre.dtype not in (np.float32, torch.float32):
+            raise ValueError("centre is float32 (n) with n = %d, got %s %s" % (n, centre.dtype, tuple(centre.shape)))
+    if n * min(2 * len(fr), MAX_SELECT_RANKS) >= MAX_SELECT_SLOTS:
+        raise ValueError("too many labels for one selection: n * n_ranks must be below 2^28, got n = %d" % n)
+    lab, as_numpy = _to_device(labels)
+    dev = lab.device
+    v, _ = _to_device(values, dev=dev)
+    c = None if centre is None else _to_device(centre, dev=dev)[0]
+    nd = float(nodata)
+    gh, gw = lab.shape
+    m = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n:                                                    # the cells that count, before any rank can be named
+        area = torch.empty(n, dtype=torch.int32, device=dev)
+        bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        rc = torch.empty((n, 2), dtype=torch.int64, device=dev)
+        vmin = torch.empty(n, dtype=torch.float32, device=dev)
+        vmax = torch.empty_like(vmin)
+        qsum = torch.empty(n, dtype=torch.int64, device=dev)
+        _call(dev, "smvs_dsm_label_stats", lab, v, gw, gh, nd, n, area, bbox, rc, m, vmin, vmax, qsum)
+        if c is not None:
+            m = torch.where(torch.isfinite(c), m, torch.zeros_like(m))
+    lo_rank, hi_rank, rem, den = quantile_ranks(m, fr)
+    split = [f[0] % f[1] != 0 for f in fr]                   # q = 0 and q = 1 never lie between two ranks
+    cols = [lo_rank[:, i] for i in range(len(fr))] + [hi_rank[:, i] for i in range(len(fr)) if split[i]]
+    got = _label_select(lab, v, n, nd, c, torch.stack(cols, dim=1))
+    lo = got[:, :len(fr)].contiguous()
+    hi = lo.clone()
+    at = len(fr)
+    for i in range(len(fr)):
+        if split[i]:
+            hi[:, i] = got[:, at]
+            at += 1
+    value = _quantile_value(lo, hi, lo_rank, rem, den, method)
+    value = torch.where((m > 0)[:, None], value, torch.full_like(value, float("nan")))
+    return {k: _back(as_numpy, t) for k, t in (("n_valid", m), ("lo", lo), ("hi", hi), ("value", value))}
+
+
+def label_nmad(labels, n, values, nodata=-999.0):
+    """The robust centre and spread of the values under every label: median float64 (n), the linear median of
+    label_quantiles(); mad float64, the linear median of |value - float32(median)| (label_quantiles with centre); nmad =
+    1.4826 mad, the standard deviation of a normal distribution with that MAD; n_valid int32.  NaN where n_valid is 0.
+    numpy if the labels came as numpy, device tensors otherwise."""
+    from fractions import Fraction
+    as_numpy = not isinstance(labels, torch.Tensor)
+    half = (Fraction(1, 2),)
+    first = label_quantiles(labels, n, values, half, "linear", None, nodata)
+    median = torch.as_tensor(first["value"])[:, 0]
+    centre = median.to(torch.float32)
+    second = label_quantiles(labels, n, values, half, "linear", centre.numpy() if as_numpy else centre, nodata)
+    mad = torch.as_tensor(second["value"])[:, 0]
+    out = {"median": median, "mad": mad, "nmad": mad * NMAD_FACTOR, "n_valid": torch.as_tensor(first["n_valid"])}
+    return {k: (t.cpu().numpy() if as_numpy else t) for k, t in out.items()}
 
 
 # ---- outlines: a label map as oriented rings of lattice corners, GeoJSON, and rings burnt back into a label map ---------------
@@ -2572,6 +2771,16 @@ def compare_dsms(est, grid_est, gt, grid_gt, register=True, nodata=-999.0, thres
     return {"shift": shift, "before": before, "after": after}
 
 
+def compare_dsms_robust(est, grid_est, gt, grid_gt, register=True, nodata=-999.0, levels=(0.6827, 0.9, 0.95), **coregister_kw):
+    """compare_dsms with dsm_metrics_robust in the place of dsm_metrics: the median error, NMAD and LE68 / LE90 / LE95 of est
+    against gt before and after the registration.  -> {"shift", "before", "after"} as compare_dsms gives them."""
+    _on_grid(gt, grid_gt)
+    plain, moved, shift = _registered(est, grid_est, gt, grid_gt, register, nodata, **coregister_kw)
+    before = dsm_metrics_robust(plain, gt, nodata, levels)
+    after = dsm_metrics_robust(moved, gt, nodata, levels) if register else before
+    return {"shift": shift, "before": before, "after": after}
+
+
 def changes(a, grid_a, b, grid_b, min_dh=2.5, min_area_m2=50.0, register=True, connectivity=8, nodata=-999.0, **coregister_kw):
     """What changed between two epochs: a is registered to b (coregister, unless register=False) and regridded onto grid_b;
     diff = a - b in float32 where both are valid, nodata elsewhere; the rises (diff > min_dh) and the falls (-diff > min_dh)
@@ -3001,6 +3210,32 @@ def dsm_metrics(est, gt, nodata, thresholds=(2.5, 7.5)):
         out["mae"] = out["rmse"] = float("nan")
         for t in thresholds:
             out["<%g" % t] = float("nan")
+    return out
+
+
+def dsm_metrics_robust(est, gt, nodata=-999.0, levels=(0.6827, 0.9, 0.95)):
+    """The accuracy figures that survive outliers, on the device: est and gt on the same grid (any real dtype, taken as
+    float32), a cell compared iff both are finite and != nodata; d = (float)((double)est - (double)gt) there, one zone over
+    the grid, label_quantiles() and label_nmad() on it (so exact order statistics, equal bits from run to run).
+    -> dict of Python numbers: n = the cells compared; median = the linear median of d; nmad = 1.4826 x the linear median of
+    |d - float32(median)|; "le68", "le90", "le95" (a level's key is its rounded percentage) = the linear quantile of |d| at
+    that level.  NaN where n is 0.  A d that is not finite in float32 is not compared.  Reading the figures is the one
+    synchronisation."""
+    fr = _quantile_fractions(levels)
+    e, _ = _to_device(est if isinstance(est, torch.Tensor) else np.asarray(est), torch.float32)
+    g, _ = _to_device(gt if isinstance(gt, torch.Tensor) else np.asarray(gt), torch.float32, e.device)
+    if e.ndim != 2 or e.shape != g.shape:
+        raise ValueError("est and gt are (gh, gw) grids of one shape, got %s and %s" % (tuple(e.shape), tuple(g.shape)))
+    nd = float(np.float32(nodata))
+    both = torch.isfinite(e) & (e != nd) & torch.isfinite(g) & (g != nd)
+    d = (e.double() - g.double()).float()
+    zone = both.to(torch.int32)
+    nan = float("nan")                                       # the zone map says which cells count: no value of d is set aside
+    spread = label_nmad(zone, 1, d, nodata=nan)
+    le = label_quantiles(zone, 1, d, fr, "linear", torch.zeros(1, dtype=torch.float32, device=e.device), nan)
+    out = {"n": int(spread["n_valid"][0]), "median": float(spread["median"][0]), "nmad": float(spread["nmad"][0])}
+    for (num, den), v in zip(fr, le["value"][0].tolist()):
+        out["le%d" % ((200 * num + den) // (2 * den))] = v
     return out
 
 
