@@ -689,6 +689,35 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   centre and ranks and from each other; workspace: smvs_dsm_label_select_workspace_bytes(n, n_ranks) bytes (0 = unsupported
  *   arguments; never 0 for supported ones, n == 0 included).
  *
+ * Focal statistics (csrc/dsm_focal.hip).  dsm (gh, gw) float32 (device), read only.  A cell is valid iff it is finite,
+ *   != (float)nodata and |z| <= 32768; q = llrint((double)z * 256), halves to even: its height in units of 2^-8 m.
+ * smvs_dsm_focal_build: writes one table buffer for the DSM.  It starts with a header of 8 int64 words (256 bytes), written on
+ *   the device: [0] qmin and [1] qmax over the valid cells, [2] n_valid, [3] c = (qmin + qmax) >> 1, the centre heights are
+ *   measured from, [4] D = max(c - qmin, qmax - c), [5 .. 7] 0; with no valid cell all of them are 0.  Behind it, each starting
+ *   on a multiple of 256 bytes, lie three inclusive 2-D prefix tables over (gh + 1) x (gw + 1) entries, entry (y, x) the sum
+ *   over the valid cells (r, c) with r < y and c < x, so row 0 and column 0 are zero and a query never branches at the grid's
+ *   edge: N int32 the count, S1 int64 the sum of d = q - c, S2 uint64 the sum of d^2 MODULO 2^64.  A difference of wrapped
+ *   prefixes is the window's sum modulo 2^64, so it is exact whenever the true sum of the window fits, however far the
+ *   prefixes themselves have wrapped: that is what lets +-32768 m heights on large grids work.  The rest of the buffer is
+ *   working space: the build's band totals and the rectangle list of the latest query.  All sums are integers, the only
+ *   atomics are the integer min / max / add of the range: equal bits from run to run, for any launch geometry, and with the
+ *   numpy statement of this rule.  Seven launches, no read of the device.
+ * smvs_dsm_focal_query: rects is a HOST array of n_rects records {dx0, dx1, dy0, dy1, sign}, bounds inclusive, sign +-1; the
+ *   window of a cell is the signed sum of these rectangles about it (a box is one record, a disc one per run of rows of equal
+ *   half-width, an annulus a disc minus a disc).  Output cell (R, C) of the (oh, ow) result sits at input cell
+ *   (r0 + R sy, c0 + C sx); every rectangle is clipped to the grid per cell, so cells outside add nothing.  Every output may
+ *   be null: n int32, s1 int64, s2 (the low 64 bits) the exact integers of the window; mean and var float64 (device), in this
+ *   order of IEEE operations, not contracted: mean = ((double)c + (double)S1 / (double)n) * 2^-8;
+ *   V = n S2 - S1 S1 as an unsigned 128-bit integer (>= 0 by Cauchy-Schwarz), Vd = (double)(uint64)(V >> 64) * 2^64 +
+ *   (double)(uint64)V, var = Vd / ((double)n * (double)n) * 2^-16, the population variance [m^2]; both NaN where
+ *   n < max(min_valid, 1).  status[0] (device int32) becomes 1 iff W+ D^2 >= 2^63 in 128-bit integers, else 0, W+ the sum of the
+ *   positive rectangles' unclipped areas: the sums may then have wrapped and no result is to be trusted.  The records are
+ *   written into the table buffer's tail by the call, so queries on one buffer belong on one stream at a time.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call, nothing written): non-null dsm, tables, rects, status; gw, gh >= 1,
+ *   (gw + 1) (gh + 1) < 2^31; tables: smvs_dsm_focal_table_bytes(gw, gh) bytes (0 = unsupported sizes), not overlapping dsm;
+ *   1 <= n_rects <= 1024; every offset within +-4096, dx0 <= dx1, dy0 <= dy1, sign +-1; W+ <= 2^24; sx, sy, ow, oh >= 1;
+ *   every output centre inside the grid; min_valid >= 0; the outputs overlap neither each other nor the tables.
+ *
  * Registration (csrc/dsm_coreg.hip).  A cell is valid iff it is finite and != (float)nodata, as above.
  * smvs_dsm_shift_stats: a (gha, gwa), the moving grid, and b (ghb, gwb), the fixed one, float32 (device), read only, of equal
  *   cell sizes (the caller's business).  For every shift (sx, sy) in [-radius, radius]^2, cell (r, c) of b is paired with cell
@@ -1290,6 +1319,12 @@ size_t smvs_dsm_label_select_workspace_bytes(int n, int n_ranks);
 int smvs_dsm_label_select(const int* labels, const float* values, int gw, int gh, float nodata, int n,
                           const float* centre /* may be null */, const int* ranks /* device, n x n_ranks */, int n_ranks,
                           float* out, int* nvalid /* may be null */, void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_focal_table_bytes(int gw, int gh);
+int smvs_dsm_focal_build(const float* dsm, int gw, int gh, float nodata, void* tables, size_t table_bytes, void* stream);
+int smvs_dsm_focal_query(const void* tables, int gw, int gh, const int* rects /* host, n_rects x 5 */, int n_rects,
+                         int ow, int oh, int c0, int r0, int sx, int sy, int min_valid,
+                         int* n, long long* s1, long long* s2, double* mean, double* var /* each may be null */,
+                         int* status, void* stream);
 size_t smvs_dsm_shift_workspace_bytes(int gwa, int gha, int gwb, int ghb, int radius);
 int smvs_dsm_shift_stats(const float* a, int gwa, int gha, const float* b, int gwb, int ghb, float nodata,
                          int ox, int oy, int radius, double dz0, double trim,

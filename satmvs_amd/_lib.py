@@ -93,6 +93,8 @@ _SIGNATURES = {
     "smvs_dsm_label": [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_label_stats": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "smvs_dsm_label_select": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_focal_build": [_vp, _i, _i, _f, _vp, _sz, _vp],
+    "smvs_dsm_focal_query": [_vp, _i, _i, _vp] + [_i] * 8 + [_vp] * 7,
     "smvs_dsm_shift_stats": [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _sz, _vp],
     "smvs_dsm_regrid": [_vp, _i, _i, _vp, _f, _vp, _i, _i, _i, C.c_double, _vp, _vp],
     "smvs_dsm_dist": [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
@@ -142,7 +144,7 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_conv3d_packed_floats": [_i] * 2, "smvs_conv3d_wgrad_workspace_floats": [_i] * 6,
                "smvs_dsm_workspace_bytes": [_sz, _i, _i], "smvs_dsm_fill_workspace_bytes": [_i] * 3,
                "smvs_dsm_morph_workspace_bytes": [_i] * 3, "smvs_dsm_label_workspace_bytes": [_i] * 2,
-               "smvs_dsm_label_select_workspace_bytes": [_i] * 2,
+               "smvs_dsm_label_select_workspace_bytes": [_i] * 2, "smvs_dsm_focal_table_bytes": [_i] * 2,
                "smvs_dsm_shift_workspace_bytes": [_i] * 5, "smvs_dsm_dist_workspace_bytes": [_i] * 3,
                "smvs_dsm_shadow_workspace_bytes": [_i] * 2, "smvs_dsm_horizon_workspace_bytes": [_i] * 3,
                "smvs_dsm_viewshed_workspace_bytes": [_i] * 3,

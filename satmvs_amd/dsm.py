@@ -33,6 +33,14 @@ and the figures of an object that survive outliers, exact order statistics per l
     spread = label_nmad(labels, n, above)                      # median, mad, nmad = 1.4826 mad per label
     score = dsm_metrics_robust(dsm, gt)                        # n, median, nmad, le68, le90, le95; compare_dsms_robust() round a shift
 
+and what the neighbourhood of every cell looks like at any radius, from exact summed-area tables built once per DSM:
+
+    tables = focal_tables(dsm)                                 # one int64 scan per DSM: count, sum and sum of squares in units of 2^-8 m
+    position = tpi(dsm, grid, radius=250.0, tables=tables)     # height minus the mean over a disc; dev() divides by the disc's std
+    rough = roughness(dsm, focal_window("disc", 50.0, grid=grid), tables=tables)   # any window: "box", "disc", "annulus"
+    overview, coarse, count = aggregate(dsm, grid, factor=8)   # block means on the coarser DSMGrid; focal_fraction() for masks
+    landform = slope_position(dtm, grid, radius=250.0)         # valley, lower / middle / upper slope, flat, ridge
+
 and their outlines as vector data, one polygon with holes per object, and polygons put back on the grid:
 
     rings = outlines(labels, len(stats["area"]), grid)         # rings of lattice corners: exterior counter-clockwise, holes clockwise
@@ -153,6 +161,11 @@ an integer centre along a wave's rows and columns before its atomics, and fits t
 smvs_dsm_label_select is a radix descent over the 32 bits of the order-preserving keys for up to 8 ranks per label at once: a
 counting pass per bit (a ballot per rank where a wave lies inside a zone, runs of lanes with one label elsewhere, the waves of a
 workgroup combined in LDS before the integer atomics) and one lane per (label, rank) that fixes the bit and lowers the rank.
+smvs_dsm_focal_build writes the inclusive 2-D prefix tables of the count, of d = q - centre and of d^2 modulo 2^64: a range pass
+(the only atomics, integer), a column pass cut into bands of 16 rows with an exact carry (band totals from the floats, a scan down
+the bands, then the prefixes), and a row pass in place, a workgroup per row in segments of 1024 entries with the carry in registers;
+smvs_dsm_focal_query is one lane per output cell over a window's rectangle records, four corner reads per table and record, the
+variance from an exact 128-bit integer.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1180,6 +1193,291 @@ def label_nmad(labels, n, values, nodata=-999.0):
     mad = torch.as_tensor(second["value"])[:, 0]
     out = {"median": median, "mad": mad, "nmad": mad * NMAD_FACTOR, "n_valid": torch.as_tensor(first["n_valid"])}
     return {k: (t.cpu().numpy() if as_numpy else t) for k, t in out.items()}
+
+
+# ---- focal statistics: exact summed-area tables, any window in O(1) per cell ---------------------------------------------------
+MAX_FOCAL_RECTS = 1024                                            # records of one window
+MAX_FOCAL_OFFSET = 4096                                           # cells a record may reach from the centre
+MAX_FOCAL_AREA = 1 << 24                                          # W+, the cells of a window's positive rectangles
+FOCAL_SHAPES = ("box", "disc", "annulus")
+
+
+@dataclass(frozen=True)
+class FocalWindow:
+    """A window as a signed sum of rectangles: rects (k, 5) int32 records {dx0, dx1, dy0, dy1, sign}, bounds inclusive;
+    cells, the cells of the window; positive, W+, the cells of the records with sign +1 (what the overflow bound counts)."""
+    rects: np.ndarray
+    cells: int
+    positive: int
+
+
+def _half_widths(radius, xres, yres, box=False):
+    """hx[k], k = 0 .. 2 ky, of row dy = k - ky: the largest dx >= 0 that belongs, -1 where none does.  Disc: (dx xres)^2 +
+    (dy yres)^2 <= radius^2 in float64 in that order; box: |dx xres| <= radius and |dy yres| <= radius."""
+    kx, ky = int(radius / xres) + 1, int(radius / yres) + 1
+    if max(kx, ky) > 2 * MAX_FOCAL_OFFSET:                   # the exact test below is quadratic in these
+        raise ValueError("a window reaches at most %d cells from its centre, got radius %r at cells of %r x %r" % (MAX_FOCAL_OFFSET, radius, xres, yres))
+    dx = np.arange(0, kx + 1, dtype=np.float64) * np.float64(xres)
+    dy = np.arange(-ky, ky + 1, dtype=np.float64) * np.float64(yres)
+    if box:
+        inside = (np.abs(dx)[None, :] <= radius) & (np.abs(dy)[:, None] <= radius)
+    else:
+        inside = (dx * dx)[None, :] + (dy * dy)[:, None] <= np.float64(radius) * np.float64(radius)
+    hx = inside.sum(axis=1).astype(np.int64) - 1             # the test is monotone in dx, so the members are 0 .. hx
+    return hx, ky
+
+
+def _disc_records(radius, xres, yres, sign, box=False):
+    hx, ky = _half_widths(radius, xres, yres, box)
+    rows = np.flatnonzero(hx >= 0)
+    if rows.size == 0:
+        return np.zeros((0, 5), dtype=np.int64), 0
+    cells = int((2 * hx[rows] + 1).sum())
+    out = []
+    start = rows[0]
+    for k in range(rows[0], rows[-1] + 1):                   # rows of equal extent side by side are one record
+        if k == rows[-1] or hx[k + 1] != hx[start]:
+            out.append((-hx[start], hx[start], start - ky, k - ky, sign))
+            start = k + 1
+    return np.array(out, dtype=np.int64), cells
+
+
+def _focal_records_checked(rects):
+    r = np.asarray(rects)
+    if r.ndim != 2 or r.shape[1] != 5 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("window records are (k, 5) integers {dx0, dx1, dy0, dy1, sign}, got %s %s" % (r.dtype, tuple(r.shape)))
+    if not 1 <= r.shape[0] <= MAX_FOCAL_RECTS:
+        raise ValueError("a window has 1 .. %d records, got %d" % (MAX_FOCAL_RECTS, r.shape[0]))
+    r = r.astype(np.int64)
+    if np.abs(r[:, :4]).max() > MAX_FOCAL_OFFSET:
+        raise ValueError("a window reaches at most %d cells from its centre" % MAX_FOCAL_OFFSET)
+    if (r[:, 0] > r[:, 1]).any() or (r[:, 2] > r[:, 3]).any() or (np.abs(r[:, 4]) != 1).any():
+        raise ValueError("a window record has dx0 <= dx1, dy0 <= dy1 and sign +1 or -1")
+    area = (r[:, 1] - r[:, 0] + 1) * (r[:, 3] - r[:, 2] + 1)
+    positive = int(area[r[:, 4] > 0].sum())
+    if positive > MAX_FOCAL_AREA:
+        raise ValueError("a window's positive records hold at most 2^24 cells, got %d" % positive)
+    return FocalWindow(np.ascontiguousarray(r, dtype=np.int32), int((area * r[:, 4]).sum()), positive)
+
+
+def focal_window(shape, radius, inner=None, grid=None):
+    """The window of the focal operators as rectangle records (include/satmvs.h smvs_dsm_focal_query): shape "box", "disc" or
+    "annulus"; radius (and inner) in cells without a grid and in metres with one.  Cell (dx, dy) belongs to a disc iff
+    (dx xres)^2 + (dy yres)^2 <= radius^2 in float64 in that order (an ellipse in cells where xres != yres), to a box iff
+    |dx xres| <= radius and |dy yres| <= radius, to an annulus iff it belongs to the disc and (dx xres)^2 + (dy yres)^2 >
+    inner^2: the disc of `radius` minus the disc of `inner`, 0 <= inner < radius.  Rows of equal extent are one record.
+    -> FocalWindow(rects (k, 5) int32, cells, positive = W+).  Host code, numpy only."""
+    if shape not in FOCAL_SHAPES:
+        raise ValueError("shape must be one of %s, got %r" % (FOCAL_SHAPES, shape))
+    radius = _finite(radius, "radius")
+    if radius < 0.0:
+        raise ValueError("radius must be >= 0, got %r" % radius)
+    if (inner is not None) != (shape == "annulus"):
+        raise ValueError("inner goes with the annulus and with it alone")
+    xres, yres = (1.0, 1.0) if grid is None else (float(_grid_checked(grid, "grid").xres), float(grid.yres))
+    rects, _ = _disc_records(radius, xres, yres, 1, box=shape == "box")
+    if shape == "annulus":
+        inner = _finite(inner, "inner")
+        if not 0.0 <= inner < radius:
+            raise ValueError("inner must be in [0, radius), got %r" % inner)
+        rects = np.concatenate([rects, _disc_records(inner, xres, yres, -1)[0]])
+    if rects.shape[0] == 0:
+        raise ValueError("the window holds no cell")
+    return _focal_records_checked(rects)
+
+
+def _window_checked(window):
+    """A FocalWindow as it is (focal_window() has checked it); bare records are checked and counted."""
+    return window if isinstance(window, FocalWindow) else _focal_records_checked(window)
+
+
+class FocalTables:
+    """The summed-area tables of one DSM (focal_tables()): the device buffer, the sizes, and the header read back once: qmin,
+    qmax [2^-8 m], n_valid, centre (the height sums are measured from) and max_abs (D, the largest |q - centre|)."""
+
+    def __init__(self, buffer, width, height, header, as_numpy):
+        self.buffer, self.width, self.height, self.as_numpy = buffer, width, height, as_numpy
+        self.qmin, self.qmax, self.n_valid, self.centre, self.max_abs = (int(v) for v in header[:5])
+
+    def check(self, window):
+        """ValueError where the window's sums may wrap: W+ max_abs^2 >= 2^63, in Python integers; no read of the device."""
+        if window.positive * self.max_abs * self.max_abs >= 2 ** 63:
+            raise ValueError("the window's sums may wrap: %d cells x (%d / 256 m)^2 >= 2^63; take a smaller window or a DSM of a "
+                             "narrower height range" % (window.positive, self.max_abs))
+
+
+def focal_tables(dsm, nodata=-999.0):
+    """The exact summed-area tables of a DSM (include/satmvs.h smvs_dsm_focal_build, DESIGN.md section 9, "Focal statistics"):
+    computed once, they serve any number of windows at any radius in O(1) per cell.  dsm (gh, gw) float32, never converted, with
+    (gw + 1) (gh + 1) < 2^31; a cell is valid iff finite, != nodata and |z| <= 32768.  -> FocalTables (one read of the device:
+    the header)."""
+    dsm = _dsm_bits(dsm)
+    gh, gw = int(dsm.shape[0]), int(dsm.shape[1])
+    if (gw + 1) * (gh + 1) >= 2 ** 31:
+        raise ValueError("focal tables need (gw + 1) (gh + 1) < 2^31, got %d x %d" % (gw, gh))
+    z, as_numpy = _to_device(dsm)
+    nbytes = _lib.load().smvs_dsm_focal_table_bytes(gw, gh)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    _call(z.device, "smvs_dsm_focal_build", z, gw, gh, float(nodata), buf, nbytes)
+    return FocalTables(buf, gw, gh, buf[:64].view(torch.int64).cpu().tolist(), as_numpy)
+
+
+def _focal_query(tables, window, stride=(1, 1), origin=(0, 0), shape=None, min_valid=1, sums=True, moments=True):
+    """One smvs_dsm_focal_query: stride (sy, sx), origin (r0, c0), shape (oh, ow) (None: every centre from the origin on).
+    -> (n, s1, s2, mean, var) device tensors, None where not asked for."""
+    if not isinstance(tables, FocalTables):
+        raise ValueError("tables come from focal_tables(), got %r" % type(tables).__name__)
+    window = _window_checked(window)
+    tables.check(window)
+    sy, sx = _int_pair(stride, "stride")
+    r0, c0 = _int_pair(origin, "origin")
+    gw, gh = tables.width, tables.height
+    if sx < 1 or sy < 1 or not (0 <= r0 < gh and 0 <= c0 < gw):
+        raise ValueError("stride must be >= 1 and the origin a cell of the grid, got stride %r, origin %r" % (stride, origin))
+    oh, ow = ((gh - 1 - r0) // sy + 1, (gw - 1 - c0) // sx + 1) if shape is None else _int_pair(shape, "shape")
+    if oh < 1 or ow < 1 or r0 + (oh - 1) * sy > gh - 1 or c0 + (ow - 1) * sx > gw - 1:
+        raise ValueError("every output centre must lie inside the grid, got shape %r" % ((oh, ow),))
+    min_valid = _int_checked(min_valid, "min_valid", 0, 2 ** 31 - 1)
+    dev = tables.buffer.device
+    new = lambda dtype: torch.empty((oh, ow), dtype=dtype, device=dev)
+    n, s1, s2 = (new(torch.int32), new(torch.int64), new(torch.int64)) if sums else (None, None, None)
+    mean, var = (new(torch.float64), new(torch.float64)) if moments else (None, None)
+    status = torch.empty(1, dtype=torch.int32, device=dev)   # the host check above already answered it: never read
+    _call(dev, "smvs_dsm_focal_query", tables.buffer, gw, gh, window.rects, int(window.rects.shape[0]), ow, oh, c0, r0, sx, sy,
+          min_valid, n, s1, s2, mean, var, status)
+    return n, s1, s2, mean, var
+
+
+def focal_sums(tables, window, stride=(1, 1), origin=(0, 0), shape=None):
+    """The exact integers of every cell's window: n int32 the valid cells, s1 int64 the sum of q - centre, s2 int64 the sum of
+    (q - centre)^2 (below 2^63: focal_tables' check), q the heights in units of 2^-8 m; centre, a Python int.  Output cell
+    (R, C) sits at input cell (origin + (R, C) * stride); rectangles are clipped to the grid.  -> dict; numpy if the tables'
+    DSM came as numpy, device tensors otherwise."""
+    n, s1, s2, _, _ = _focal_query(tables, window, stride, origin, shape, moments=False)
+    out = dict(zip(("n", "s1", "s2"), _back(tables.as_numpy, n, s1, s2)))
+    out["centre"] = tables.centre
+    return out
+
+
+def _focal_tables_of(dsm_or_tables, nodata):
+    return dsm_or_tables if isinstance(dsm_or_tables, FocalTables) else focal_tables(dsm_or_tables, nodata)
+
+
+def _focal_stats(tables, window, min_valid, stride=(1, 1)):
+    n, _, _, mean, var = _focal_query(tables, window, stride, min_valid=min_valid)
+    return n, mean, var
+
+
+def focal_stats(dsm_or_tables, window, min_valid=1, nodata=-999.0):
+    """Mean and spread of every cell's window (smvs_dsm_focal_query): n int32; mean [m] and var [m^2] float64 in the entry's
+    fixed order of operations, the population variance; std = sqrt(var).  NaN where n < max(min_valid, 1).  dsm_or_tables: a
+    DSM (tables are built and dropped) or focal_tables() of one (nodata is then the tables').  -> dict."""
+    tables = _focal_tables_of(dsm_or_tables, nodata)
+    n, mean, var = _focal_stats(tables, window, min_valid)
+    return dict(zip(("n", "mean", "var", "std"), _back(tables.as_numpy, n, mean, var, torch.sqrt(var))))
+
+
+def _focal_valid(z, nodata):
+    return _valid_cells(z, nodata) & (z.abs() <= 32768.0)
+
+
+def _focal_grid(value, keep, nodata):
+    """(float)value where `keep` and the value is a number, nodata elsewhere."""
+    keep = keep & ~torch.isnan(value)
+    return torch.where(keep, value.float(), torch.full(value.shape, float(nodata), dtype=torch.float32, device=value.device))
+
+
+def focal_mean(dsm, window, min_valid=1, nodata=-999.0, tables=None):
+    """The DSM smoothed by a focal mean: (float)mean of focal_stats(), nodata where n < max(min_valid, 1).  tables: focal_tables()
+    of this DSM, to share them between calls.  -> (gh, gw) float32."""
+    tables = tables or focal_tables(dsm, nodata)
+    n, mean, _ = _focal_stats(tables, window, min_valid)
+    return _back(tables.as_numpy, _focal_grid(mean, n >= min_valid, nodata))
+
+
+def roughness(dsm, window, min_valid=1, nodata=-999.0, tables=None):
+    """The standard deviation of the heights in every cell's window [m]: (float)sqrt(var) of focal_stats(), nodata where
+    n < max(min_valid, 1).  -> (gh, gw) float32."""
+    tables = tables or focal_tables(dsm, nodata)
+    n, _, var = _focal_stats(tables, window, min_valid)
+    return _back(tables.as_numpy, _focal_grid(torch.sqrt(var), n >= min_valid, nodata))
+
+
+def _tpi(dsm, grid, radius, inner, min_valid, nodata, tables):
+    _on_grid(_dsm_bits(dsm), _grid_checked(grid, "grid"))
+    window = focal_window("disc" if inner is None else "annulus", radius, inner, grid)
+    tables = tables or focal_tables(dsm, nodata)
+    z, as_numpy = _to_device(dsm, dev=tables.buffer.device)
+    n, mean, var = _focal_stats(tables, window, min_valid)
+    return as_numpy, z.double() - mean, torch.sqrt(var), _focal_valid(z, nodata) & (n >= min_valid)
+
+
+def tpi(dsm, grid, radius, inner=None, min_valid=1, nodata=-999.0, tables=None):
+    """The topographic position index: (float)((double)z - mean) with the mean over a disc of `radius` [m] about the cell, or
+    over the annulus between `inner` and `radius` where inner is given (focal_window()); nodata where the cell itself is invalid
+    or its window holds fewer than max(min_valid, 1) valid cells.  -> (gh, gw) float32."""
+    as_numpy, t, _, keep = _tpi(dsm, grid, radius, inner, min_valid, nodata, tables)
+    return _back(as_numpy, _focal_grid(t, keep, nodata))
+
+
+def dev(dsm, grid, radius, inner=None, min_valid=1, nodata=-999.0, tables=None):
+    """The deviation from mean elevation: (float)(((double)z - mean) / std) over tpi()'s window, the TPI in units of the
+    window's own standard deviation; nodata where tpi() has none and where std is 0.  -> (gh, gw) float32."""
+    as_numpy, t, std, keep = _tpi(dsm, grid, radius, inner, min_valid, nodata, tables)
+    return _back(as_numpy, _focal_grid(t / std, keep & (std > 0.0), nodata))
+
+
+def focal_fraction(mask, window):
+    """The share of set cells among the cells of every cell's window that lie inside the grid: the density of a footprint
+    mask (extract_objects' labels > 0) or of a validity mask.  The mask goes through the same entry as float32 0 / 1; the count
+    of set cells is the integer (s1 + n centre) / 256, the share float64 count / n, NaN where the window holds no cell of the
+    grid.  mask (gh, gw) bool or uint8.  -> (gh, gw) float64."""
+    m, as_numpy = _to_device(_mask_checked(mask))
+    tables = focal_tables((m != 0).float())
+    n, s1, _, _, _ = _focal_query(tables, window, moments=False)
+    n = n.to(torch.int64)
+    count = (s1 + n * tables.centre) >> 8
+    return _back(as_numpy, torch.where(n > 0, count.double() / n.double(), torch.full_like(count, float("nan"), dtype=torch.float64)))
+
+
+def aggregate(dsm, grid, factor, min_valid=1, nodata=-999.0):
+    """A block-averaged overview: cell (R, C) of the result is the focal mean over the factor x factor block whose upper-left
+    cell is (R factor, C factor) (the strided query with the rectangle [0, factor - 1]^2), nodata where the block holds fewer
+    than max(min_valid, 1) valid cells; a last partial block is kept and clipped.  The new grid's cell (0, 0) has its centre
+    (factor - 1) / 2 cells east and south of the old one's and the resolution is multiplied by factor.
+    -> (dsm (ceil(gh / factor), ceil(gw / factor)) float32, DSMGrid, count int32)."""
+    _on_grid(_dsm_bits(dsm), _grid_checked(grid, "grid"))
+    f = _int_checked(factor, "factor", 1, MAX_FOCAL_OFFSET + 1)
+    tables = focal_tables(dsm, nodata)
+    n, _, _, mean, _ = _focal_query(tables, np.array([[0, f - 1, 0, f - 1, 1]], dtype=np.int32), (f, f), min_valid=min_valid)
+    coarse = DSMGrid(grid.e0 + 0.5 * (f - 1) * grid.xres, grid.n0 - 0.5 * (f - 1) * grid.yres, grid.xres * f, grid.yres * f,
+                     int(n.shape[1]), int(n.shape[0]))
+    out, count = _back(tables.as_numpy, _focal_grid(mean, n >= min_valid, nodata), n)
+    return out, coarse, count
+
+
+SLOPE_POSITIONS = ("no data", "valley", "lower slope", "flat", "middle slope", "upper slope", "ridge")
+
+
+def slope_position(dsm, grid, radius, slope_deg=5.0, min_valid=1, nodata=-999.0):
+    """Weiss' six slope positions from dev() over a disc of `radius` [m] and slope(): uint8 0 no data (dev or slope has none),
+    1 valley (dev <= -1), 2 lower slope (-1 < dev <= -0.5), 3 flat (-0.5 < dev < 0.5, slope <= slope_deg), 4 middle slope
+    (the same band, steeper), 5 upper slope (0.5 <= dev < 1), 6 ridge (dev >= 1).  dev() standardises LOCALLY, by the
+    standard deviation of each cell's own window, where Weiss standardises the TPI by its standard deviation over the whole
+    grid.  The defaults were chosen for 5 m grids on the synthetic scene; they are not tuned on real data.
+    -> (gh, gw) uint8."""
+    slope_deg = _finite(slope_deg, "slope_deg")
+    as_numpy, t, std, keep = _tpi(dsm, grid, radius, None, min_valid, nodata, None)
+    d = (t / std).float()
+    s, _ = _to_device(slope(dsm, grid, nodata), dev=d.device)
+    cls = torch.full(d.shape, 3, dtype=torch.uint8, device=d.device)
+    cls[s > slope_deg] = 4
+    cls[d <= -0.5] = 2
+    cls[d <= -1.0] = 1
+    cls[d >= 0.5] = 5
+    cls[d >= 1.0] = 6
+    cls[~(keep & (std > 0.0)) | torch.isnan(d) | torch.isnan(s)] = 0
+    return _back(as_numpy, cls)
 
 
 # ---- outlines: a label map as oriented rings of lattice corners, GeoJSON, and rings burnt back into a label map ---------------
