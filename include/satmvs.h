@@ -718,6 +718,33 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   1 <= n_rects <= 1024; every offset within +-4096, dx0 <= dx1, dy0 <= dy1, sign +-1; W+ <= 2^24; sx, sy, ow, oh >= 1;
  *   every output centre inside the grid; min_valid >= 0; the outputs overlap neither each other nor the tables.
  *
+ * Focal order statistics (csrc/dsm_rank.hip).  dsm (gh, gw) float32 (device), read only.  Cells and order are those of the zonal
+ *   order statistics: a cell is valid iff it is finite and != (float)nodata; values are ordered by the order-preserving uint32
+ *   image of their bits, -0.0 below +0.0; they are never converted: a selected value is one of the input values with its own
+ *   bits.  runs is a HOST array of n_runs records {dy, dx0, dx1}, bounds inclusive: the window of cell (r, c) is the SET of the
+ *   cells (r + dy, c + dx), dx0 <= dx <= dx1, over all records (no signs: an annulus is two runs a row), clipped at the grid, so
+ *   cells outside add nothing.  The records travel in the kernel's arguments: no workspace, no buffer tail, and calls with
+ *   different windows may run on different streams at once.
+ * smvs_dsm_focal_select: levels is a HOST array of n_levels pairs (num, den).  For every cell p, n = the number of valid cells
+ *   of p's window, and for level j, in integers as dsm.quantile_ranks states them: h = (n - 1) num, lo_rank = h / den,
+ *   hi_rank = lo_rank + (h % den > 0).  lo[j][p] and hi[j][p], float32 (n_levels, gh, gw), are the order statistics of those
+ *   0-based ranks among the window's valid cells, duplicates counted; both are (float)nodata where n = 0.  n_out (int32
+ *   (gh, gw)) gets n; n_out and hi may be null.  Deviation mode: with centre non-null, (gh, gw) float32 (device), the selection
+ *   at p runs on d = (float)fabs((double)v - (double)centre[p]): one float64 subtraction, one fabs, one rounding, not
+ *   contracted.  Validity is still decided on v (a d that rounds to +Inf is selected as such); a p whose centre is not finite
+ *   has n = 0.
+ * smvs_dsm_focal_count: t (gh, gw) float32 (device), a threshold per cell.  below[p] is the number of valid cells of p's window
+ *   whose key is below key(t[p]), equal[p] the number whose key equals it, both int32, both -1 where t[p] is a NaN; n_out as
+ *   above.  t may be dsm itself (the elevation percentile of a cell in its neighbourhood); with t a selected value it gives that
+ *   value's certificate, below <= rank < below + equal.
+ *   No atomics, every result a selection or a count: equal bits from run to run, on any stream, for any launch geometry, and
+ *   with the numpy statement of this rule.  One launch per call over tiles of SMVS_DSM_RANK_TILE x SMVS_DSM_RANK_TILE cells;
+ *   neither entry reads the device back.
+ * Limits (SMVS_ERR_ARG, checked before any HIP call, nothing written): non-null dsm, runs, levels, lo (select); dsm, runs, t,
+ *   below, equal (count); gw, gh >= 1, gw * gh < 2^31; 1 <= n_runs <= 130; every offset within +-32; dx0 <= dx1; runs sorted by
+ *   (dy, dx0), the runs of one row disjoint and not touching; 1 <= n_levels <= 4; 0 <= num <= den, 1 <= den <= 2^16; the
+ *   outputs distinct from the inputs and from each other.
+ *
  * Registration (csrc/dsm_coreg.hip).  A cell is valid iff it is finite and != (float)nodata, as above.
  * smvs_dsm_shift_stats: a (gha, gwa), the moving grid, and b (ghb, gwb), the fixed one, float32 (device), read only, of equal
  *   cell sizes (the caller's business).  For every shift (sx, sy) in [-radius, radius]^2, cell (r, c) of b is paired with cell
@@ -1325,6 +1352,12 @@ int smvs_dsm_focal_query(const void* tables, int gw, int gh, const int* rects /*
                          int ow, int oh, int c0, int r0, int sx, int sy, int min_valid,
                          int* n, long long* s1, long long* s2, double* mean, double* var /* each may be null */,
                          int* status, void* stream);
+#define SMVS_DSM_RANK_TILE 32 /* side of the square tile of output cells one workgroup of the focal order statistics owns */
+int smvs_dsm_focal_select(const float* dsm, int gw, int gh, float nodata, const int* runs /* host, n_runs x 3 */, int n_runs,
+                          const int* levels /* host, n_levels x 2 */, int n_levels, const float* centre /* may be null */,
+                          int* n_out /* may be null */, float* lo, float* hi /* may be null */, void* stream);
+int smvs_dsm_focal_count(const float* dsm, int gw, int gh, float nodata, const int* runs /* host, n_runs x 3 */, int n_runs,
+                         const float* t, int* n_out /* may be null */, int* below, int* equal, void* stream);
 size_t smvs_dsm_shift_workspace_bytes(int gwa, int gha, int gwb, int ghb, int radius);
 int smvs_dsm_shift_stats(const float* a, int gwa, int gha, const float* b, int gwb, int ghb, float nodata,
                          int ox, int oy, int radius, double dz0, double trim,

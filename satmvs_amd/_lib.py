@@ -95,6 +95,8 @@ _SIGNATURES = {
     "smvs_dsm_label_select": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_focal_build": [_vp, _i, _i, _f, _vp, _sz, _vp],
     "smvs_dsm_focal_query": [_vp, _i, _i, _vp] + [_i] * 8 + [_vp] * 7,
+    "smvs_dsm_focal_select": [_vp, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "smvs_dsm_focal_count": [_vp, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "smvs_dsm_shift_stats": [_vp, _i, _i, _vp, _i, _i, _f, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _sz, _vp],
     "smvs_dsm_regrid": [_vp, _i, _i, _vp, _f, _vp, _i, _i, _i, C.c_double, _vp, _vp],
     "smvs_dsm_dist": [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp],

@@ -41,6 +41,12 @@ and what the neighbourhood of every cell looks like at any radius, from exact su
     overview, coarse, count = aggregate(dsm, grid, factor=8)   # block means on the coarser DSMGrid; focal_fraction() for masks
     landform = slope_position(dtm, grid, radius=250.0)         # valley, lower / middle / upper slope, flat, ridge
 
+and what no sum can say about it, exact selections within a window of up to +-32 cells:
+
+    smooth = focal_median(dsm, focal_window("disc", 50.0, grid=grid))   # edge-preserving; focal_quantiles() for any level
+    clean = despike_robust(dsm, focal_window("box", 7))        # |z - median| > max(3 nmad, 0.5 m) of focal_nmad() -> nodata
+    share = elevation_percentile(dsm, focal_window("disc", 100.0, grid=grid))   # the cell's rank in its window, 0 .. 1
+
 and their outlines as vector data, one polygon with holes per object, and polygons put back on the grid:
 
     rings = outlines(labels, len(stats["area"]), grid)         # rings of lattice corners: exterior counter-clockwise, holes clockwise
@@ -166,6 +172,8 @@ smvs_dsm_focal_build writes the inclusive 2-D prefix tables of the count, of d =
 the bands, then the prefixes), and a row pass in place, a workgroup per row in segments of 1024 entries with the carry in registers;
 smvs_dsm_focal_query is one lane per output cell over a window's rectangle records, four corner reads per table and record, the
 variance from an exact 128-bit integer.
+smvs_dsm_focal_select stages a 32 x 32 tile and its window's reach as keys in LDS, the window's row runs in the kernel arguments;
+every lane then runs a radix descent over its own window, counting from LDS; smvs_dsm_focal_count is one counting pass of the same.
 smvs_dsm_shift_stats pairs every cell with its partner under every shift of a square, tiles of both grids in LDS and the
 shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination cell.
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
@@ -1478,6 +1486,194 @@ def slope_position(dsm, grid, radius, slope_deg=5.0, min_valid=1, nodata=-999.0)
     cls[d >= 1.0] = 6
     cls[~(keep & (std > 0.0)) | torch.isnan(d) | torch.isnan(s)] = 0
     return _back(as_numpy, cls)
+
+
+# ---- focal order statistics: exact moving-window medians, quantiles and counts --------------------------------------------------
+MAX_RANK_RUNS = 130                                               # row runs of one window: two a row at +-32 rows
+MAX_RANK_OFFSET = 32                                              # cells a window may reach from its centre
+MAX_RANK_LEVELS = 4                                               # levels of one smvs_dsm_focal_select call
+RANK_TILE = 32                                                    # SMVS_DSM_RANK_TILE of include/satmvs.h
+
+
+def _window_runs(window):
+    """The window of the focal order statistics as row runs (include/satmvs.h smvs_dsm_focal_select): (k, 3) int32 records
+    {dy, dx0, dx1}, bounds inclusive, sorted by (dy, dx0), the runs of a row neither overlapping nor touching.  window: a
+    FocalWindow (focal_window(): its signed rectangles are rasterised here on the host, and every cell's coverage must come out
+    0 or 1, so box, disc and annulus hold exactly focal_window's cells), bare rectangle records, or a 2-D boolean footprint of
+    odd sizes about its middle cell.  A window reaches at most 32 cells from its centre and has at most 130 runs."""
+    if isinstance(window, FocalWindow) or not (isinstance(window, (np.ndarray, torch.Tensor)) and window.dtype in (np.bool_, torch.bool)):
+        rects = _window_checked(window).rects.astype(np.int64)
+        reach = int(np.abs(rects[:, :4]).max())
+        if reach > MAX_RANK_OFFSET:
+            raise ValueError("a window of the focal order statistics reaches at most %d cells from its centre, got %d" % (MAX_RANK_OFFSET, reach))
+        cover = np.zeros((2 * reach + 1, 2 * reach + 1), dtype=np.int64)
+        for dx0, dx1, dy0, dy1, sign in rects:
+            cover[dy0 + reach:dy1 + reach + 1, dx0 + reach:dx1 + reach + 1] += sign
+        if cover.min() < 0 or cover.max() > 1:
+            raise ValueError("the window's signed rectangles must cover every cell 0 or 1 times, got a coverage of %d"
+                             % (cover.max() if cover.max() > 1 else cover.min()))
+        foot = cover == 1
+    else:
+        foot = window.cpu().numpy() if isinstance(window, torch.Tensor) else window
+        if foot.ndim != 2 or foot.shape[0] % 2 != 1 or foot.shape[1] % 2 != 1:
+            raise ValueError("a footprint is a 2-D boolean array of odd sizes, got shape %s" % (tuple(foot.shape),))
+        if max(foot.shape) // 2 > MAX_RANK_OFFSET and (np.abs(np.argwhere(foot) - np.array(foot.shape) // 2) > MAX_RANK_OFFSET).any():
+            raise ValueError("a window of the focal order statistics reaches at most %d cells from its centre" % MAX_RANK_OFFSET)
+    ky, kx = foot.shape[0] // 2, foot.shape[1] // 2
+    runs = []
+    for row in range(foot.shape[0]):
+        edge = np.diff(np.concatenate([[0], foot[row].astype(np.int8), [0]]))
+        for x0, x1 in zip(np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)):
+            runs.append((row - ky, x0 - kx, x1 - 1 - kx))
+    if not 1 <= len(runs) <= MAX_RANK_RUNS:
+        raise ValueError("a window of the focal order statistics has 1 .. %d row runs, got %d" % (MAX_RANK_RUNS, len(runs)))
+    return np.array(runs, dtype=np.int32)
+
+
+def _rank_grid(a, name, like):
+    """A float32 grid of the DSM's shape, never converted."""
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+    if tuple(a.shape) != tuple(like.shape) or a.dtype not in (np.float32, torch.float32):
+        raise ValueError("%s is float32 of the DSM's shape %s, got %s %s" % (name, tuple(like.shape), a.dtype, tuple(a.shape)))
+    return a
+
+
+def _focal_select(z, runs, nodata, fr, centre):
+    """smvs_dsm_focal_select over the levels fr in chunks of 4 -> n int32 (gh, gw), lo, hi float32 (Q, gh, gw).  A chunk without
+    a level between two ranks (num % den == 0 throughout) asks for no hi: it is lo."""
+    gh, gw = z.shape
+    n = torch.empty((gh, gw), dtype=torch.int32, device=z.device)
+    lo = torch.empty((len(fr), gh, gw), dtype=torch.float32, device=z.device)
+    hi = torch.empty_like(lo)
+    for s0 in range(0, len(fr), MAX_RANK_LEVELS):
+        chunk = fr[s0:s0 + MAX_RANK_LEVELS]
+        split = any(num % den != 0 for num, den in chunk)
+        _call(z.device, "smvs_dsm_focal_select", z, gw, gh, nodata, runs, int(runs.shape[0]), np.array(chunk, dtype=np.int32), len(chunk),
+              centre, n if s0 == 0 else None, lo[s0:s0 + len(chunk)], hi[s0:s0 + len(chunk)] if split else None)
+        if not split:
+            hi[s0:s0 + len(chunk)] = lo[s0:s0 + len(chunk)]
+    return n, lo, hi
+
+
+def _focal_quantiles(z, runs, fr, method, centre, min_valid, nodata):
+    n, lo, hi = _focal_select(z, runs, nodata, fr, centre)
+    lo_rank, _, rem, den = quantile_ranks(n.reshape(-1), fr)
+    grids = lambda t: t.t().reshape(lo.shape)                # (cells, Q) -> (Q, gh, gw)
+    value = _quantile_value(lo, hi, grids(lo_rank), grids(rem), den[:, None, None], method)
+    value = torch.where((n >= max(min_valid, 1))[None], value, torch.full_like(value, float("nan")))
+    return n, lo, hi, value
+
+
+def focal_quantiles(dsm, window, q=(0.5,), method="linear", centre=None, min_valid=1, nodata=-999.0):
+    """Exact quantiles of the heights in every cell's window (include/satmvs.h smvs_dsm_focal_select, DESIGN.md section 9, "Focal
+    order statistics"): dsm (gh, gw) float32, never converted; a cell is valid iff finite and != nodata; window as _window_runs()
+    takes it, clipped at the grid.  q, method: as in label_quantiles().  With centre ((gh, gw) float32) the statistics at cell p
+    are those of |v - centre[p]| (float64 difference, rounded to float32 once); a p whose centre is not finite has no cell.
+    -> dict: n_valid int32 (gh, gw), the valid cells of the window; lo, hi float32 (Q, gh, gw), the order statistics of
+    quantile_ranks(), input values with their own bits, nodata where n_valid is 0; value float64 (Q, gh, gw) by `method`, NaN
+    where n_valid < max(min_valid, 1).  Selection, no sums: equal bits from run to run.  numpy if the DSM came as numpy."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    fr = _quantile_fractions(q)
+    if method not in QUANTILE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (QUANTILE_METHODS, method))
+    if centre is not None:
+        centre = _rank_grid(centre, "centre", dsm)
+    min_valid = _int_checked(min_valid, "min_valid", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    c = None if centre is None else _to_device(centre, dev=z.device)[0]
+    n, lo, hi, value = _focal_quantiles(z, runs, fr, method, c, min_valid, float(nodata))
+    return {k: _back(as_numpy, t) for k, t in (("n_valid", n), ("lo", lo), ("hi", hi), ("value", value))}
+
+
+def focal_median(dsm, window, min_valid=1, nodata=-999.0, fill=False):
+    """The DSM under a median filter of any window within +-32 cells: a valid cell becomes (float) of the "midpoint" median of its
+    window's valid cells, despike()'s median: v[n / 2] of the sorted values, or (float)(0.5 ((double)v[n / 2 - 1] +
+    (double)v[n / 2])) for even n; nodata where the window holds fewer than max(min_valid, 1) valid cells.  Invalid cells keep
+    their bits; with `fill` they are treated like the valid ones.  -> (gh, gw) float32."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    min_valid = _int_checked(min_valid, "min_valid", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    n, _, _, value = _focal_quantiles(z, runs, [(1, 2)], "midpoint", None, min_valid, float(nodata))
+    out = _focal_grid(value[0], n >= max(min_valid, 1), nodata)
+    return _back(as_numpy, out if fill else torch.where(_valid_cells(z, nodata), out, z))
+
+
+def _focal_nmad(z, runs, min_valid, nodata):
+    n, _, _, median = _focal_quantiles(z, runs, [(1, 2)], "linear", None, min_valid, nodata)
+    _, _, _, mad = _focal_quantiles(z, runs, [(1, 2)], "linear", median[0].float(), min_valid, nodata)
+    return n, median[0], mad[0]
+
+
+def focal_nmad(dsm, window, min_valid=1, nodata=-999.0):
+    """The robust centre and spread of every cell's window, label_nmad() about a cell: median float64 (gh, gw), the linear median
+    of focal_quantiles(); mad, the linear median of |v - float32(median)| over the same window; nmad = 1.4826 mad; n_valid
+    int32.  NaN where n_valid < max(min_valid, 1).  -> dict."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    min_valid = _int_checked(min_valid, "min_valid", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    n, median, mad = _focal_nmad(z, runs, min_valid, float(nodata))
+    return dict(zip(("median", "mad", "nmad", "n_valid"), _back(as_numpy, median, mad, mad * NMAD_FACTOR, n)))
+
+
+def despike_robust(dsm, window, k=3.0, floor=0.5, min_valid=3, nodata=-999.0, return_removed=False):
+    """despike() beyond its 7 x 7 window and with a threshold the neighbourhood sets itself: a valid cell becomes nodata iff its
+    window holds fewer than min_valid valid cells or |(double)z - median| > max(k nmad, floor), median and nmad from
+    focal_nmad() (floor [m] keeps flat ground, where nmad is 0, from losing every cell).  Every other cell is copied bit for bit.
+    -> the cleaned (gh, gw) float32 (and, with return_removed, a uint8 map of the removed cells)."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    k, floor = _finite(k, "k"), _finite(floor, "floor")
+    if k < 0.0 or floor < 0.0:
+        raise ValueError("k and floor must be >= 0, got %r and %r" % (k, floor))
+    min_valid = _int_checked(min_valid, "min_valid", 1, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    n, median, mad = _focal_nmad(z, runs, min_valid, float(nodata))
+    far = (z.double() - median).abs() > torch.clamp(k * (mad * NMAD_FACTOR), min=floor)
+    removed = _valid_cells(z, nodata) & ((n < min_valid) | far)
+    out = torch.where(removed, torch.full_like(z, float(nodata)), z)
+    out, removed = _back(as_numpy, out, removed.to(torch.uint8))
+    return (out, removed) if return_removed else out
+
+
+def _focal_counts(z, runs, t, nodata):
+    gh, gw = z.shape
+    n, below, equal = (torch.empty((gh, gw), dtype=torch.int32, device=z.device) for _ in range(3))
+    _call(z.device, "smvs_dsm_focal_count", z, gw, gh, nodata, runs, int(runs.shape[0]), t, n, below, equal)
+    return n, below, equal
+
+
+def focal_counts(dsm, window, threshold=None, nodata=-999.0):
+    """Where a threshold stands among the valid cells of every cell's window (include/satmvs.h smvs_dsm_focal_count): n the
+    valid cells, below those under the threshold in the order of the keys (-0.0 below +0.0), equal those with its bits' key;
+    int32 (gh, gw) each, below and equal -1 where the threshold is a NaN.  threshold: None = the cell's own height, a number, or
+    a (gh, gw) float32 grid (a selected value: below <= rank < below + equal certifies it).  -> (n, below, equal)."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    number = isinstance(threshold, (int, float, np.floating, np.integer)) and not isinstance(threshold, bool)
+    if threshold is not None and not number:
+        threshold = _rank_grid(threshold, "threshold", dsm)
+    z, as_numpy = _to_device(dsm)
+    t = z if threshold is None else torch.full_like(z, float(threshold)) if number else _to_device(threshold, dev=z.device)[0]
+    return _back(as_numpy, *_focal_counts(z, runs, t, float(nodata)))
+
+
+def elevation_percentile(dsm, window, min_valid=2, nodata=-999.0):
+    """The share of a cell's neighbourhood that lies below it, the robust counterpart of tpi() and dev(): at a valid cell whose
+    window holds n >= max(min_valid, 2) valid cells, (below + 0.5 (equal - 1)) / (n - 1) with focal_counts() at the cell's own
+    height: 0 at the lowest cell of its window, 1 at the highest, ties share the middle of their ranks.  NaN elsewhere.
+    -> (gh, gw) float64."""
+    dsm = _dsm_bits(dsm)
+    runs = _window_runs(window)
+    min_valid = _int_checked(min_valid, "min_valid", 0, 2 ** 31 - 1)
+    z, as_numpy = _to_device(dsm)
+    n, below, equal = _focal_counts(z, runs, z, float(nodata))
+    share = (below.double() + 0.5 * (equal.double() - 1.0)) / (n.double() - 1.0)
+    keep = _valid_cells(z, nodata) & (n >= max(min_valid, 2))
+    return _back(as_numpy, torch.where(keep, share, torch.full_like(share, float("nan"))))
 
 
 # ---- outlines: a label map as oriented rings of lattice corners, GeoJSON, and rings burnt back into a label map ---------------
