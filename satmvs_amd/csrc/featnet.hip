@@ -342,13 +342,14 @@ SMVS_EXPORT int smvs_featnet_pack_weights(const float* const* params, int base_c
     FnLayer L[FN_NL];
     const int nl = fn_layers(base_channels, arch, L);
     const FnLayout lay = fn_layout(base_channels, arch);
+    for (int i = 0; i < nl; ++i)                // before the first launch: a refused call leaves `packed` as it was
+        if (L[i].cout > 64) return fail(SMVS_ERR_UNSUPPORTED, "base_channels %d too large for the BatchNorm fold kernel", base_channels);
     // execution-order layer -> index of its first pointer
     const int first_unet[15] = {0, 5, 10, 15, 20, 25, 30, 35, 60, 40, 45, 61, 50, 55, 62};
     const int first_fpn[13] = {0, 5, 10, 15, 20, 25, 30, 35, 40, 41, 43, 44, 46};
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < nl; ++i) {
         const float* const* q = params + (arch == 0 ? first_unet[i] : first_fpn[i]);
-        if (L[i].cout > 64) return fail(SMVS_ERR_UNSUPPORTED, "base_channels %d too large for the BatchNorm fold kernel", base_channels);
         const int n = (int)fn_packed_conv(L[i].cin, L[i].cout, L[i].k);
         hipLaunchKernelGGL(fn_pack_conv_kernel, dim3((n + 255) / 256), dim3(256), 0, st, q[0], packed + lay.w[i],
                            L[i].cin, L[i].cout, L[i].k, L[i].transposed);

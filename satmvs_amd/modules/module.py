@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import threading
 
 import torch
@@ -101,6 +102,25 @@ def _workspace(module, attr, nbytes, dev):
 def _autograd_needed(x, tensors):
     """True when a gradient could be asked of this call: the native kernels are forward-only."""
     return torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors))
+
+
+def _f32(v):
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+_NATIVE_NORM_EPS = 1e-5       # the eps the native inference kernels fold (featnet.hip, costreg.hip, red.hip)
+
+
+def _norm_eps_native(module):
+    """True when every BatchNorm / GroupNorm of `module` carries the eps the native inference kernels hard-code; a model
+    built with another eps takes the PyTorch composite.  The norm layers are looked up once per module object."""
+    norms = module.__dict__.get("_native_norms")
+    if norms is None:
+        norms = [m for m in module.modules() if isinstance(m, (nn.modules.batchnorm._BatchNorm, nn.GroupNorm))]
+        module.__dict__["_native_norms"] = norms
+    # compared as float32: RED's kernels use 1e-5f, and an eps that went through a float32 (a checkpoint's, np.float32(1e-5))
+    # is the same model, not one for the slower composite
+    return all(_f32(m.eps) == _f32(_NATIVE_NORM_EPS) for m in norms)
 
 
 # ---- small conv wrappers (parameter names: .conv / .bn) ----------------------------------------------
@@ -385,6 +405,8 @@ class _REDCore(nn.Module):
             return False
         if not cost.is_cuda or cost.dtype is not torch.float32 or self.base_channels != 8 or cost.dim() != 4:
             return False
+        if not _norm_eps_native(self):        # the kernels normalise with eps = 1e-5
+            return False
         if _autograd_needed(cost, _tensors_by_path(self, self._PARAM_ORDER)):
             return False
         b, c, h, w = cost.shape
@@ -626,6 +648,8 @@ class CostRegNet(nn.Module):
             return False
         if not x.is_cuda or self.training or x.dim() != 5 or self.conv0.conv.out_channels != 8:
             return False
+        if not _norm_eps_native(self):        # the BatchNorm fold uses eps = 1e-5
+            return False
         if _autograd_needed(x, _tensors_by_path(self, self._names())):
             return False
         b, c, d, h, w = x.shape
@@ -739,6 +763,8 @@ class FeatureNet(nn.Module):
         if SW.force_composite("FEATNET"):     # A/B switch: force the stock PyTorch composite
             return False
         if not x.is_cuda or self.training or self.num_stage != 3 or self.base_channels > 16 or x.dim() < 4:
+            return False
+        if not _norm_eps_native(self):        # the BatchNorm fold uses eps = 1e-5
             return False
         if _autograd_needed(x, _tensors_by_path(self, self._names())):
             return False
