@@ -271,8 +271,8 @@ class ConvGRUCell2(nn.Module):
         # (a .double() model, exotic channel counts that leave a gate half unaligned, B*C > 65535) takes torch's operators
         native = (x.is_cuda and x.dtype is torch.float32 and h.dtype is torch.float32 and gates.dtype is torch.float32
                   and x.shape[0] * gates.shape[1] <= 65535)
-        if native and not (SW.train_composite_mask & 1):              # both gate norms + sigmoids: one native call each way
-            rn, un = self.reset_gate_norm, self.update_gate_norm
+        if native and not (SW.train_composite_mask & 1) and rn.eps == un.eps and rn.affine and un.affine:
+            # both gate norms + sigmoids: one native call each way (it takes one eps: norms that differ there go one by one)
             r, u = torch.split(_GroupNormPairFn.apply(gates, rn.weight, rn.bias, un.weight, un.bias, rn.eps, 1), gates.shape[1] // 2, 1)
         else:
             r, u = torch.split(gates, gates.shape[1] // 2, 1)

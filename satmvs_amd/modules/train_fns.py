@@ -792,10 +792,11 @@ class _ConvGRUCellFn(torch.autograd.Function):
         _lib.launch(dev, "smvs_groupnorm1_bwd", dcand, craw, C * HW, cand, nw_, stats_o, 2, dcraw, C * HW, dn[0], dn[1],
                     _gn_scratch(dev, 2 * B * C * nseg), B, C, HW)
         _lib.launch(dev, "smvs_conv3x3_fwd", 0, dcraw, C, None, 0, _conv_packed(ow, 2, C, Cx + C), None, None, dxc, B, Cx + C, H, W, 0)
-        dow, dob = _wgrad_now_or_later(ctx.sink, ow, ob, x, rh, dcraw, 1)
+        need = ctx.needs_input_grad         # a frozen layer (weight and bias) records nothing: nobody would ever collect it from the sink
+        dow, dob = _wgrad_now_or_later(ctx.sink, ow, ob, x, rh, dcraw, 1) if need[8] or need[9] else (None, None)
         _lib.launch(dev, "smvs_gru_mul_cat_bwd_acc", dxc, r, h, dh_b, dru, B, Cx, C, HW)
         _lib.launch(dev, "smvs_groupnorm1_pair_bwd", dru, gates, ru, rw, uw, stats_g, 1, dgates, g4[0], g4[1], g4[2], g4[3],
                     _gn_scratch(dev, 4 * B * C * nseg), B, C, HW)
         _lib.launch(dev, "smvs_conv3x3_fwd", 0, dgates, 2 * C, None, 0, _conv_packed(gw, 2, 2 * C, Cx + C), None, dxc, dxc, B, Cx + C, H, W, 0)
-        dgw, dgb = _wgrad_now_or_later(ctx.sink, gw, gb, x, h, dgates, 1)
+        dgw, dgb = _wgrad_now_or_later(ctx.sink, gw, gb, x, h, dgates, 1) if need[2] or need[3] else (None, None)
         return dxc[:, :Cx], dxc[:, Cx:], dgw, dgb, g4[0], g4[1], g4[2], g4[3], dow, dob, dn[0], dn[1], None
