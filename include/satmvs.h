@@ -1195,6 +1195,44 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   table both or neither; gw, gh >= 1, gw * gh <= 2^24; 1 <= rounds <= 4096; L and table in range; reverse 0 or 1; inputs,
  *   outputs and workspace do not overlap; workspace: smvs_dsm_cost_workspace_bytes(gw, gh) (0 = unsupported arguments): 16 KB
  *   of round counters, 1 KB for the table and 4 bytes per 256 cells.  No kernel uses scratch. */
+/* Seeded flood ("Seeded flood"): grey-scale geodesic reconstruction, a flood from chosen cells at chosen
+ * levels, and its back-links as a D8 direction grid: the marker watershed.  Integer arithmetic throughout.
+ *   Cells, heights.  As in "Hydrology": a cell is valid iff it is finite, != (float)nodata, |z| <= 32768, and its domain byte is
+ *   non-zero when a domain (gh, gw) uint8 is given.  q = llrint(256 z), halves to even; g = polarity q with polarity +1 or -1.
+ *   The neighbours are k = 0 .. 7 as there.  Invalid and off-grid neighbours are WALLS; they are not outlets.
+ *   Seeds.  marker (gh, gw) float32 with the same validity rule (finite, != nodata, |m| <= 32768).  A valid cell with a valid
+ *   marker is a seed at level s = max(g_c, polarity q(marker_c) + offset); offset is an int32 in quanta, |offset| <= 2^25.
+ *   Key.  K = (w, d), packed as the flood packs it, is the unique solution of
+ *     K(c) = max((g_c, 0), min(S_c, min over the valid neighbours n of K(n) + 1))
+ *   with S_c = (s, 0) at a seed and +infinity elsewhere, and +infinity + 1 = +infinity (saturating): a component without a seed
+ *   stays at exactly 0xfffffffe00000000 however many rounds run.  Every step strictly raises its argument, so no finite cycle
+ *   supports itself: a finite key hangs on a chain of strictly lower keys that ends at a seed with K = S, the solution is
+ *   unique, and Dijkstra from the seeds and any chaotic downward relaxation from (S, +infinity) reach it.  With polarity +1, w is
+ *   the reconstruction by erosion of the marker (clamped to the surface from above) over the surface; with polarity -1, -w is the
+ *   reconstruction by dilation of the marker (clamped from below) under it.
+ *   Back-link.  uint8 in the direction codes of "Hydrology": 255 at an invalid or unreached cell; 0 at a ROOT, a seed with
+ *   K(c) == S_c (the seed wins a tie against a neighbour); otherwise k + 1 for the neighbour with the least key, ties to the
+ *   lowest k.  Keys fall strictly along a link, so the links form a forest rooted at the roots, and smvs_dsm_flow_basins,
+ *   smvs_dsm_flow_accumulate and smvs_dsm_flow_length take it as it is.  (Keys that are no fixed point may leave a cell with no
+ *   lower neighbour: it gets 0.)
+ *   Reading.  surface: the cell's own z bits where w == g (untouched cells come back bit for bit), else (float)(polarity w /
+ *   256.0), exact.  level_steps: int32 d.  Invalid and unreached cells get (float)nodata, -1 and 255.  n_unreached, a device
+ *   int: the valid cells still at +infinity.
+ * smvs_dsm_seed_begin writes the keys the relaxation starts from (seeds (s, 0), other valid cells +infinity, invalid cells all
+ *   ones) and the number of seeds to n_seeds, a device int (block counts summed in a fixed order, no atomics).
+ *   smvs_dsm_seed_rounds runs `rounds` (1 .. 4096) global rounds and leaves in status (a device int) how many tiles changed in
+ *   the last one: 0 means the keys are the solution.  A round is one workgroup per tile of 32 x 32 cells, which relaxes the tile
+ *   in LDS against a halo of one cell until the tile is at its own fixed point and writes the interior back if anything moved.
+ *   Unlike the flood, all valid cells are open, seeds included, because another seed may undercut them; as keys only fall, the
+ *   rounds need no marker.  gw gh + 2 rounds bound any grid.  smvs_dsm_seed_read turns keys into surface, level_steps, backlink
+ *   and n_unreached (each may be null).  The three take the same dsm, nodata and polarity; begin and read the same marker,
+ *   domain and offset.  No host synchronisation in any entry.  Every workspace word a kernel reads was written by a kernel of
+ *   the same call; the only atomic is the per-launch counter of moved tiles: equal bits from run to run, for any batching of
+ *   the rounds, on any stream, and equal to the Python statement of this rule (tests/dsm_watershed_oracle.py).
+ * Limits (SMVS_ERR_ARG, checked before any HIP call): non-null dsm, marker, keys, n_seeds, status and workspace; polarity +1
+ *   or -1; gw, gh >= 1, gw * gh < 2^30; |offset| <= 2^25; 1 <= rounds <= 4096; no buffer written overlaps another buffer (the
+ *   inputs may overlap one another: h-maxima give the DSM as its own marker); workspace: smvs_dsm_seed_workspace_bytes(gw, gh)
+ *   (0 = unsupported arguments): 16 KB of round counters and 4 bytes per 256 cells.  No kernel uses scratch. */
 /* Meshes ("Meshes"): an error-bounded triangle mesh of a DSM, the adaptive right-triangulated irregular
  *   network (RTIN: longest-side bisection) over the lattice of cell centres, in integers throughout.
  *   Lattice.  The vertices are the cell centres (row r, col c) of a (gh, gw) float32 DSM with the heights of the exact tools:
@@ -1452,6 +1490,17 @@ int smvs_dsm_cost_read(const unsigned short* friction /* may be null */, const f
                        float nodata, const int* L /* HOST, 8 */, const int* table /* HOST, 256; null iff dsm is */,
                        int reverse, const unsigned long long* keys, unsigned long long max_cost,
                        long long* raw /* may be null */, double* cost /* may be null */, unsigned char* backlink /* may be null */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t smvs_dsm_seed_workspace_bytes(int gw, int gh);
+int smvs_dsm_seed_begin(const float* dsm, const float* marker, const unsigned char* domain /* may be null */, int gw, int gh,
+                        float nodata, int polarity, int offset, unsigned long long* keys, int* n_seeds,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_seed_rounds(const float* dsm, int gw, int gh, float nodata, int polarity, unsigned long long* keys, int rounds,
+                         int* status, void* workspace, size_t workspace_bytes, void* stream);
+int smvs_dsm_seed_read(const float* dsm, const float* marker, const unsigned char* domain /* may be null */, int gw, int gh,
+                       float nodata, int polarity, int offset, const unsigned long long* keys,
+                       float* surface /* may be null */, int* level_steps /* may be null */,
+                       unsigned char* backlink /* may be null */, int* n_unreached /* may be null */,
                        void* workspace, size_t workspace_bytes, void* stream);
 size_t smvs_dsm_mesh_workspace_bytes(int gw, int gh, int tile);
 int smvs_dsm_mesh_errors(const float* dsm, int gw, int gh, float nodata, int tile, long long* errors, void* stream);

@@ -128,6 +128,9 @@ _SIGNATURES = {
     "smvs_dsm_cost_begin": [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_cost_rounds": [_vp, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp],
     "smvs_dsm_cost_read": [_vp, _vp, _i, _i, _f, _vp, _vp, _i, _vp, C.c_ulonglong, _vp, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_seed_begin": [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "smvs_dsm_seed_rounds": [_vp, _i, _i, _f, _i, _vp, _i, _vp, _vp, _sz, _vp],
+    "smvs_dsm_seed_read": [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_mesh_errors": [_vp, _i, _i, _f, _i, _vp, _vp],
     "smvs_dsm_mesh_count": [_vp, _vp, _i, _i, _f, _i, C.c_longlong, _vp, _vp, _sz, _vp],
     "smvs_dsm_mesh_write": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
@@ -154,6 +157,7 @@ _SIZE_FUNCS = {"smvs_rpc_plane_coef_bytes": [_i] * 3, "smvs_red_packed_floats": 
                "smvs_dsm_simplify_workspace_bytes": [_i] * 2, "smvs_dsm_contour_workspace_bytes": [_i] * 4,
                "smvs_dsm_flood_workspace_bytes": [_i] * 2, "smvs_dsm_flow_workspace_bytes": [_i] * 2,
                "smvs_dsm_stream_workspace_bytes": [_i] * 2, "smvs_dsm_cost_workspace_bytes": [_i] * 2,
+               "smvs_dsm_seed_workspace_bytes": [_i] * 2,
                "smvs_dsm_mesh_workspace_bytes": [_i] * 3,
                "smvs_dsm_facet_workspace_bytes": [_i] * 2,
                "smvs_sgm_census_workspace_bytes": [_i] * 3}

@@ -78,6 +78,14 @@ and distance over ground that is not uniformly passable: accumulated cost, the s
     served_by, n = cost_allocation(backlink)                   # = basins(backlink): the source each cell's cheapest trip ends at
     paths = least_cost_paths(backlink, targets, grid)          # the trips of the targets as merged links, into write_streams()
 
+and objects that have merged into one blob split at their saddles: a flood from chosen cells at chosen levels (the seeded flood):
+
+    lower = h_maxima(above, 2.0)                               # every dome cut down to what stands less than 2 m over its saddle
+    tops, n, table, dome = peaks(above, 2.0, grid)             # the top plateaus of the domes with a prominence of 2 m or more
+    segments = watershed(above, tops, mask=above > 2.5)        # every cell to the peak it is reached from over the highest pass
+    labels, n, table = split_objects(above, grid, h=2.0)       # extract_objects -> peaks -> watershed; into outlines(), write_geojson()
+    rec = reconstruct(marker, dsm, "dilation")                 # the building block; "erosion"; h_minima(); open_by_reconstruction()
+
 and the surface itself as a triangle mesh with a guaranteed error (adaptive RTIN), for viewers, engines, printing, texturing:
 
     errors = mesh_errors(dtm, tile=256)                        # once per DSM: the exact error of every hierarchy triangle, saturated
@@ -157,6 +165,10 @@ per round through a scan of junction marks at their tour positions, and find eve
 doubling; smvs_dsm_flow_length is one doubling over the forest with the three step counts as sums.
 smvs_dsm_cost_begin / _rounds / _read are the flood's relaxation with another step rule: uint64 accumulated costs over the same
 tiles, the eight integer step costs of a lane's cells in registers, the back-links read off the final keys one lane per cell.
+smvs_dsm_seed_begin / _rounds / _read are the flood's relaxation with other ends: a valid cell with a valid marker is a seed at
+level s = max(g, polarity q(marker) + offset), K = max((g, 0), min(S, min over the valid neighbours of K + 1)) with +infinity + 1 =
++infinity, invalid and off-grid neighbours are walls, all valid cells are open (another seed may undercut a seed), and the
+back-links (0 at a seed with K = S, else the neighbour with the least key, ties to the lowest k) are a D8 forest for basins().
 smvs_dsm_mesh_errors is one lane per lattice vertex over all levels of the bisection hierarchy, the deviation from each
 triangle's plane raised into its split vertex's word by 64-bit integer max atomics (a wave an 8 x 8 block, its lanes combined per
 split vertex first), then one gather pass per level; smvs_dsm_mesh_count / _write flag the emitted triangles per slot of the
@@ -2839,6 +2851,226 @@ def least_cost_paths(backlink, targets, grid=None, raw=None):
         at = _to_device(raw, dev=dev)[0][r, c]
         out["target_cost"] = torch.where(at < 0, torch.full((), float("inf"), dtype=torch.float64, device=dev), at.double() / COST_UNIT)
     return {k: _back(as_numpy, t) for k, t in out.items()}
+
+
+# ---- seeded flood: geodesic reconstruction, h-maxima, peaks by prominence, the marker watershed ------------------------------------
+RECONSTRUCT_METHODS = {"dilation": -1, "erosion": 1}              # the polarity of smvs_dsm_seed_*
+MAX_SEED_OFFSET = 2 ** 25                                         # |offset| of smvs_dsm_seed_begin, in quanta of 2^-8 m
+MAX_H_QUANTA = 2 ** 24                                            # floor(256 h) of h_maxima(), h_minima(), peaks()
+
+
+def _domain_checked(mask, shape):
+    """A mask of the flood's domain (None: every cell), checked before any device work."""
+    if mask is None:
+        return None
+    mask = _mask_checked(mask)
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError("mask shape %s differs from the DSM's %s" % (tuple(mask.shape), tuple(shape)))
+    return mask
+
+
+def _domain(mask, dev):
+    """A checked mask -> uint8 on dev (None stays None)."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor):
+        mask = np.not_equal(mask, 0).view(np.uint8)
+    return (_to_device(mask, dev=dev)[0] != 0).to(torch.uint8).contiguous()
+
+
+def _h_quanta(h):
+    """floor(256 h) of a prominence [m], 1 .. 2^24."""
+    h = _finite(h, "h")
+    quanta = int(math.floor(h * 256.0))
+    if not 1 <= quanta <= MAX_H_QUANTA:
+        raise ValueError("floor(256 h) must be in 1 .. 2^24 (h from 2^-8 m to 65536 m), got h = %r" % h)
+    return quanta
+
+
+def _seed_flood(z, marker, domain, nodata, polarity, offset, batch=None, surface=False, steps=False, link=False):
+    """The seeded flood of device grids (include/satmvs.h, "Seeded flood") -> dict: the outputs asked for, and "rounds"."""
+    dev = z.device
+    gh, gw = z.shape
+    nbytes = _lib.load().smvs_dsm_seed_workspace_bytes(gw, gh)
+    if nbytes == 0:
+        raise ValueError("unsupported flood: %d x %d cells" % (gw, gh))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    keys = torch.empty((gh, gw), dtype=torch.int64, device=dev)
+    word = torch.empty(2, dtype=torch.int32, device=dev)
+    _call(dev, "smvs_dsm_seed_begin", z, marker, domain, gw, gh, nodata, polarity, offset, keys, word[:1], ws, nbytes)
+
+    def rounds(step):
+        _call(dev, "smvs_dsm_seed_rounds", z, gw, gh, nodata, polarity, keys, step, word[1:], ws, nbytes)
+        return int(word[1].item())
+    out = {"rounds": _relax(rounds, gw * gh, "smvs_dsm_seed_rounds", batch)}
+    out["surface"] = torch.empty_like(z) if surface else None
+    out["steps"] = torch.empty((gh, gw), dtype=torch.int32, device=dev) if steps else None
+    out["link"] = torch.empty((gh, gw), dtype=torch.uint8, device=dev) if link else None
+    _call(dev, "smvs_dsm_seed_read", z, marker, domain, gw, gh, nodata, polarity, offset, keys, out["surface"], out["steps"], out["link"], None, ws, nbytes)
+    return out
+
+
+def _reconstruct(marker, surface, polarity, offset, mask, nodata, return_steps, return_link, return_rounds, batch):
+    surface = _hydro_dsm(surface)
+    marker = _dsm_bits(marker)
+    if tuple(marker.shape) != tuple(surface.shape):
+        raise ValueError("marker shape %s differs from the surface's %s" % (tuple(marker.shape), tuple(surface.shape)))
+    mask = _domain_checked(mask, surface.shape)
+    if batch is not None:
+        batch = _int_checked(batch, "batch", 1, MAX_FLOOD_BATCH)
+    z, as_numpy = _to_device(surface)
+    m = z if marker is surface else _to_device(marker, dev=z.device)[0]
+    got = _seed_flood(z, m, _domain(mask, z.device), float(nodata), polarity, offset, batch, True, return_steps, return_link)
+    out = (got["surface"],) + ((got["steps"],) if return_steps else ()) + ((got["link"],) if return_link else ())
+    out = _back(as_numpy, *out)
+    if not return_rounds:
+        return out
+    return (out if isinstance(out, tuple) else (out,)) + (got["rounds"],)
+
+
+def reconstruct(marker, surface, method="dilation", mask=None, nodata=-999.0, return_steps=False, return_link=False, return_rounds=False,
+                batch=None):
+    """Grey-scale geodesic reconstruction (include/satmvs.h, "Seeded flood") of `marker` under
+    (method="dilation") or over ("erosion") `surface`: both (gh, gw) float32, never converted, fewer than 2^30 cells; valid =
+    finite, != nodata, |z| <= 32768 m, and inside `mask` (bool or integer, non-zero = inside) when one is given.  Heights count
+    in steps of 2^-8 m.  The marker is clamped to the surface (from below for the dilation, from above for the erosion); a valid
+    cell with a valid marker is a seed, and the result at a cell is the best level a path from any seed reaches it at: for the
+    dilation the highest min(marker at the seed, lowest surface along the path), 8-connected; invalid cells are walls.  A cell
+    whose result is the surface comes back with the surface's own bits, every other one as a multiple of 2^-8 m; invalid cells
+    and cells no seed reaches (a component without a valid marker) come back as nodata.
+    -> the reconstruction (gh, gw) float32; with return_steps also steps (gh, gw) int32, the steps within the flat from where
+    the level was set (-1 where nodata); with return_link also the back-links (gh, gw) uint8 in the codes of flow_direction()
+    ("index"): 0 at a root (a seed nothing undercut), k + 1 towards the neighbour the flood came from, 255 where nodata: a
+    forest that basins(), flow_length() and flow_accumulation() take; with return_rounds also the global rounds run.  The host
+    reads the device's status once per batch of rounds (8, then doubling; batch=k fixes it).  Every bit depends on the inputs
+    alone.  numpy if the surface came as numpy, device tensors otherwise."""
+    if method not in RECONSTRUCT_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(RECONSTRUCT_METHODS), method))
+    return _reconstruct(marker, surface, RECONSTRUCT_METHODS[method], 0, mask, nodata, return_steps, return_link, return_rounds, batch)
+
+
+def h_maxima(dsm, h, mask=None, nodata=-999.0, return_rounds=False, batch=None):
+    """The h-maxima transform: the reconstruction by dilation of dsm - h under dsm, which cuts every dome down to what stands
+    less than h above its saddle.  One reconstruction with the DSM as its own marker and the offset floor(256 h) quanta (1 ..
+    2^24) added on the device in integers: no float32 subtraction is formed on the host.  The other arguments and the result
+    as reconstruct()."""
+    return _reconstruct(dsm, dsm, -1, _h_quanta(h), mask, nodata, False, False, return_rounds, batch)
+
+
+def h_minima(dsm, h, mask=None, nodata=-999.0, return_rounds=False, batch=None):
+    """The h-minima transform: the reconstruction by erosion of dsm + h over dsm, which fills every pit up to h above its
+    floor.  As h_maxima(), with the other polarity."""
+    return _reconstruct(dsm, dsm, 1, _h_quanta(h), mask, nodata, False, False, return_rounds, batch)
+
+
+def _first_cells(lab, n):
+    """The first cell in raster order of the labels 1 .. n of a device label map -> int64 (n) flat indices (gh gw where absent)."""
+    cells = lab.numel()
+    first = torch.full((n + 1,), cells, dtype=torch.int64, device=lab.device)
+    flat = lab.reshape(-1).long().clamp(min=0, max=n)
+    first.scatter_reduce_(0, flat, torch.arange(cells, device=lab.device), "amin")
+    return first[1:]
+
+
+def peaks(dsm, h, grid=None, mask=None, min_height=None, connectivity=8, nodata=-999.0):
+    """The peaks of a DSM by prominence: the cells where q - q(h_maxima(dsm, h)) == floor(256 h), the top plateaus of every dome
+    that stands at least h above the saddle to higher ground (or has none inside its component), found by one reconstruction.
+    With mask the flood stays inside it; with min_height only plateau cells with dsm > float32(min_height) count.
+    -> (labels (gh, gw) int32, n, table, dome): the plateaus numbered by label(connectivity); table, from label_stats(): first
+    int32 (n, 2) the (row, col) of every plateau's first cell in raster order, area int32 [cells], height float32, and with
+    grid (a DSMGrid of that shape) east, north float64 of the first cell's centre; dome (gh, gw) float32 = dsm - h_maxima,
+    exact (a multiple of 2^-8 m in 0 .. h), nodata where the DSM has no height.  The exact prominence of each peak is out of
+    scope.  numpy if the DSM came as numpy, device tensors otherwise."""
+    dsm = _hydro_dsm(dsm, grid)
+    quanta = _h_quanta(h)
+    connectivity = _connectivity_checked(connectivity)
+    if min_height is not None:
+        min_height = _finite(min_height, "min_height")
+    mask = _domain_checked(mask, dsm.shape)
+    z, as_numpy = _to_device(dsm)
+    dev = z.device
+    got = _seed_flood(z, z, _domain(mask, dev), float(nodata), -1, quanta, None, True, True)
+    reached = got["steps"] >= 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    dome_q = torch.where(reached, torch.round(z.double() * 256.0) - torch.round(got["surface"].double() * 256.0), zero)
+    top = reached & (dome_q == float(quanta))
+    if min_height is not None:
+        top &= z > float(np.float32(min_height))
+    dome = torch.where(reached, (dome_q / 256.0).float(), torch.full_like(z, float(np.float32(nodata))))
+    labels, n = label(top, connectivity)
+    stats = label_stats(labels, n, values=z, nodata=nodata)
+    first = _first_cells(labels, n)
+    gw = z.shape[1]
+    row, col = torch.div(first, gw, rounding_mode="floor"), first % gw
+    table = {"first": torch.stack([row, col], dim=1).to(torch.int32), "area": stats["area"], "height": stats["max"]}
+    if grid is not None:
+        table["east"] = float(grid.e0) + col.double() * float(grid.xres)
+        table["north"] = float(grid.n0) - row.double() * float(grid.yres)
+    return _back(as_numpy, labels), n, {k: _back(as_numpy, t) for k, t in table.items()}, _back(as_numpy, dome)
+
+
+def watershed(surface, markers, mask=None, peaks_up=True, nodata=-999.0, return_level=False):
+    """The marker watershed of a surface (include/satmvs.h, "Seeded flood"): surface (gh, gw) float32, never converted; markers
+    (gh, gw) int32, > 0 = a marker cell with that label (from peaks(), label(), or any map); mask as in reconstruct().  The
+    surface is flooded from the marker cells at their own height, downwards from the peaks (peaks_up=True: objects on an nDSM)
+    or upwards from the pits (False: catchment basins), every cell is reached over the lowest pass (the highest, peaks up), and
+    ties go by the steps within a flat and then to the lowest neighbour number, so touching objects part along their saddles.
+    The segments are basins() of the flood's back-links, each given the marker label at its root; the roots are the marker cells
+    in row-major order.  -> (gh, gw) int32 in the markers' numbering, 0 where a cell is invalid, outside the mask or reached
+    by no marker; with return_level also level (gh, gw) float32, the pass height at which the cell was reached (its own bits
+    where that is the cell's height, nodata where the label is 0).  numpy if the surface came as numpy, device tensors
+    otherwise."""
+    surface = _hydro_dsm(surface)
+    markers = _labels_checked(markers)
+    if tuple(markers.shape) != tuple(surface.shape):
+        raise ValueError("markers shape %s differs from the surface's %s" % (tuple(markers.shape), tuple(surface.shape)))
+    mask = _domain_checked(mask, surface.shape)
+    z, as_numpy = _to_device(surface)
+    dev = z.device
+    mk = _to_device(markers, dev=dev)[0]
+    seeds = torch.where(mk > 0, z, torch.full_like(z, float("nan")))
+    got = _seed_flood(z, seeds, _domain(mask, dev), float(nodata), -1 if peaks_up else 1, 0, None, return_level, False, True)
+    basin, _ = basins(got["link"])
+    roots = torch.nonzero(got["link"].reshape(-1) == 0)[:, 0]
+    lut = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev), mk.reshape(-1)[roots]])
+    out = lut[basin.long()]
+    return _back(as_numpy, out, got["surface"]) if return_level else _back(as_numpy, out)
+
+
+def split_objects(above, grid, h=2.0, min_height=2.5, min_area_m2=50.0, connectivity=8, nodata=-999.0):
+    """The objects of an nDSM, split where they merge: extract_objects(above, grid, min_height, min_area_m2) -> peaks(above, h,
+    mask = objects > 0) -> watershed(above, peaks, mask = objects > 0), so that a terrace of houses, or a building and the trees
+    that touch it, part along their saddles wherever both sides stand at least h above the saddle.  The segments are renumbered
+    1 .. n in raster order of their first cells, label()'s numbering.  h = 2 m was chosen on a synthetic scene and is NOT tuned
+    on real data; smoothing beforehand (focal_median()) is the caller's business: noise of more than h splits a roof.
+    -> (labels (gh, gw) int32, n, table): table is label_stats(labels, n, values=above, grid=grid) plus `object` int32 (n), the
+    label of extract_objects() under every segment.  outlines(), write_geojson() and label_quantiles() take the result as it
+    is.  numpy if `above` came as numpy, device tensors otherwise."""
+    above = _on_grid(_hydro_dsm(above), grid)
+    _h_quanta(h)
+    connectivity = _connectivity_checked(connectivity)
+    min_height, min_area_m2 = _finite(min_height, "min_height"), _finite(min_area_m2, "min_area_m2")
+    if min_area_m2 < 0.0:
+        raise ValueError("min_area_m2 must be finite and >= 0, got %r" % min_area_m2)
+    z, as_numpy = _to_device(above)
+    objects, _ = extract_objects(z, grid, min_height, min_area_m2, connectivity, nodata)
+    inside = objects > 0
+    tops, n, _, _ = peaks(z, h, mask=inside, connectivity=connectivity, nodata=nodata)
+    seg = watershed(z, tops, mask=inside, nodata=nodata)
+    first = _first_cells(seg, n)
+    order = torch.argsort(first)
+    new_id = torch.zeros(n + 1, dtype=torch.int32, device=z.device)
+    new_id[order + 1] = torch.arange(1, n + 1, dtype=torch.int32, device=z.device)
+    labels = new_id[seg.long()]
+    table = label_stats(labels, n, values=z, grid=grid, nodata=nodata)
+    table["object"] = objects.reshape(-1)[first[order]]
+    return _back(as_numpy, labels), n, {k: _back(as_numpy, t) for k, t in table.items()}
+
+
+def open_by_reconstruction(dsm, radius, nodata=-999.0):
+    """reconstruct(morph(dsm, radius, "open"), dsm): the opening that removes what a (2 radius + 1)^2 square does not fit into
+    and does not round the corners of what it keeps.  -> (gh, gw) float32, as reconstruct()."""
+    return reconstruct(morph(dsm, radius, "open", nodata), dsm, nodata=nodata)
 
 
 # ---- meshes: the error-bounded triangulation of a DSM (adaptive RTIN), PLY and OBJ -----------------------------------------------
