@@ -811,6 +811,38 @@ int smvs_featnet_fwd(const float* packed, const float* imgs, float* stage1, floa
  *   >= 1 and below 2^31 cells; |ox|, |oy| < 2^30; mode 0 .. 5; in mode 5 1 <= feather <= 1024 and every d2 non-null (feather
  *   and d2 are ignored otherwise); out, count, source and spread distinct from each other and from every layer buffer.
  *
+ * Stack fusion (csrc/dsm_stack.hip): order statistics along the layer axis.  Layers are smvs_dsm_layer records exactly as
+ *   smvs_dsm_mosaic takes them: a HOST array of 1 .. 64 layers, z on the device and read only, d2 ignored (it may be null);
+ *   layer k's cell (r, c) lies on destination cell (r + oy_k, c + ox_k), |ox|, |oy| < 2^30, and what falls off the destination
+ *   is ignored.  A layer cell is valid iff it is finite and != (float)nodata.  For a destination cell V is the list of the
+ *   layers valid there in ascending k, m = |V|.  Order is that of the keys of the zonal and focal order statistics (-0.0 below
+ *   +0.0), duplicates count, and a selected value is one of the input values with its own bits.
+ * smvs_dsm_stack_select: levels is a HOST array of n_levels pairs (num, den).  For level j, in integers as dsm.quantile_ranks
+ *   states them: h = (m - 1) num, lo_rank = h / den, hi_rank = lo_rank + (h % den > 0).  lo[j] and hi[j], float32 (n_levels,
+ *   gh, gw), are the values of those 0-based ranks among V, (float)nodata where m = 0.  count (uint8 (gh, gw)) gets m; count
+ *   and hi may be null.  Deviation mode: with centre non-null, (gh, gw) float32 (device), the selection at cell p runs on
+ *   d = (float)fabs((double)z - (double)centre[p]): one float64 subtraction, one fabs, one rounding, not contracted.  Validity
+ *   is still decided on z (a d that rounds to +Inf is selected as such); a p whose centre is not finite has m = 0.  This is
+ *   smvs_dsm_focal_select's deviation rule.
+ * smvs_dsm_stack_fuse: the robust fusion of the stack, in this operation order.  With a and b the order statistics (m - 1) / 2
+ *   and (m - 1) / 2 + rem of V, rem = (m - 1) % 2: M64 = a + (b - a) (rem / 2) in float64, each operation rounded by itself
+ *   (the "linear" quantile at 1/2); med32 = (float)M64.  d_k = (float)fabs((double)z_k - (double)med32) for k in V; D64 is the
+ *   same linear median over the d_k, mad32 = (float)D64 (a NaN where both middle deviations are +Inf).  thr = fmax(kmad
+ *   (double)mad32, floor): a NaN product loses, as in C fmax.  Layer k of V is an inlier iff (double)d_k <= thr; n_in counts
+ *   them.  S is the float64 sum of (double)z_k over the inliers in ascending k, STARTED FROM ITS FIRST TERM; out = (float)(S /
+ *   n_in), and med32 if n_in = 0 (even m, two different middle values and a small threshold).  One layer alone therefore comes
+ *   back bit for bit in out.  out, median = med32 and mad = mad32 are float32 (gh, gw); count = m and n_in are uint8; members
+ *   and inliers are int64 with bit k set for "layer k is valid here" and "layer k is an inlier here".  Where m < max(min_count,
+ *   1): out, median and mad get (float)nodata, n_in, members and inliers 0, count still m.  Every output but out may be null;
+ *   the entry writes every element of those given.
+ *   Both entries: one launch, one lane per destination cell, the layer table in the kernel arguments, the lane's sorted keys in
+ *   n_layers KiB of LDS per workgroup; no workspace, atomics, state or host read-back, any stream; selections and sums in a
+ *   fixed order: equal bits from run to run and with the numpy statement of this rule.
+ *   Limits (SMVS_ERR_ARG, checked before any HIP call, nothing written): non-null layers, every z, levels and lo (select), out
+ *   (fuse); 1 <= n_layers <= 64; 1 <= n_levels <= 8, 0 <= num <= den, 1 <= den <= 2^16; kmad and floor finite and >= 0;
+ *   0 <= min_count <= 64; every size >= 1 and below 2^31 cells; |ox|, |oy| < 2^30; the outputs distinct from each other, from
+ *   centre and from every layer's z.
+ *
  * Sun (csrc/dsm_sun.hip).
  * smvs_dsm_shadow: cast shadows as an exclusive running maximum along lines of cells that run towards the sun.  dsm (gh, gw)
  *   float32 (device), read only; a cell is valid iff it is finite and != (float)nodata, as above.  (ucol, urow) is the
@@ -1407,6 +1439,15 @@ int smvs_dsm_dist(const unsigned char* mask, int gw, int gh, int border, int max
                   int* d2, void* workspace, size_t workspace_bytes, void* stream);
 int smvs_dsm_mosaic(const smvs_dsm_layer* layers, int n_layers, float nodata, int mode, int feather,
                     int gw, int gh, float* out, unsigned char* count, unsigned char* source, float* spread, void* stream);
+int smvs_dsm_stack_select(const smvs_dsm_layer* layers, int n_layers, float nodata,
+                          const int* levels /* host, n_levels x 2: num, den */, int n_levels,
+                          const float* centre /* device (gh, gw), may be null */,
+                          int gw, int gh, unsigned char* count /* may be null */,
+                          float* lo, float* hi /* (n_levels, gh, gw); hi may be null */, void* stream);
+int smvs_dsm_stack_fuse(const smvs_dsm_layer* layers, int n_layers, float nodata,
+                        double kmad, double floor, int min_count, int gw, int gh,
+                        float* out, float* median, float* mad, unsigned char* count, unsigned char* n_in,
+                        long long* members, long long* inliers /* all but out may be null */, void* stream);
 size_t smvs_dsm_shadow_workspace_bytes(int gw, int gh);
 int smvs_dsm_shadow(const float* dsm, int gw, int gh, float nodata,
                     double ucol, double urow, double a, double b, double tol,

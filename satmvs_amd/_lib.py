@@ -101,6 +101,8 @@ _SIGNATURES = {
     "smvs_dsm_regrid": [_vp, _i, _i, _vp, _f, _vp, _i, _i, _i, C.c_double, _vp, _vp],
     "smvs_dsm_dist": [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "smvs_dsm_mosaic": [_vp, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "smvs_dsm_stack_select": [_vp, _i, _f, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "smvs_dsm_stack_fuse": [_vp, _i, _f, C.c_double, C.c_double, _i, _i, _i] + [_vp] * 8,
     "smvs_dsm_shadow": [_vp, _i, _i, _f] + [C.c_double] * 5 + [_vp, _vp, _vp, _sz, _vp],
     "smvs_dsm_gradient": [_vp, _i, _i, _f, C.c_double, C.c_double, _vp, _vp, _vp],
     "smvs_dsm_horizon": [_vp, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp],

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libsatmvs_hip.so")
-SOURCES = ["costvol.hip", "costvol_fused.hip", "costvol_bwd.hip", "warp.hip", "regress.hip", "red.hip", "costreg.hip", "featnet.hip", "filter.hip", "groupnorm.hip", "conv_wgrad.hip", "batchnorm.hip", "dsm.hip", "dsm_render.hip", "dsm_post.hip", "dsm_morph.hip", "dsm_label.hip", "dsm_coreg.hip", "dsm_mosaic.hip", "dsm_sun.hip", "dsm_horizon.hip", "dsm_viewshed.hip", "dsm_outline.hip", "dsm_simplify.hip", "dsm_contour.hip", "dsm_hydro.hip", "dsm_stream.hip", "dsm_cost.hip", "dsm_watershed.hip", "dsm_mesh.hip", "dsm_facet.hip", "dsm_zonal.hip", "dsm_focal.hip", "dsm_rank.hip", "sgm.hip"]
+SOURCES = ["costvol.hip", "costvol_fused.hip", "costvol_bwd.hip", "warp.hip", "regress.hip", "red.hip", "costreg.hip", "featnet.hip", "filter.hip", "groupnorm.hip", "conv_wgrad.hip", "batchnorm.hip", "dsm.hip", "dsm_render.hip", "dsm_post.hip", "dsm_morph.hip", "dsm_label.hip", "dsm_coreg.hip", "dsm_mosaic.hip", "dsm_stack.hip", "dsm_sun.hip", "dsm_horizon.hip", "dsm_viewshed.hip", "dsm_outline.hip", "dsm_simplify.hip", "dsm_contour.hip", "dsm_hydro.hip", "dsm_stream.hip", "dsm_cost.hip", "dsm_watershed.hip", "dsm_mesh.hip", "dsm_facet.hip", "dsm_zonal.hip", "dsm_focal.hip", "dsm_rank.hip", "sgm.hip"]
 HEADERS = ["smvs_device.h", "smvs_host.h", "mfma_conv.h", "costvol_kernels.h", "dsm_common.h", "dsm_geo.h", "dsm_scan.h", "dsm_chain.h", "dsm_flow.h", "dsm_unionfind.h", os.path.join("..", "..", "include", "satmvs.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fvisibility=hidden", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

@@ -1,5 +1,5 @@
 // dsm_common.h -- what the DSM sources (dsm.hip, dsm_render.hip, dsm_post.hip, dsm_morph.hip, dsm_label.hip, dsm_coreg.hip,
-// dsm_mosaic.hip, dsm_sun.hip, dsm_horizon.hip, dsm_viewshed.hip, dsm_outline.hip, dsm_simplify.hip, dsm_contour.hip, dsm_hydro.hip,
+// dsm_mosaic.hip, dsm_stack.hip, dsm_sun.hip, dsm_horizon.hip, dsm_viewshed.hip, dsm_outline.hip, dsm_simplify.hip, dsm_contour.hip, dsm_hydro.hip,
 // dsm_stream.hip, dsm_cost.hip, dsm_watershed.hip, dsm_mesh.hip, dsm_facet.hip, dsm_zonal.hip, dsm_focal.hip, dsm_rank.hip) and the headers dsm_geo.h, dsm_chain.h and dsm_flow.h share: the validity test of a cell, the order-preserving uint32 image of a float, the register sorting
 // network, the height quantum of the exact tools, and on the host the grid-size and aliasing checks, the round and block counts and
 // the launch macro.

@@ -191,6 +191,8 @@ shifts' integer sums in registers; smvs_dsm_regrid is one lane per destination c
 smvs_dsm_dist is an exact squared Euclidean distance transform in two line passes (rows since the last background cell
 carried along columns, then a lower envelope searched outwards along rows in LDS); smvs_dsm_mosaic is one lane per
 destination cell over a table of up to 64 layers, float64 sums in the list's order.
+smvs_dsm_stack_select / _fuse are one lane per destination cell over the same table, the lane's valid keys kept sorted by
+insertion in its own column of LDS: every level is one read, the MAD a merge outwards from the median along that column.
 smvs_dsm_shadow is an exclusive running maximum of z - tan(elevation) (distance towards the sun) along sheared lines of
 the grid, a lane per line, cut into bands with an exact carry, the east-west directions between tile transposes through LDS;
 smvs_dsm_gradient is Horn's 3 x 3 gradient, one lane per cell.
@@ -3648,30 +3650,17 @@ def mosaic_grid(grids):
     return _grid_checked(out, "the mosaic's grid")
 
 
-def mosaic(dsms, grids, to_grid=None, mode="feather", feather=16, align=None, nodata=-999.0,
-           return_count=False, return_source=False, return_spread=False):
-    """Several DSMs put together on one grid (include/satmvs.h smvs_dsm_mosaic, DESIGN.md section 9, "Mosaic").  dsms[k] is
-    (grids[k].height, grids[k].width) of any real dtype (taken as float32), numpy or a device tensor; at most 64 layers;
-    to_grid=None means mosaic_grid(grids).  Where several layers are valid a destination cell takes, by `mode`, the "first" or
-    "last" of them in the list's order, the "min" or "max" (ties to the earlier layer), their "mean" (float64, in the list's
-    order), or the "feather" blend: the mean with the weights min(max(d, 1), feather), d the distance [cells] of the layer's
-    cell to the layer's nearest void or edge (smvs_dsm_dist of its validity mask with the border as background), so a tile
-    fades out over `feather` cells towards its seams instead of leaving a step there.  Cells no layer covers get nodata; one
-    layer alone comes back bit for bit in every mode.
-    A layer is aligned iff its xres and yres equal to_grid's and its offsets ox = (e0_k - e0_d) / xres, oy = (n0_d - n0_k) /
-    yres (float64) are within 1e-6 cell of integers -- a stated choice: world-file doubles at UTM magnitudes resolve about
-    1e-10 cell of 5 m, and 1e-6 cell is 5 micrometres.  An unaligned layer raises ValueError unless align = "nearest" or
-    "bilinear", which regrid()s it first onto the part of to_grid's lattice it covers.  The defaults (feather 16, 1e-6 cell)
-    are a choice for 5 m grids on a synthetic scene (DESIGN.md), not tuned on real data.
-    -> (to_grid.height, to_grid.width) float32, then with return_count uint8 the number of valid layers per cell, with
-    return_source uint8 the layer taken (first .. max) or weighing most (mean: the first valid; feather; 255 = none), with
-    return_spread float32 highest - lowest valid layer (the overlap-agreement map; nodata where none), in that order; numpy
-    if dsms[0] came as numpy, device tensors otherwise."""
-    if mode not in MOSAIC_MODES:
-        raise ValueError("mode must be one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
+def _align_checked(align):
     if align is not None and align not in REGRID_MODES:
         raise ValueError("align must be None or one of %s, got %r" % (sorted(REGRID_MODES), align))
-    feather = _int_checked(feather, "feather", 1, MAX_DIST)
+    return align
+
+
+def _plan_layers(dsms, grids, to_grid, align):
+    """Where the layers of a mosaic or a stack lie on the destination's lattice, as mosaic() states it; to_grid=None means
+    mosaic_grid(grids).  Host work only: every check is made before a device is asked for.
+    -> (to_grid, dsms, grids, plan), plan[k] = (ox, oy, None) of an aligned layer, (c0, r0, the sub-grid of to_grid's lattice to
+    regrid onto) of an unaligned one."""
     dsms = list(dsms)
     grids = _grids_checked(grids)
     if len(dsms) != len(grids):
@@ -3697,27 +3686,197 @@ def mosaic(dsms, grids, to_grid=None, mode="feather", feather=16, align=None, no
         sub = DSMGrid(float(to_grid.e0) + c0 * float(to_grid.xres), float(to_grid.n0) - r0 * float(to_grid.yres),
                       to_grid.xres, to_grid.yres, c1 - c0 + 1, r1 - r0 + 1)
         plan.append((c0, r0, sub))
+    return to_grid, dsms, grids, plan
+
+
+def _place_layers(dsms, grids, plan, align, nodata):
+    """The planned layers on the device, an unaligned one regrid()ded by `align` onto its sub-grid.
+    -> (dev, as_numpy, [(z float32 device tensor, ox, oy)]); the caller keeps the tensors alive until its call is enqueued."""
     as_numpy = not isinstance(dsms[0], torch.Tensor)
     dev = _dev() if as_numpy or not dsms[0].is_cuda else dsms[0].device
-    nd = float(np.float32(nodata))
-    table = (_Layer * len(dsms))()
-    held = []                                                # every layer's tensors, alive until the call is enqueued
-    for k, (z, g, (ox, oy, sub)) in enumerate(zip(dsms, grids, plan)):
+    layers = []
+    for z, g, (ox, oy, sub) in zip(dsms, grids, plan):
         z, _ = _to_device(z, torch.float32, dev)
         if sub is not None:
             z = regrid(z, g, sub, mode=align, nodata=nodata)
-        d2 = None
-        if mode == "feather":
-            d2 = _dist((torch.isfinite(z) & (z != nd)).to(torch.uint8), feather, True)
-        held.append((z, d2))
-        table[k] = _Layer(z.data_ptr(), d2.data_ptr() if d2 is not None else None, int(z.shape[1]), int(z.shape[0]), ox, oy)
+        layers.append((z, ox, oy))
+    return dev, as_numpy, layers
+
+
+def _layer_table(layers, d2=None):
+    """The smvs_dsm_layer records of _plan_layers()'s layers, d2[k] (or none) beside each."""
+    table = (_Layer * len(layers))()
+    for k, (z, ox, oy) in enumerate(layers):
+        table[k] = _Layer(z.data_ptr(), d2[k].data_ptr() if d2 is not None else None, int(z.shape[1]), int(z.shape[0]), ox, oy)
+    return table
+
+
+def mosaic(dsms, grids, to_grid=None, mode="feather", feather=16, align=None, nodata=-999.0,
+           return_count=False, return_source=False, return_spread=False):
+    """Several DSMs put together on one grid (include/satmvs.h smvs_dsm_mosaic, DESIGN.md section 9, "Mosaic").  dsms[k] is
+    (grids[k].height, grids[k].width) of any real dtype (taken as float32), numpy or a device tensor; at most 64 layers;
+    to_grid=None means mosaic_grid(grids).  Where several layers are valid a destination cell takes, by `mode`, the "first" or
+    "last" of them in the list's order, the "min" or "max" (ties to the earlier layer), their "mean" (float64, in the list's
+    order), or the "feather" blend: the mean with the weights min(max(d, 1), feather), d the distance [cells] of the layer's
+    cell to the layer's nearest void or edge (smvs_dsm_dist of its validity mask with the border as background), so a tile
+    fades out over `feather` cells towards its seams instead of leaving a step there.  Cells no layer covers get nodata; one
+    layer alone comes back bit for bit in every mode.
+    A layer is aligned iff its xres and yres equal to_grid's and its offsets ox = (e0_k - e0_d) / xres, oy = (n0_d - n0_k) /
+    yres (float64) are within 1e-6 cell of integers -- a stated choice: world-file doubles at UTM magnitudes resolve about
+    1e-10 cell of 5 m, and 1e-6 cell is 5 micrometres.  An unaligned layer raises ValueError unless align = "nearest" or
+    "bilinear", which regrid()s it first onto the part of to_grid's lattice it covers.  The defaults (feather 16, 1e-6 cell)
+    are a choice for 5 m grids on a synthetic scene (DESIGN.md), not tuned on real data.
+    -> (to_grid.height, to_grid.width) float32, then with return_count uint8 the number of valid layers per cell, with
+    return_source uint8 the layer taken (first .. max) or weighing most (mean: the first valid; feather; 255 = none), with
+    return_spread float32 highest - lowest valid layer (the overlap-agreement map; nodata where none), in that order; numpy
+    if dsms[0] came as numpy, device tensors otherwise."""
+    if mode not in MOSAIC_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
+    align = _align_checked(align)
+    feather = _int_checked(feather, "feather", 1, MAX_DIST)
+    to_grid, dsms, grids, plan = _plan_layers(dsms, grids, to_grid, align)
+    dev, as_numpy, layers = _place_layers(dsms, grids, plan, align, nodata)
+    gw, gh = int(to_grid.width), int(to_grid.height)
+    nd = float(np.float32(nodata))
+    d2 = None
+    if mode == "feather":
+        d2 = [_dist((torch.isfinite(z) & (z != nd)).to(torch.uint8), feather, True) for z, _, _ in layers]
+    table = _layer_table(layers, d2)
     out = torch.empty((gh, gw), dtype=torch.float32, device=dev)
     count = torch.empty((gh, gw), dtype=torch.uint8, device=dev) if return_count else None
     source = torch.empty((gh, gw), dtype=torch.uint8, device=dev) if return_source else None
     spread = torch.empty((gh, gw), dtype=torch.float32, device=dev) if return_spread else None
-    _call(dev, "smvs_dsm_mosaic", table, len(dsms), float(nodata), MOSAIC_MODES[mode], feather, gw, gh, out, count, source, spread)
-    del held
+    _call(dev, "smvs_dsm_mosaic", table, len(layers), float(nodata), MOSAIC_MODES[mode], feather, gw, gh, out, count, source, spread)
+    del layers, d2                                           # every layer's tensors, alive until the call is enqueued
     return _back(as_numpy, *([out] + [t for t in (count, source, spread) if t is not None]))
+
+
+# ---- stack fusion: order statistics along the layer axis -----------------------------------------------------------------------
+MAX_STACK_LEVELS = 8                                              # levels of one smvs_dsm_stack_select call
+
+
+def _stack_select(dev, table, n_layers, gw, gh, nodata, fr, centre):
+    """smvs_dsm_stack_select over the levels fr in chunks of 8 -> count uint8 (gh, gw), lo, hi float32 (Q, gh, gw).  A chunk without
+    a level between two ranks (num % den == 0 throughout) asks for no hi: it is lo."""
+    count = torch.empty((gh, gw), dtype=torch.uint8, device=dev)
+    lo = torch.empty((len(fr), gh, gw), dtype=torch.float32, device=dev)
+    hi = torch.empty_like(lo)
+    for s0 in range(0, len(fr), MAX_STACK_LEVELS):
+        chunk = fr[s0:s0 + MAX_STACK_LEVELS]
+        split = any(num % den != 0 for num, den in chunk)
+        _call(dev, "smvs_dsm_stack_select", table, n_layers, nodata, np.array(chunk, dtype=np.int32), len(chunk), centre, gw, gh,
+              count if s0 == 0 else None, lo[s0:s0 + len(chunk)], hi[s0:s0 + len(chunk)] if split else None)
+        if not split:
+            hi[s0:s0 + len(chunk)] = lo[s0:s0 + len(chunk)]
+    return count, lo, hi
+
+
+def _stack_quantiles(dev, table, n_layers, gw, gh, nodata, fr, method, centre, min_layers):
+    count, lo, hi = _stack_select(dev, table, n_layers, gw, gh, nodata, fr, centre)
+    lo_rank, _, rem, den = quantile_ranks(count.reshape(-1).to(torch.int32), fr)
+    grids = lambda t: t.t().reshape(lo.shape)                # (cells, Q) -> (Q, gh, gw)
+    value = _quantile_value(lo, hi, grids(lo_rank), grids(rem), den[:, None, None], method)
+    value = torch.where((count >= max(min_layers, 1))[None], value, torch.full_like(value, float("nan")))
+    return count, lo, hi, value
+
+
+def _stack_inputs(dsms, grids, to_grid, align, min_layers, nodata, centre=None):
+    """The checks and the planning the stack functions share, every check before any device work
+    -> (dev, as_numpy, layers, table, gw, gh, min_layers, centre on the device or None)."""
+    align = _align_checked(align)
+    min_layers = _int_checked(min_layers, "min_layers", 0, MAX_MOSAIC_LAYERS)
+    to_grid, dsms, grids, plan = _plan_layers(dsms, grids, to_grid, align)
+    gw, gh = int(to_grid.width), int(to_grid.height)
+    if centre is not None:
+        if not isinstance(centre, torch.Tensor):
+            centre = np.asarray(centre)
+        if tuple(centre.shape) != (gh, gw) or centre.dtype not in (np.float32, torch.float32):
+            raise ValueError("centre is float32 of the destination's shape (%d, %d), got %s %s" % (gh, gw, centre.dtype, tuple(centre.shape)))
+    dev, as_numpy, layers = _place_layers(dsms, grids, plan, align, nodata)
+    if centre is not None:
+        centre = _to_device(centre, dev=dev)[0]
+    return dev, as_numpy, layers, _layer_table(layers), gw, gh, min_layers, centre
+
+
+def stack_quantiles(dsms, grids, to_grid=None, q=(0.5,), method="linear", centre=None, align=None, min_layers=1, nodata=-999.0):
+    """Exact quantiles, cell by cell, of a stack of DSMs of the same ground (include/satmvs.h smvs_dsm_stack_select, DESIGN.md
+    section 9, "Stack fusion"): one per stereo pair, triplet, date or sgm_heights run.  dsms, grids, to_grid and align are
+    mosaic()'s, and so is the placing of the layers (at most 64); a layer counts at a cell iff its value there is finite and
+    != nodata.  q, method: as in label_quantiles().  With centre ((gh, gw) float32 of the destination) the statistics at cell p
+    are those of |z - centre[p]| (float64 difference, rounded to float32 once); a p whose centre is not finite has no layer.
+    -> dict: n_valid uint8 (gh, gw), the layers that count; lo, hi float32 (Q, gh, gw), the order statistics of
+    quantile_ranks() among them, layer values with their own bits (order: -0.0 below +0.0), nodata where n_valid is 0; value
+    float64 (Q, gh, gw) by `method`, NaN where n_valid < max(min_layers, 1).  Selection, no sums: equal bits from run to run.
+    numpy if dsms[0] came as numpy, device tensors otherwise."""
+    fr = _quantile_fractions(q)
+    if method not in QUANTILE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (QUANTILE_METHODS, method))
+    dev, as_numpy, layers, table, gw, gh, min_layers, c = _stack_inputs(dsms, grids, to_grid, align, min_layers, nodata, centre)
+    count, lo, hi, value = _stack_quantiles(dev, table, len(layers), gw, gh, float(nodata), fr, method, c, min_layers)
+    del layers                                               # every layer's tensor, alive until the calls are enqueued
+    return {k: _back(as_numpy, t) for k, t in (("n_valid", count), ("lo", lo), ("hi", hi), ("value", value))}
+
+
+def stack_median(dsms, grids, to_grid=None, align=None, min_layers=1, nodata=-999.0):
+    """The per-cell median DSM of a stack: (float) of the "linear" median of stack_quantiles() (for an even number of layers
+    lo + (hi - lo) 0.5 in float64), nodata where fewer than max(min_layers, 1) layers count.  Its bits are those of fuse_stack()'s
+    `median`.  -> (gh, gw) float32."""
+    dev, as_numpy, layers, table, gw, gh, min_layers, _ = _stack_inputs(dsms, grids, to_grid, align, min_layers, nodata)
+    count, _, _, value = _stack_quantiles(dev, table, len(layers), gw, gh, float(nodata), [(1, 2)], "linear", None, min_layers)
+    del layers
+    return _back(as_numpy, _focal_grid(value[0], count >= max(min_layers, 1), nodata))
+
+
+def stack_nmad(dsms, grids, to_grid=None, align=None, min_layers=1, nodata=-999.0):
+    """The robust centre and spread of a stack, cell by cell: focal_nmad()'s two selections along the layer axis.  median float64
+    (gh, gw), the linear median of stack_quantiles(); mad, the linear median of |z - float32(median)| over the same layers; nmad =
+    1.4826 mad; n_valid uint8.  NaN where n_valid < max(min_layers, 1); (float) of median and mad are fuse_stack()'s `median` and
+    `mad`.  -> dict."""
+    dev, as_numpy, layers, table, gw, gh, min_layers, _ = _stack_inputs(dsms, grids, to_grid, align, min_layers, nodata)
+    nd = float(nodata)
+    count, _, _, median = _stack_quantiles(dev, table, len(layers), gw, gh, nd, [(1, 2)], "linear", None, min_layers)
+    _, _, _, mad = _stack_quantiles(dev, table, len(layers), gw, gh, nd, [(1, 2)], "linear", median[0].float(), min_layers)
+    del layers
+    return dict(zip(("median", "mad", "nmad", "n_valid"), _back(as_numpy, median[0], mad[0], mad[0] * NMAD_FACTOR, count)))
+
+
+def fuse_stack(dsms, grids, to_grid=None, k=3.0, floor=0.5, min_layers=1, align=None, nodata=-999.0, return_info=False):
+    """A stack of DSMs of the same ground fused robustly, cell by cell (include/satmvs.h smvs_dsm_stack_fuse, DESIGN.md section 9,
+    "Stack fusion"): the mean (float64, in the list's order) of the layers within max(k nmad, floor) of the stack's median there,
+    nmad = 1.4826 mad, the median and the MAD those of stack_nmad() -- despike_robust()'s rule along the layer axis, so one cloud,
+    one mismatched pair or one new building does not move the cell.  dsms, grids, to_grid and align are mosaic()'s (at most 64
+    layers).  A cell with fewer than max(min_layers, 1) layers gets nodata; where no layer passes (an even number of layers, two
+    different middle values and a small k and floor) the cell gets the median; one layer alone comes back bit for bit.  The
+    threshold's factor k 1.4826 is formed here in float64.  The defaults (k 3, floor 0.5 m) are despike_robust()'s, chosen on a
+    synthetic scene and not tuned on real data.
+    -> (gh, gw) float32, and with return_info a dict beside it: median, mad float32; count, n_inliers uint8; members, inliers
+    int64 with bit j set where layer j counts / is an inlier (stack_outliers() reads them).  numpy if dsms[0] came as numpy."""
+    k, floor = _finite(k, "k"), _finite(floor, "floor")
+    if k < 0.0 or floor < 0.0:
+        raise ValueError("k and floor must be >= 0, got %r and %r" % (k, floor))
+    dev, as_numpy, layers, table, gw, gh, min_layers, _ = _stack_inputs(dsms, grids, to_grid, align, min_layers, nodata)
+    out = torch.empty((gh, gw), dtype=torch.float32, device=dev)
+    info = {}
+    if return_info:
+        for name, dtype in (("median", torch.float32), ("mad", torch.float32), ("count", torch.uint8), ("n_inliers", torch.uint8),
+                            ("members", torch.int64), ("inliers", torch.int64)):
+            info[name] = torch.empty((gh, gw), dtype=dtype, device=dev)
+    _call(dev, "smvs_dsm_stack_fuse", table, len(layers), float(nodata), k * NMAD_FACTOR, floor, min_layers, gw, gh, out,
+          *[info.get(name) for name in ("median", "mad", "count", "n_inliers", "members", "inliers")])
+    del layers
+    if not return_info:
+        return _back(as_numpy, out)
+    return _back(as_numpy, out), {name: _back(as_numpy, t) for name, t in info.items()}
+
+
+def stack_outliers(info, k):
+    """Where layer k of a fused stack disagrees with the consensus: 1 where it counts at the cell but is no inlier (a cloud, a
+    change, a mismatch), from the `members` and `inliers` of fuse_stack(..., return_info=True).  -> (gh, gw) uint8, of info's kind."""
+    k = _int_checked(k, "k", 0, MAX_MOSAIC_LAYERS - 1)
+    members, inliers = info["members"], info["inliers"]
+    if isinstance(members, torch.Tensor):
+        return (((members & ~inliers) >> k) & 1).to(torch.uint8)
+    return ((np.asarray(members) & ~np.asarray(inliers)) >> np.int64(k) & np.int64(1)).astype(np.uint8)
 
 
 # ---- orthophoto ---------------------------------------------------------------------------------------------------------------
